@@ -1,6 +1,11 @@
 """Benchmark of the hot path: batched tracking-QP solves on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--cpu-seconds S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints
+the result line.  --full adds everything else: the per-step latency pass, the solver telemetry, the roofline
+figures, the secondary legs (SQP, in-flight batches, closed loop, offline planner) and the CPU baselines; the
+options that size or skip those legs (--cpu-seconds, --no-cpu, --inflight, ...) act only with --full.
 
 A step = one launch of the batched solver over the config's ego batch (C2: trajectory1,
 N=20, B=4096 per GPU, seed 2; inputs resident in HBM).  Multi-GPU (one rank per GPU, started by
@@ -49,6 +54,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (u0, U, Xpred, status, iters of "
+                         "this rank's egos) as DIR/<name>.npy in float64 (ranks above 0: DIR/<name>.rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-step latency pass, solver "
+                         "telemetry, roofline figures, the secondary legs and the CPU baselines (the options below "
+                         "size or skip those and act only with --full)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--inflight", type=int, default=4, metavar="K",
@@ -165,6 +177,47 @@ def main():
     wall = time.perf_counter() - t0
     if gpu:
         gpu_s = ev0.elapsed_time(ev1) / 1e3
+    else:
+        step_ms = np.diff(np.array(tk)) * 1e3
+        gpu_s = float(step_ms.sum()) / 1e3
+    elapsed = comm.max(max(wall, gpu_s))
+    if args.dump_outputs:
+        last = dict(u0=u0, U=Uo, Xpred=Xo, status=st, iters=it) if gpu else host
+        dump_outputs(args.dump_outputs, rank, {k: v.cpu().numpy() if gpu else v for k, v in last.items()})
+    head = {
+        "metric": "tracking-QP solves/sec @ N=20, batch=4096; p50 solve latency",
+        "value": world * B * args.steps / elapsed,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "timing": "value / ms_per_step: the K timed steps back to back between two HIP events (max over ranks, "
+                  "bracketed by barrier + synchronize)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.config}: trajectory{wb['traj']}.json, N={N}, batch={B} egos per GPU, "
+                               f"max_obs={mo}, seed {cfg['seed']} (SURVEY 8d)", "global_batch": world * B,
+                   "horizon": N, "parallelism": f"dp{world} (ego shards)"},
+        "comm": {"transport": comm.transport,
+                 "note": "the ranks' exchange (barrier, max-over-ranks time; with --full the telemetry gather): "
+                         "'rccl' = libmpcqp's communicator (mpc_comm_*), 'local' = world 1, 'gloo' = the CPU "
+                         "stand-in"},
+    }
+    if not gpu:
+        head["device"] = "cpu-standin"
+        head["note"] = "--device cpu: libmpcqp's host backend with gloo, a stand-in for the launcher tests"
+    if not args.full:
+        # a plain run ends here: the headline figure and what it was measured on
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        comm.close()
+        return
+
+    if gpu:
         nlat = min(args.steps, 50)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(nlat + 1)]
         ev[0].record(stream)
@@ -173,10 +226,6 @@ def main():
             ev[i + 1].record(stream)
         sync()
         step_ms = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(nlat)])
-    else:
-        step_ms = np.diff(np.array(tk)) * 1e3
-        gpu_s = float(step_ms.sum()) / 1e3
-    elapsed = comm.max(max(wall, gpu_s))
 
     # the one collective: gather of per-rank solver telemetry (after the timed region)
     st_h = st.cpu().numpy() if gpu else host["status"]
@@ -218,29 +267,10 @@ def main():
             plan["fleet"] = {"error": f"{type(e).__name__}: {e}"}
 
     if rank == 0:
-        out = {
-            "metric": "tracking-QP solves/sec @ N=20, batch=4096; p50 solve latency",
-            "value": world * B * args.steps / elapsed,
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / args.steps,
+        out = dict(head)
+        out.update({
             "p50_batch_latency_ms": float(np.median(step_ms)),
-            "timing": "value / ms_per_step: the K timed steps back to back between two HIP events (max over ranks, "
-                      "bracketed by barrier + synchronize); p50: a second pass of min(K, 50) steps with an event "
-                      "after each",
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{args.config}: trajectory{wb['traj']}.json, N={N}, batch={B} egos per GPU, "
-                                   f"max_obs={mo}, seed {cfg['seed']} (SURVEY 8d)", "global_batch": world * B,
-                       "horizon": N, "parallelism": f"dp{world} (ego shards)"},
-            "comm": {"transport": comm.transport,
-                     "note": "the ranks' one exchange (barrier, max-over-ranks time, telemetry gather): 'rccl' = "
-                             "libmpcqp's communicator (mpc_comm_*), 'local' = world 1, 'gloo' = the CPU stand-in"},
+            "timing": head["timing"] + "; p50: a second pass of min(K, 50) steps with an event after each",
             "solver": tel,
             "roofline": {"bound": "fp64-valu", "achieved": flops / avg_launch_s / 1e12, "peak": FP64_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": flops / avg_launch_s / 1e12 / FP64_PEAK_TFLOPS,
@@ -263,11 +293,9 @@ def main():
                          "hbm_algorithmic_GBs": nbytes / avg_launch_s / 1e9,
                          "executed_frac": executed.get("executed_frac"), "valu_busy": executed.get("valu_busy"),
                          "executed": executed},
-        }
+        })
         if not gpu:
-            out["device"] = "cpu-standin"
-            out["note"] = ("--device cpu: libmpcqp's host backend with gloo, a stand-in for the launcher tests; "
-                           "the roofline fields are not a GPU measurement")
+            out["note"] += "; the roofline fields are not a GPU measurement"
         if args.nlp_steps > 0 and gpu:
             out["nlp_sqp"] = nlp_leg(args.nlp_steps, wb, B, N, mo, X, U, dev)
         if args.inflight > 1 and gpu:
@@ -284,6 +312,24 @@ def main():
             out["cpu_baseline"] = cpu_baseline(wb, N, mo, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     comm.close()
+
+
+def dump_outputs(dirname, rank, arrays):
+    """--dump-outputs: the arrays a caller of the timed path receives (mpcqp.Solver.solve_batch's names: u0 [B,2],
+    U [B,N,2], Xpred [B,N+1,5], status [B], iters [B]) from the last timed step, each as <name>.npy in float64
+    (the integer status and iteration counts are exact in it).  The configs' own batches make 5-19 MB; a --batch
+    whose arrays would pass 64 MB is cut to a fixed, seeded sample of its egos (the same rows of every array,
+    in order).  The inputs are a function of the arguments alone (workloads.make_batch, seeded by the config), so
+    two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    B = len(arrays["status"])
+    keep = int(64e6 // (8 * sum(a[0].size for a in arrays.values())))
+    rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False)) if B > keep else slice(None)
+    for name, a in arrays.items():
+        a = a[rows]
+        np.save(os.path.join(dirname, name + (f".rank{rank}" if rank else "") + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
 
 
 def launch_ranks(args):

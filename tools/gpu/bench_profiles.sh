@@ -3,8 +3,9 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 R=$GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py --steps 20 --warmup 3 --cpu-seconds 15 --closed-loop ${CL:-512} > gpurun_out/bench.log 2>&1 || { echo "bench failed"; tail gpurun_out/bench.log; exit 1; }
-tail -1 gpurun_out/bench.log
+OUT=${OUT:-$R/bench_out}; mkdir -p $OUT
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 15 --closed-loop ${CL:-512} > $OUT/bench.log 2>&1 || { echo "bench failed"; tail $OUT/bench.log; exit 1; }
+tail -1 $OUT/bench.log
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_stats $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_stats -o run --output-format csv -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu --inflight 0 --nlp-steps 0 --closed-loop 0 --plan-chunks 0 > $R/gpurun_out/prof_stats.log 2>&1 || { echo "stats failed"; tail $R/gpurun_out/prof_stats.log; exit 1; }

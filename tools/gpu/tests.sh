@@ -5,5 +5,6 @@ timeout -k 10 900 python -u -m pytest tests/ -m gpu -v -s --timeout 300 --timeou
     > gpurun_out/gpu_tests.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^(FAILED|ERROR)|passed|failed|^E " gpurun_out/gpu_tests.log | head -20
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 --cpu-seconds 10 > gpurun_out/bench.log 2>&1 || { echo "bench failed"; tail gpurun_out/bench.log; exit 1; }
-tail -1 gpurun_out/bench.log
+OUT=${OUT:-bench_out}; mkdir -p $OUT
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 10 > $OUT/bench.log 2>&1 || { echo "bench failed"; tail $OUT/bench.log; exit 1; }
+tail -1 $OUT/bench.log
