@@ -1520,7 +1520,10 @@ mpc_solve_kernel(DevTable tab, KParams Pr, int B, const double* __restrict__ x0g
             if (!xo_start) {
                 wave_sync();
                 riccati_factor<NT, FAC_CF>(S, N, dt, gl);
-                if constexpr (ACL && GL == 64) riccati_solve<NTR, ACL>(S, N, dt, gl);
+                // GL = 64 crossovers solve on the AC rows (phase 0 below), so their start does too; the GL = 64
+                // interior-point kernels of the split launch (MPC_IPM_GL64, N = 20) follow a GL = 32 MODE_XO
+                // crossover, which solved in K-row form: so does the start they recompute without the stage cache
+                if constexpr (ACL && GL == 64 && !(MODE == MODE_IPM && NT == 20)) riccati_solve<NTR, ACL>(S, N, dt, gl);
                 else riccati_solve<NTR, false>(S, N, dt, gl);
             }
             if (MODE == MODE_IPM && cached) {

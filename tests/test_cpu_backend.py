@@ -70,6 +70,70 @@ def test_backend_equals_oracle(env, cfg, sqp):
     assert np.array_equal(r["status"], ro["status"]) and np.array_equal(r["iters"], ro["iters"])
 
 
+def _assert_equals_oracle(r, ro, label):
+    err = float(np.abs(r["U"] - ro["U"]).max())
+    print(f"{label}: max|dU| {err:.1e}, bit-identical {np.array_equal(r['U'], ro['U'])}")
+    assert err <= 1e-12
+    assert np.abs(r["Xpred"] - ro["Xpred"]).max() <= 1e-10
+    assert np.array_equal(r["u0"], r["U"][:, 0])
+    assert np.array_equal(r["status"], ro["status"]) and np.array_equal(r["iters"], ro["iters"])
+
+
+def _horizon_cases():
+    import test_gpu_horizons as H
+    cases = [(name, N, 1, True) for name in ("C2", "C3", "C5") for N in H.SWEEP_N]
+    cases += [(name, N, 3, w) for name, N, w in H.SQP_CASES]
+    cases += [("C4", 30, 1, False), ("C5", 40, 1, False)]
+    return cases
+
+
+@pytest.mark.parametrize("name,N,sqp,with_obs", _horizon_cases())
+def test_backend_equals_oracle_horizon_sweep(env, name, N, sqp, with_obs):
+    """The horizon sweep of tests/test_gpu_horizons.py (lane-group boundaries 15 | 16 and 31 | 32, horizons up to
+    63, 203 egos) on the host backend, at the bar of test_backend_equals_oracle; it also checks, without a GPU,
+    that the sweep's batches hold the crossover-certified, deferred and elastic instances the GPU test needs."""
+    import test_gpu_horizons as H
+    mpcqp, _, _, W, _, _ = env
+    wb = H.sweep_batch(name, N, with_obs)
+    ld = W.loader(wb["traj"])
+    p = mpcqp.default_params(N=N, max_obs=wb["max_obs"], sqp_iters=sqp)
+    r = mpcqp.Solver(ld.X_ref, ld.U_ref, p, device=-1).solve_batch(wb["x0"], wb["obs"], wb["n_obs"])
+    ro, _ = H.oracle_solve(name, N, sqp, with_obs)
+    _assert_equals_oracle(r, ro, f"{name} N={N} sqp_iters={sqp} obstacles={with_obs}")
+    if sqp == 1 and with_obs:
+        H.assert_sweep_paths(name, N, r)
+
+
+def test_horizon_sweep_has_odd_and_even_deferred_counts():
+    """The sweep's interior-point launches see an even and an odd work list (two instances per wavefront at
+    N = 16 and 17): 46 and 47 deferred C2 instances on the oracle."""
+    import test_gpu_horizons as H
+    cnt = [int((H.oracle_solve("C2", N)[0]["iters"] > 0).sum()) for N in (16, 17)]
+    assert cnt == [46, 47]
+
+
+@pytest.mark.parametrize("N", [10, 20, 40])
+def test_backend_obstacle_slab_edges(env, N):
+    """The 64-row obstacle slab of tests/test_gpu_horizons.py (n_obs from 0 to 64) on the host backend: equal to
+    the oracle, and NaN in the rows at and past n_obs changes no bit."""
+    import test_gpu_horizons as H
+    mpcqp, _, _, W, _, _ = env
+    wb = H.slab_batch()
+    ld = W.loader(wb["traj"])
+    slv = mpcqp.Solver(ld.X_ref, ld.U_ref, mpcqp.default_params(N=N, max_obs=H.SLAB_MAX_OBS), device=-1)
+    r = slv.solve_batch(wb["x0"], wb["obs"], wb["n_obs"])
+    ro, _ = H.slab_oracle(N)
+    _assert_equals_oracle(r, ro, f"slab N={N}")
+    poisoned = wb["obs"].copy()
+    poisoned[np.arange(H.SLAB_MAX_OBS)[None, :] >= wb["n_obs"][:, None]] = np.nan
+    rn = slv.solve_batch(wb["x0"], poisoned, wb["n_obs"])
+    for k in H.KEYS:
+        assert np.array_equal(rn[k], r[k]), k
+    n0, n2, nxo = int((ro["status"] == 0).sum()), int((ro["status"] == 2).sum()), int((ro["iters"] == 0).sum())
+    print(f"slab N={N}: status 0: {n0}, status 2: {n2}, crossover-certified {nxo}")
+    assert 39 <= n0 <= 41 and 26 <= n2 <= 28 and 13 <= nxo <= 19, (n0, n2, nxo)
+
+
 @pytest.mark.parametrize("ti", [1, 2, 3])
 def test_lookup_and_pose_match_goldens(env, ti):
     mpcqp = env[0]

@@ -67,9 +67,11 @@ def assert_identical(a, b, what):
 
 @pytest.mark.parametrize("cfg,B,N", [("C2", 1024, None), ("C3", 1024, None), ("C4", 1024, None), ("C2", 1024, 10)])
 def test_two_phase_equals_single_kernel(lib, cfg, B, N):
-    """Split launch (MODE_XO + MODE_IPM) == single launch (MODE_FULL), host and device entries.  Covers the
-    N = 20 kernels (C2, C3), the runtime-horizon GL = 32 kernels (C4, N = 30) and GL = 16 (N = 10, four
-    instances per wavefront); the crossover solves in K-row form in both launch paths."""
+    """Split launch (MODE_XO + MODE_IPM) == single launch (MODE_ONE: MPC_TWO_PHASE=0 with sqp_iters = 1), host
+    and device entries.  Covers the N = 20 kernels (C2, C3), the N = 30 kernels (C4; NT = 30 with obstacles) and
+    the runtime-horizon GL = 16 kernels (N = 10, no obstacles, four instances per wavefront); the crossover
+    solves in K-row form in both launch paths.  The runtime-horizon GL = 32 kernels (horizons 16-31 other than
+    20 and 30) and the obstacle-free N = 30 kernels are compared in tests/test_gpu_horizons.py."""
     torch = pytest.importorskip("torch")
     import workloads as W
     wb = W.make_batch(cfg, B=B, seed=7)
