@@ -36,9 +36,9 @@ using mpcqp_host::HostTable;
 constexpr int kMaxN = MPC_MAX_N;
 constexpr int kRows = 9;          // soft rows per stage: lane +-d, +-(d + L/2 o), +-(d + L o), 2 obstacle, v >= 0
 constexpr int kBox = 4;           // box rows per control: +u1, -u1, +u2, -u2
-constexpr double kTau = 0.995;    // the device constants (mpcqp.hip: TAU, START_SHIFT, POLISH_*, SQP_*)
+constexpr double kTau = 0.995;    // the device constants (TAU; solve_kernel.h: START_SHIFT, POLISH_*, SQP_*)
 constexpr double kStartShift = 3.0;
-constexpr double kMuCheck = 1e-4;     // interior-point checkpoint (mpcqp.hip: MU_CHECK, CHECK_SEP, CHECK_ROUNDS)
+constexpr double kMuCheck = 1e-4;     // interior-point checkpoint (solve_kernel.h: MU_CHECK, CHECK_SEP, CHECK_ROUNDS)
 constexpr double kCheckSep = 100.0;
 constexpr int kCheckRounds = 2;
 // MPC_CHECKPOINT=0 in the environment switches the checkpoint off (A/B; the device kernels read the same flag)

@@ -272,7 +272,7 @@ inline bool build_host_table(const double* X, int T, const double* U, int Tu, Ho
     return true;
 }
 
-// host restatement of the device interval search (seg_t in mpcqp.hip): scipy's searchsorted lower bound
+// host restatement of the device interval search (seg_t in device_common.h): scipy's searchsorted lower bound
 // of v in s[0..T), found by binary search inside the buckets around v's, clamped to [1, n - 1]
 inline int seg_host(const HostTable& h, int n, double v) {
     const double* s = h.buf.data();

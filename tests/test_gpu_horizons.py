@@ -1,6 +1,7 @@
 """GPU tests of the solver kernel instantiations and of the horizons on the lane-group boundaries.
 
-launch_solve (csrc/mpcqp.hip) picks one of the 50 instantiations of mpc_solve_kernel<GL, OBS, MODE, NT> from the
+launch_solve (csrc/mpcqp.hip) picks one of the 50 instantiations of mpc_solve_kernel<GL, OBS, MODE, NT>
+(csrc/solve_kernel.h; its stage recursions: csrc/riccati_lanes.h) from the
 horizon (GL = 16 for N <= 15, 32 for N <= 31, else 64; NT = N at the specialised horizons 20, 30, 40, else 0 =
 runtime horizon), from whether obstacles were passed (OBS), from sqp_iters and the batch size (MODE: the split
 pair XO + IPM for single-QP solves with two or more instances per wavefront, ONE for the other single-QP

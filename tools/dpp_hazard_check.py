@@ -2,8 +2,9 @@
 
 A DPP instruction whose broadcast source VGPR was written by a VALU instruction fewer than 2 instructions
 earlier reads a stale value (2 wait states are required; s_nop N provides N + 1).  The inline-asm recursions
-of mpcqp.hip are outside the compiler's hazard recognizer, so they pad by hand; this script checks every
-v_*_dpp of a listing (straight-line look-back within a basic block; a label resets the window).
+of the tracker library (csrc/riccati_lanes.h, compiled as part of mpcqp.hip) are outside the compiler's hazard
+recognizer, so they pad by hand; this script checks every v_*_dpp of a listing (straight-line look-back
+within a basic block; a label resets the window).
 
   python tools/dpp_hazard_check.py listing.s [kernel-name-substring]"""
 import re

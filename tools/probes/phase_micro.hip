@@ -1,8 +1,8 @@
 // Cycle cost of the Riccati phases of the product kernel in isolation (one wavefront, two N = 20
-// groups, synthetic but well-conditioned stage data).  Includes the product source, so it times the
-// exact device code that ships.  s_memtime cycles per call, averaged over REP calls.
+// groups, synthetic but well-conditioned stage data).  Includes the product's recursion header, so it times
+// the exact device code that ships.  s_memtime cycles per call, averaged over REP calls.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o phase_micro phase_micro.hip
-#include "../../safe-autonomous-driving-mpc_amd/csrc/mpcqp.hip"
+#include "../../safe-autonomous-driving-mpc_amd/csrc/riccati_lanes.h"
 #include <cstdio>
 
 #define NTP 20
