@@ -31,8 +31,9 @@ extern "C" {
 
 /* 2: status[] / hist_status[] may carry the MPC_SQP_UNCONVERGED flag (16) OR-ed onto the code; mask with
  *    MPC_STATUS_MASK before comparing with MPC_OK .. MPC_NUMERICAL (version 1 returned 0-3 only).
- * 3: the ego-shard communicator (mpc_comm_*, mpc_gather*, MPC_E_COMM); nothing else changed. */
-#define MPCQP_VERSION 3
+ * 3: the ego-shard communicator (mpc_comm_*, mpc_gather*, MPC_E_COMM); nothing else changed.
+ * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed. */
+#define MPCQP_VERSION 4
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
 
@@ -182,6 +183,73 @@ void mpc_default_fsm(mpc_fsm* f);
 int mpc_closed_loop(mpc_ctx* c, int B, const double* x_init, const mpc_fsm* fsm, int max_steps, double s_stop,
                     double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl, int* hist_status,
                     int* n_steps, double* step_ms);
+
+/* Closed-loop scenario sweep: mpc_closed_loop with a scenario per ego, the acceptance-check quantities
+ * accumulated while the loop runs, and histories only for the egos the caller names.  Ego b's loop is
+ * exactly mpc_closed_loop's loop with scenario fsm[b] (same FSM transitions, slab order, solver launch,
+ * Euler plant, arithmetic order and exit test); nothing the call allocates grows with B * max_steps.
+ *
+ * Columns of the per-ego summary quant [B][MPC_CL_NQ]; 0..10 are shard.CL_FIELDS in its order, and every
+ * row equals shard.closed_loop_quantities on that ego's full histories (a NaN state or control propagates
+ * into the extreme like numpy's max / min; an ego that never ran has its initial s and |d|, zeros and a NaN
+ * gap). */
+#define MPC_CLQ_EGO 0            /* b (the caller adds its shard offset)                                  */
+#define MPC_CLQ_N_STEPS 1
+#define MPC_CLQ_S_FINAL 2
+#define MPC_CLQ_MAX_DEV 3        /* max |d| over the initial state and every state reached                */
+#define MPC_CLQ_U1_MIN 4
+#define MPC_CLQ_U1_MAX 5
+#define MPC_CLQ_U2_MIN 6
+#define MPC_CLQ_U2_MAX 7
+#define MPC_CLQ_MAX_STEP_MS 8    /* max of step_ms over the steps this ego ran (0 if none)                */
+#define MPC_CLQ_MIN_OBS_DIST 9   /* min (car_s - s) over steps with a car, s the state before the step;
+                                    NaN if never                                                          */
+#define MPC_CLQ_RED_PASS 10      /* 1.0: the first state with s > tl_pos was reached while RED (decided at
+                                    the first step that starts from such a state, with that step's light
+                                    after the FSM update; a first crossing at the final state does not
+                                    count)                                                                */
+#define MPC_CLQ_N_INFEASIBLE 11  /* steps whose (status & MPC_STATUS_MASK) == MPC_INFEASIBLE              */
+#define MPC_CLQ_N_NOT_OK 12      /* steps whose masked status != MPC_OK                                   */
+#define MPC_CL_NQ 13
+
+/*   fsm, n_fsm   n_fsm == B: fsm[b] is ego b's scenario; n_fsm == 1: one scenario shared by all; fsm NULL
+ *                with n_fsm == 0: none.  The solver runs with an obstacle slab of 2 when any ego's scenario
+ *                has a switch on; an ego whose own scenario has both off gets no obstacle, records NaN for
+ *                the car and 0 (RED) for the light, like mpc_closed_loop without scenarios.
+ *   quant        [B][MPC_CL_NQ], required.
+ *   hist_egos    [n_hist] egos whose histories are kept: distinct, in [0, B).  hist_x .. hist_status are
+ *                [n_hist][...] with mpc_closed_loop's per-ego layout, row k for ego hist_egos[k]; any may be
+ *                NULL, all must be NULL when n_hist == 0.
+ *   n_steps [B], step_ms [max_steps]: optional here.  Step times are always taken (a small ring of events
+ *                read at the every-8-steps host sync); MPC_CLQ_MAX_STEP_MS is max(step_ms[:n_steps[b]]).
+ * Misuse (n_fsm not in {0 with NULL, 1, B}, quant NULL, n_hist < 0, a history pointer with n_hist == 0, an
+ * index out of range or repeated) is MPC_E_ARG. */
+int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, const mpc_fsm* fsm, int n_fsm, int max_steps,
+                          double s_stop, double* quant, int n_hist, const int* hist_egos, double* hist_x,
+                          double* hist_u, double* hist_obs_s, int* hist_tl, int* hist_status, int* n_steps,
+                          double* step_ms);
+
+/* The verdicts of the restated acceptance check (the package's sanity_checks.py, check_verdicts, which
+ * restates the reference's sanity_checks.py:79-184) from the sweep's quantities.  The constants are those of
+ * sanity_checks.py: LATERAL_LIMIT, CONTROLS_TOL, CPU_LIMIT, SAFETY_DIST, and the 1 m of the destination
+ * check (:97-103). */
+#define MPC_CL_DEST_TOL 1.0          /* destination: not (s_final < s_total - 1.0)            */
+#define MPC_CL_LATERAL_LIMIT 1.5     /* on road: not (max |d| > 1.5 m)                        */
+#define MPC_CL_CONTROLS_TOL 0.1      /* controls within the context's u_min / u_max -+ 0.1    */
+#define MPC_CL_STEP_MS_LIMIT 150.0   /* real time: not (max step time > 150 ms)               */
+#define MPC_CL_SAFETY_DIST 1.0       /* car: no gap, or not (min gap < 1.0 m)                 */
+/* verdict bits, in check_verdicts' order */
+#define MPC_CLV_DESTINATION 1
+#define MPC_CLV_ON_ROAD 2
+#define MPC_CLV_STEER_OK 4
+#define MPC_CLV_ACCEL_OK 8
+#define MPC_CLV_REALTIME 16
+#define MPC_CLV_OBSTACLE_OK 32
+#define MPC_CLV_LIGHT_OK 64
+#define MPC_CLV_PASSED 128           /* all of the above                                      */
+/* Host only.  quant [B][MPC_CL_NQ]; verdicts [B] bitmask (may be NULL); counts[k] = egos with bit 1 << k set
+ * (may be NULL).  The control bounds are the context's u_min / u_max. */
+int mpc_cl_verdicts(const mpc_ctx* c, int B, const double* quant, double s_total, int* verdicts, int counts[8]);
 
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no

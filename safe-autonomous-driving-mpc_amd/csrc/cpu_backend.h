@@ -932,6 +932,8 @@ private:
 // ---------------------------------------------------------------------------------------------
 // the backend object behind a device = -1 context
 // ---------------------------------------------------------------------------------------------
+inline void sweep_max_step_ms(int B, const int* n_steps, const std::vector<double>& ms, double* quant);
+
 struct Backend {
     HostTable table;
     std::unique_ptr<Ref> ref;
@@ -1106,7 +1108,195 @@ struct Backend {
         }
         return MPC_SUCCESS;
     }
+
+    // mpc_closed_loop_sweep on the host: closed_loop above with ego b's scenario fsm[n_fsm == 1 ? 0 : b], the
+    // check quantities (include/mpcqp.h, MPC_CLQ_*) accumulated while the loop runs, and history rows only for
+    // the egos with slot[b] >= 0 (row slot[b] of the [n_hist][...] arrays).  quant is [B][MPC_CL_NQ]; n_steps
+    // and step_ms are optional.  The extremes take a NaN operand and keep it, like numpy's max / min
+    int closed_loop_sweep(const mpc_params& p0, int B, const double* x_init, const mpc_fsm* fsm, int n_fsm,
+                          bool with_fsm, int max_steps, double s_stop, double* quant, int n_hist, const int* slot,
+                          double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl, int* hist_status,
+                          int* n_steps, double* step_ms) const {
+        mpc_params p = p0;
+        p.max_obs = with_fsm ? 2 : 0;
+        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist;
+        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
+        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
+        if (hist_obs_s) std::fill(hist_obs_s, hist_obs_s + nh * ns, NAN);
+        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
+        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
+        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
+        std::vector<double> x(x_init, x_init + nb * 5), car(nb), timer(nb, 0.0), ms;
+        std::vector<int> flags(nb * 4, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
+        std::vector<double> xa, obsa, u0a;
+        std::vector<int> nobsa, sta;
+        for (int b = 0; b < B; ++b) {
+            car[b] = fsm[n_fsm == 1 ? 0 : b].obs_start_s;
+            active[b] = x[5 * (size_t)b] <= s_stop;
+            if (hist_x && slot[b] >= 0)
+                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+            double* q = quant + (size_t)b * MPC_CL_NQ;
+            std::fill(q, q + MPC_CL_NQ, 0.0);
+            q[MPC_CLQ_EGO] = (double)b;
+            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
+            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
+            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
+        }
+        for (int step = 0; step < max_steps; ++step) {
+            const auto t0 = std::chrono::steady_clock::now();
+            alist.clear();
+            for (int b = 0; b < B; ++b)
+                if (active[b]) alist.push_back(b);
+            if (alist.empty()) break;
+            const int nl = (int)alist.size();
+            xa.assign((size_t)nl * 5, 0.0);
+            obsa.assign((size_t)nl * 4, 0.0);
+            nobsa.assign(nl, 0);
+            u0a.assign((size_t)nl * 2, 0.0);
+            sta.assign(nl, 0);
+            for (int i = 0; i < nl; ++i) {
+                const int b = alist[i];
+                const mpc_fsm& F = fsm[n_fsm == 1 ? 0 : b];
+                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
+                int* fl = flags.data() + 4 * (size_t)b;      // car active, car triggered, light green, waiting
+                double* o = obsa.data() + 4 * (size_t)i;
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                int n = 0;
+                double car_s = NAN;
+                if (F.dynamic_obstacle) {                    // ObstaclesFSM.update, :335-349
+                    if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
+                    if (fl[0]) {
+                        car[b] = car[b] + F.obs_v * p.dt;
+                        if (car[b] > F.obs_end_s) {
+                            fl[0] = 0;
+                        } else {
+                            o[0] = car[b];
+                            o[1] = F.obs_v;
+                            n = 1;
+                            car_s = car[b];
+                        }
+                    }
+                }
+                if (F.traffic_light && !fl[2]) {             // :351-372
+                    const double dist = F.tl_pos - s;
+                    if (0.0 < dist && dist < F.tl_trigger_s) {
+                        o[2 * n] = F.tl_pos;
+                        o[2 * n + 1] = 0.0;
+                        ++n;
+                        if (v < 0.1 && dist < 10.0) fl[3] = 1;
+                    }
+                    if (fl[3]) {
+                        timer[b] += p.dt;
+                        if (timer[b] >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
+                    }
+                }
+                nobsa[i] = n;
+                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+                if (car_s == car_s) {                        // the gap of check_quantities, hist_obs_s[i] - hist_x[i, 0]
+                    const double g = car_s - s;
+                    if (!(qflags[b] & 1)) {
+                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                        qflags[b] |= 1;
+                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
+                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                    }
+                }
+                if (F.traffic_light && !(qflags[b] & 2) && s > F.tl_pos) {   // the first state past the light
+                    qflags[b] |= 2;
+                    if (!fl[2]) q[MPC_CLQ_RED_PASS] = 1.0;
+                }
+                if (slot[b] >= 0) {
+                    if (hist_obs_s) hist_obs_s[(size_t)slot[b] * ns + step] = car_s;
+                    if (hist_tl) hist_tl[(size_t)slot[b] * ns + step] = fl[2];
+                }
+            }
+            solve_batch(p, nl, xa.data(), with_fsm ? obsa.data() : nullptr, with_fsm ? nobsa.data() : nullptr,
+                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
+            for (int i = 0; i < nl; ++i) {                   // plant step x + dt f(x, u0, k_ref(s)), :403-406
+                const int b = alist[i];
+                double* xb = x.data() + 5 * (size_t)b;
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                double st[5];
+                ref->state(xb[0], st);
+                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
+                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
+                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
+                if (slot[b] >= 0) {
+                    const size_t h = (size_t)slot[b];
+                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
+                    if (hist_u) {
+                        hist_u[(h * ns + step) * 2] = u1;
+                        hist_u[(h * ns + step) * 2 + 1] = u2;
+                    }
+                    if (hist_status) hist_status[h * ns + step] = sta[i];
+                }
+                nrun[b] = step + 1;
+                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
+                q[MPC_CLQ_S_FINAL] = xb[0];
+                const double ad = std::fabs(xb[1]);
+                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
+                if (step == 0) {                             // every ego that runs at all runs step 0
+                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
+                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
+                } else {
+                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
+                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
+                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
+                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
+                }
+                const int code = sta[i] & MPC_STATUS_MASK;
+                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
+                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
+                if (!(xb[0] <= s_stop)) active[b] = 0;
+            }
+            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            if (step_ms) step_ms[step] = ms.back();
+        }
+        sweep_max_step_ms(B, nrun.data(), ms, quant);
+        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
+        return MPC_SUCCESS;
+    }
 };
+
+// MPC_CLQ_MAX_STEP_MS of every ego: the prefix max of the step times over the steps it ran, max(ms[:n]) with
+// numpy's NaN rule, 0 for an ego that never ran (shared by the device path of mpc_closed_loop_sweep)
+inline void sweep_max_step_ms(int B, const int* n_steps, const std::vector<double>& ms, double* quant) {
+    std::vector<double> pm(ms.size() + 1, 0.0);
+    for (size_t i = 0; i < ms.size(); ++i)
+        pm[i + 1] = (i == 0 || ms[i] > pm[i] || ms[i] != ms[i]) ? ms[i] : pm[i];
+    for (int b = 0; b < B; ++b) {
+        const size_t n = std::min((size_t)std::max(n_steps[b], 0), ms.size());
+        quant[(size_t)b * MPC_CL_NQ + MPC_CLQ_MAX_STEP_MS] = pm[n];
+    }
+}
+
+// mpc_cl_verdicts: sanity_checks.check_verdicts row by row on quant [B][MPC_CL_NQ] (each test negated like
+// there, so a NaN passes the same way); the control bounds are p's.  verdicts and counts may be null
+inline void cl_verdicts(const mpc_params& p, int B, const double* quant, double s_total, int* verdicts,
+                        int* counts) {
+    if (counts)
+        for (int k = 0; k < 8; ++k) counts[k] = 0;
+    const double* lo = p.u_min;
+    const double* hi = p.u_max;
+    for (int b = 0; b < B; ++b) {
+        const double* q = quant + (size_t)b * MPC_CL_NQ;
+        int v = 0;
+        if (!(q[MPC_CLQ_S_FINAL] < s_total - MPC_CL_DEST_TOL)) v |= MPC_CLV_DESTINATION;
+        if (!(q[MPC_CLQ_MAX_DEV] > MPC_CL_LATERAL_LIMIT)) v |= MPC_CLV_ON_ROAD;
+        if (!(q[MPC_CLQ_U1_MIN] < lo[0] - MPC_CL_CONTROLS_TOL || q[MPC_CLQ_U1_MAX] > hi[0] + MPC_CL_CONTROLS_TOL))
+            v |= MPC_CLV_STEER_OK;
+        if (!(q[MPC_CLQ_U2_MIN] < lo[1] - MPC_CL_CONTROLS_TOL || q[MPC_CLQ_U2_MAX] > hi[1] + MPC_CL_CONTROLS_TOL))
+            v |= MPC_CLV_ACCEL_OK;
+        if (!(q[MPC_CLQ_MAX_STEP_MS] > MPC_CL_STEP_MS_LIMIT)) v |= MPC_CLV_REALTIME;
+        const double gap = q[MPC_CLQ_MIN_OBS_DIST];
+        if (gap != gap || !(gap < MPC_CL_SAFETY_DIST)) v |= MPC_CLV_OBSTACLE_OK;
+        if (q[MPC_CLQ_RED_PASS] == 0.0) v |= MPC_CLV_LIGHT_OK;
+        if (v == MPC_CLV_PASSED - 1) v |= MPC_CLV_PASSED;
+        if (verdicts) verdicts[b] = v;
+        if (counts)
+            for (int k = 0; k < 8; ++k) counts[k] += (v >> k) & 1;
+    }
+}
 
 }  // namespace mpcqp_cpu
 

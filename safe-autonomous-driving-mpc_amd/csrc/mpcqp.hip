@@ -21,6 +21,7 @@
 //   riccati_lanes.h        the lane-distributed Riccati recursions (inline-asm DPP chains)
 //   solve_kernel.h         mpc_solve_kernel and mpc_lookup_kernel
 //   closed_loop_kernels.h  closed-loop FSM / plant / compaction kernels, pose kernel
+//   sweep_kernels.h        the scenario sweep's FSM / plant kernels (a scenario per ego, check quantities)
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points) and, last, the comm layer (comm.h).
 #include <hip/hip_runtime.h>
@@ -40,6 +41,7 @@
 #include "cpu_backend.h"
 #include "solve_kernel.h"
 #include "closed_loop_kernels.h"
+#include "sweep_kernels.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -707,6 +709,232 @@ extern "C" int mpc_closed_loop(mpc_ctx* c, int B, const double* x_init, const mp
     }
     cleanup();
     return rc;
+}
+
+// mpc_closed_loop with a scenario per ego, the check quantities accumulated on the device and histories for
+// the named egos only (include/mpcqp.h).  Device allocations: the closed loop's per-ego state (ClState), the
+// scenarios [B] when they differ, the quantities [MPC_CL_NQ][B], two int arrays [B] (flags, history slots),
+// n_steps [B] and the kept histories [n_hist][max_steps ..]: O(B) + O(n_hist * max_steps).  Step times come
+// from a ring of SW_EVENTS events read at the every-8-steps host sync
+#define SW_EVENTS 9
+extern "C" int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, const mpc_fsm* fsm, int n_fsm,
+                                     int max_steps, double s_stop, double* quant, int n_hist, const int* hist_egos,
+                                     double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl,
+                                     int* hist_status, int* n_steps, double* step_ms) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
+    if (fsm ? !(n_fsm == 1 || n_fsm == B) : n_fsm != 0)
+        return fail(MPC_E_ARG, "n_fsm must be B (a scenario per ego), 1 (shared) or 0 with fsm NULL");
+    if (!quant) return fail(MPC_E_ARG, "quant is required");
+    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
+    if (n_hist == 0 && (hist_x || hist_u || hist_obs_s || hist_tl || hist_status))
+        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
+    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
+    std::vector<int> slot;
+    try {
+        slot.assign((size_t)B, -1);
+    } catch (const std::bad_alloc&) {
+        return fail(MPC_E_ALLOC, "history slot map");
+    }
+    for (int k = 0; k < n_hist; ++k) {
+        const int e = hist_egos[k];
+        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
+        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
+        slot[e] = k;
+    }
+    if (B == 0) return MPC_SUCCESS;
+    if (!x_init) return fail(MPC_E_ARG, "x_init is required");
+    int rc = check_params(&c->p);
+    if (rc) return rc;
+    mpc_fsm F;
+    mpc_default_fsm(&F);                             // no scenario: both switches off
+    if (fsm && n_fsm == 1) F = fsm[0];
+    const bool per_ego = fsm && n_fsm != 1;          // n_fsm == B > 1
+    bool with_fsm = F.dynamic_obstacle || F.traffic_light;
+    if (per_ego)
+        for (int b = 0; b < B && !with_fsm; ++b) with_fsm = fsm[b].dynamic_obstacle || fsm[b].traffic_light;
+    if (c->cpu) {
+        int hrc = MPC_SUCCESS;
+        const int erc = host_call([&] {
+            hrc = c->cpu->closed_loop_sweep(c->p, B, x_init, per_ego ? fsm : &F, per_ego ? B : 1, with_fsm, max_steps,
+                                            s_stop, quant, n_hist, slot.data(), hist_x, hist_u, hist_obs_s, hist_tl,
+                                            hist_status, n_steps, step_ms);
+        });
+        return erc != MPC_SUCCESS ? erc : hrc;
+    }
+    KParams kp = kparams(&c->p);
+    kp.max_obs = with_fsm ? 2 : 0;          // the FSM yields at most the car and the light
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist;
+    std::vector<void*> bufs;
+    auto dalloc = [&](size_t bytes) -> void* {
+        void* ptr = nullptr;
+        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
+        bufs.push_back(ptr);
+        return ptr;
+    };
+    auto release = [&]() { for (void* q : bufs) hipFree(q); };
+    ClState C;
+    C.x = (double*)dalloc(nb * 5 * 8);
+    C.obs = (double*)dalloc(nb * 4 * 8);
+    C.nobs = (int*)dalloc(nb * 4);
+    C.active = (int*)dalloc(nb * 4);
+    C.obs_s = (double*)dalloc(nb * 8);
+    C.tl_timer = (double*)dalloc(nb * 8);
+    C.fsm_flags = (int*)dalloc(nb * 4 * 4);
+    C.n_active = (int*)dalloc(4);
+    C.alist = (int*)dalloc(nb * 4);
+    C.n_list = (int*)dalloc(4);
+    C.xa = (double*)dalloc(nb * 5 * 8);
+    C.obsa = (double*)dalloc(nb * 4 * 8);
+    C.nobsa = (int*)dalloc(nb * 4);
+    C.u0a = (double*)dalloc(nb * 2 * 8);
+    C.sta = (int*)dalloc(nb * 4);
+    double* d_xinit = (double*)dalloc(nb * 5 * 8);
+    SwState S;
+    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
+    S.qflags = (int*)dalloc(nb * 4);
+    int* d_hslot = (int*)dalloc(nb * 4);
+    S.hslot = d_hslot;
+    S.n_steps = (int*)dalloc(nb * 4);
+    mpc_fsm* d_fsm = per_ego ? (mpc_fsm*)dalloc(nb * sizeof(mpc_fsm)) : nullptr;
+    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
+    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
+    S.hist_obs_s = hist_obs_s ? (double*)dalloc(nh * ns * 8) : nullptr;
+    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
+    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
+    for (void* q : bufs)
+        if (!q) { release(); return fail(MPC_E_ALLOC, "hipMalloc sweep buffers"); }
+    if ((per_ego && !d_fsm) || (hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_obs_s && !S.hist_obs_s) ||
+        (hist_tl && !S.hist_tl) || (hist_status && !S.hist_status)) {
+        release();
+        return fail(MPC_E_ALLOC, "hipMalloc sweep scenarios / histories");
+    }
+    hipStream_t st = c->stream;
+    hipEvent_t ev[SW_EVENTS] = {};
+    auto cleanup = [&]() {
+        hipStreamSynchronize(st);
+        for (auto& e : ev)
+            if (e) hipEventDestroy(e);
+        release();
+    };
+    // steps that never run stay NaN / -1 (all-ones bytes)
+    bool ok0 = true;
+    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
+    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
+    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
+    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
+    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
+    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (per_ego) ok0 = ok0 && hipMemcpyAsync(d_fsm, fsm, nb * sizeof(mpc_fsm), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok0) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "sweep buffer initialisation");
+    }
+    const dim3 tb(256), tg((B + 255) / 256);
+    if (per_ego) hipLaunchKernelGGL(sw_init_kernel<true>, tg, tb, 0, st, B, F, d_fsm, C, S, d_xinit, s_stop, max_steps);
+    else hipLaunchKernelGGL(sw_init_kernel<false>, tg, tb, 0, st, B, F, d_fsm, C, S, d_xinit, s_stop, max_steps);
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+            cleanup();
+            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
+        }
+    if (hipEventRecord(ev[0], st) != hipSuccess) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
+    }
+    // step i ran between events i and i + 1 of the ring; read at a host sync, at most 8 steps after the last
+    // read, so no event is re-recorded before its interval has been taken
+    std::vector<double> ms;
+    auto read_times = [&](int upto) {
+        for (int i = (int)ms.size(); i < upto; ++i) {
+            float t = NAN;
+            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
+            ms.push_back(t);
+        }
+    };
+    rc = MPC_SUCCESS;
+    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
+    int nl = 0;
+    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "sweep initial ego list");
+    }
+    try {
+        for (int step = 0; step < max_steps && nl > 0; ++step) {
+            if (per_ego) hipLaunchKernelGGL(sw_fsm_kernel<true>, tg, tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
+            else hipLaunchKernelGGL(sw_fsm_kernel<false>, tg, tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
+            const dim3 lg((nl + 255) / 256);
+            hipLaunchKernelGGL(cl_gather_kernel, lg, tb, 0, st, nl, C);
+            rc = launch_solve(c, kp, nl, C.xa, with_fsm ? C.obsa : nullptr, with_fsm ? C.nobsa : nullptr, nullptr,
+                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
+            if (rc) break;
+            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
+                rc = fail(MPC_E_DEVICE, "sweep active-count reset");
+                break;
+            }
+            hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, s_stop, step, max_steps);
+            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
+                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
+                break;
+            }
+            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
+                int na = 0;
+                if (hipMemcpyAsync(&na, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipStreamSynchronize(st) != hipSuccess) {
+                    rc = fail(MPC_E_DEVICE, "sweep step sync");
+                    break;
+                }
+                read_times(step + 1);
+                if (na == 0) break;
+                if (na < nl) {                                  // egos left: shrink the solver's list
+                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
+                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess) {
+                        rc = fail(MPC_E_DEVICE, "sweep ego list");
+                        break;
+                    }
+                }
+            }
+        }
+        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "sweep kernel launch");
+        if (rc == MPC_SUCCESS) {
+            std::vector<double> hq(nb * MPC_CL_NQ);
+            std::vector<int> hn(nb);
+            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_obs_s) ok = ok && hipMemcpyAsync(hist_obs_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = ok && hipStreamSynchronize(st) == hipSuccess;
+            if (!ok) {
+                rc = fail(MPC_E_DEVICE, "sweep copy-back");
+            } else {
+                for (size_t b = 0; b < nb; ++b)               // [MPC_CL_NQ][B] on the device -> [B][MPC_CL_NQ]
+                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
+                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
+                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
+                if (step_ms)
+                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        rc = fail(MPC_E_ALLOC, "sweep host buffers");
+    }
+    cleanup();
+    return rc;
+}
+
+extern "C" int mpc_cl_verdicts(const mpc_ctx* c, int B, const double* quant, double s_total, int* verdicts,
+                               int counts[8]) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0 || (B > 0 && !quant)) return fail(MPC_E_ARG, "B < 0 or quant is NULL");
+    mpcqp_cpu::cl_verdicts(c->p, B, quant, s_total, verdicts, counts);
+    return MPC_SUCCESS;
 }
 
 extern "C" int mpc_global_pose(mpc_ctx* c, int n, const double* s, const double* d, double* out) {

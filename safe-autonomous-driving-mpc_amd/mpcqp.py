@@ -53,10 +53,16 @@ class MpcError(RuntimeError):
 
 EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_batch_device", "mpc_lookup",
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
-           "mpc_closed_loop", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
+# columns of mpc_closed_loop_sweep's per-ego summary (MPC_CLQ_*): shard.CL_FIELDS, then two status counters
+CL_NQ = 13
+CLQ_FIELDS = ("ego", "n_steps", "s_final", "max_dev", "u1_min", "u1_max", "u2_min", "u2_max", "max_step_ms",
+              "min_obs_dist", "red_pass", "n_infeasible", "n_not_ok")
+# verdict bits of mpc_cl_verdicts (MPC_CLV_*), sanity_checks.check_verdicts' order
+CLV_NAMES = ("destination", "on_road", "steer_ok", "accel_ok", "realtime", "obstacle_ok", "light_ok", "passed")
 
 _lib = None
 
@@ -96,6 +102,11 @@ def lib():
     L.mpc_closed_loop.restype = C.c_int
     L.mpc_closed_loop.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(MpcFsm), C.c_int, C.c_double, _dp, _dp, _dp,
                                   _ip, _ip, _ip, _dp]
+    L.mpc_closed_loop_sweep.restype = C.c_int
+    L.mpc_closed_loop_sweep.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(MpcFsm), C.c_int, C.c_int, C.c_double, _dp,
+                                        C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp]
+    L.mpc_cl_verdicts.restype = C.c_int
+    L.mpc_cl_verdicts.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _ip]
     L.mpc_comm_unique_id.restype = C.c_int
     L.mpc_comm_unique_id.argtypes = [C.c_char_p]
     L.mpc_comm_create.restype = C.c_int
@@ -240,6 +251,62 @@ class Solver:
                                      float(s_stop), _p(hx), _p(hu), _p(ho), _pi(ht), _pi(hs), _pi(ns), _p(sm)),
                "mpc_closed_loop")
         return dict(hist_x=hx, hist_u=hu, hist_obs_s=ho, hist_tl=ht, hist_status=hs, n_steps=ns, step_ms=sm)
+
+    def closed_loop_sweep(self, x_init, scenarios, max_steps, s_stop=None, s_max=None, hist_egos=(), lo=0):
+        """mpc_closed_loop_sweep: the batched closed loop with a scenario per ego, the check quantities
+        accumulated while it runs, and histories only for the egos in `hist_egos`.
+        x_init [B,5]; scenarios: None (no scenario), one MpcFsm (shared), or a sequence / ctypes array of B
+        MpcFsm (ego b runs scenarios[b]); the loop runs while s <= s_stop (default s_max - 1).
+        Returns dict(quant [B,13] (columns CLQ_FIELDS; `lo`, the shard offset, is added to column 0), n_steps [B],
+        step_ms [max_steps], hist_egos [n_hist], hist_x [n_hist,max_steps+1,5], hist_u [n_hist,max_steps,2],
+        hist_obs_s, hist_tl, hist_status [n_hist,max_steps]: row k belongs to ego hist_egos[k])."""
+        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
+        B = x_init.shape[0]
+        if s_stop is None:
+            if s_max is None:
+                raise ValueError("give s_stop or s_max")
+            s_stop = s_max - 1.0
+        if scenarios is None:
+            fsm, n_fsm = None, 0
+        elif isinstance(scenarios, MpcFsm):
+            fsm, n_fsm = C.pointer(scenarios), 1
+        else:
+            n_fsm = len(scenarios)
+            if isinstance(scenarios, C.Array):
+                arr = scenarios
+            else:
+                arr = (MpcFsm * max(n_fsm, 1))()
+                for i, f in enumerate(scenarios):
+                    C.memmove(C.byref(arr, i * C.sizeof(MpcFsm)), C.byref(f), C.sizeof(MpcFsm))
+            fsm = C.cast(arr, C.POINTER(MpcFsm))
+        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
+        nh = he.size
+        quant = np.empty((B, CL_NQ))
+        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
+        hx = hu = ho = ht = hs = None
+        if nh:
+            hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); ho = np.empty((nh, max_steps))
+            ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
+        _check(lib().mpc_closed_loop_sweep(self.h, B, _p(x_init), fsm, int(n_fsm), int(max_steps), float(s_stop),
+                                           _p(quant), nh, _pi(he) if nh else None, _p(hx), _p(hu), _p(ho), _pi(ht),
+                                           _pi(hs), _pi(ns), _p(sm)), "mpc_closed_loop_sweep")
+        quant[:, 0] += lo
+        if not nh:
+            hx = np.empty((0, max_steps + 1, 5)); hu = np.empty((0, max_steps, 2)); ho = np.empty((0, max_steps))
+            ht = np.empty((0, max_steps), np.int32); hs = np.empty((0, max_steps), np.int32)
+        return dict(quant=quant, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu, hist_obs_s=ho,
+                    hist_tl=ht, hist_status=hs)
+
+    def cl_verdicts(self, quant, s_total):
+        """mpc_cl_verdicts: the restated acceptance verdicts (sanity_checks.check_verdicts, with this context's
+        control bounds) of a sweep's quantities.  Returns (verdicts [B] int32 bitmask, bit k = CLV_NAMES[k];
+        counts [8] egos with each bit set)."""
+        quant = np.ascontiguousarray(quant, np.float64).reshape(-1, CL_NQ)
+        v = np.empty(quant.shape[0], np.int32)
+        counts = np.zeros(8, np.int32)
+        _check(lib().mpc_cl_verdicts(self.h, quant.shape[0], _p(quant), float(s_total), _pi(v), _pi(counts)),
+               "mpc_cl_verdicts")
+        return v, counts
 
     def global_pose(self, s, d):
         """TrajectoryLoader.get_global_pose on the device table, batched: s, d [n] -> [n, 3] (x, y, psi)."""

@@ -289,6 +289,24 @@ def pack_closed_loop(quant, r, rows, hist_egos, max_steps):
                            hist.view(np.uint8).ravel()])
 
 
+def pack_sweep(res, rows, hist_egos, max_steps):
+    """pack_closed_loop's payload from a sweep result (mpcqp.Solver.closed_loop_sweep): the first
+    len(CL_FIELDS) quantity columns, already computed by the library, and the histories the sweep kept (its
+    first `hist_egos` selected egos, in the order they were named).  unpack_closed_loop and
+    closed_loop_report read it unchanged."""
+    quant = np.asarray(res["quant"])[:, :len(CL_FIELDS)]
+    B = quant.shape[0]
+    h = min(hist_egos, len(res["hist_egos"]))
+    q = np.full((rows, len(CL_FIELDS)), np.nan)
+    q[:B] = quant
+    hist = np.full((hist_egos, max_steps, HIST_COLS), np.nan, np.float32)
+    if h:
+        hist[:h, :, :5] = res["hist_x"][:h, 1:max_steps + 1]
+        hist[:h, :, 5:] = res["hist_u"][:h, :max_steps]
+    return np.concatenate([np.array([B, h], np.int32).view(np.uint8), q.view(np.uint8).ravel(),
+                           hist.view(np.uint8).ravel()])
+
+
 def unpack_closed_loop(buf, rows, hist_egos, max_steps):
     buf = np.ascontiguousarray(buf, np.uint8)
     B, h = buf[:8].view(np.int32)

@@ -308,6 +308,55 @@ def run_simulation_batch(mpc, fsm, trajectory, x_init=None, B=1, max_steps=2000,
     return r
 
 
+def scenario_grid(base_fsm, **axes):
+    """The Cartesian product of ObstaclesFSM field values as a list of scenarios: copies of `base_fsm` with
+    the named fields replaced, e.g. scenario_grid(fsm, obs_v=[2, 4, 6], tl_stop_duration=[5, 20]) -> 6 scenarios.
+    Order: itertools.product over the axes in keyword order, so the last axis varies fastest
+    ((2, 5), (2, 20), (4, 5), ...)."""
+    import copy
+    import itertools
+    for k in axes:
+        if not hasattr(base_fsm, k):
+            raise ValueError(f"ObstaclesFSM has no field {k!r}")
+    out = []
+    for values in itertools.product(*axes.values()):
+        f = copy.copy(base_fsm)
+        for k, v in zip(axes, values):
+            setattr(f, k, v)
+        out.append(f)
+    return out
+
+
+def _fsm_record(fsm):
+    """mpc_fsm of one ego of a sweep: the ObstaclesFSM's fields (fsm_params), both switches off for None."""
+    if fsm is None:
+        return mpcqp.default_fsm()
+    return mpcqp.default_fsm(dynamic_obstacle=int(bool(fsm.dynamic_obstacle)), traffic_light=int(bool(fsm.traffic_light)),
+                             **{k: float(getattr(fsm, k)) for k in FSM_PRESETS["trajectory2"]})
+
+
+def run_scenario_sweep(mpc, scenarios, trajectory, x_init, max_steps=2000, hist_egos=(), s_stop=None):
+    """One closed loop per (ego, scenario) pair in a single library call (mpc_closed_loop_sweep): ego b starts
+    at x_init[b] and runs scenarios[b], an ObstaclesFSM or None (no scenario), while s <= s_stop (default
+    s_max - 1).  The check quantities are accumulated while the loop runs; full histories come back only for
+    the egos in `hist_egos`.  Returns mpcqp.Solver.closed_loop_sweep's dict plus 'verdicts' [B] (bitmask,
+    mpcqp.CLV_NAMES), 'counts' {name: egos passing} and one boolean column [B] per verdict name
+    (sanity_checks.check_verdicts with s_total = s_max)."""
+    x_init = np.asarray(x_init, np.float64).reshape(-1, 5)
+    scenarios = list(scenarios)
+    if len(scenarios) != x_init.shape[0]:
+        raise ValueError("one scenario (or None) per ego")
+    recs = None if all(f is None for f in scenarios) else [_fsm_record(f) for f in scenarios]
+    slv = mpc.solver(max_obs=0)
+    r = slv.closed_loop_sweep(x_init, recs, max_steps, s_stop=s_stop, s_max=trajectory.s_max, hist_egos=hist_egos)
+    v, counts = slv.cl_verdicts(r["quant"], trajectory.s_max)
+    r["verdicts"] = v
+    r["counts"] = {k: int(counts[i]) for i, k in enumerate(mpcqp.CLV_NAMES)}
+    for i, k in enumerate(mpcqp.CLV_NAMES):
+        r[k] = (v & (1 << i)) != 0
+    return r
+
+
 def closed_loop_checks(mpc, fsm, trajectory, r, verbose=False):
     """The restated trajectory_tracking_check (sanity_checks.py:79-184) on every ego of a closed_loop()
     result (mpcqp.Solver.closed_loop layout); returns the per-ego verdicts [B] (bool)."""

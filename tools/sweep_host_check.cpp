@@ -1,0 +1,121 @@
+// Stand-alone sanitizer check of the host backend's scenario sweep (csrc/cpu_backend.h: closed_loop_sweep,
+// sweep_max_step_ms, cl_verdicts), built and run by tools/sweep_host_check.py with
+// -fsanitize=address,undefined:
+//   sweep_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
+// Runs the shapes of tests/test_sweep_cpu.py's per-ego test on 3 worker threads: six egos with six scenarios,
+// N = 5, every history kept; then the same sweep with two selected egos and with no history at all, and the
+// verdicts.  Each ego's kept history must equal a one-ego closed_loop run with its scenario byte for byte.
+// Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/mpcqp.h"
+#include "../safe-autonomous-driving-mpc_amd/csrc/cpu_backend.h"
+
+static mpc_fsm scenario(int dyn, int tl) {
+    mpc_fsm f;
+    std::memset(&f, 0, sizeof(f));
+    f.dynamic_obstacle = dyn; f.traffic_light = tl;
+    f.obs_trigger_s = 710.0; f.obs_start_s = 780.0; f.obs_v = 4.0; f.obs_end_s = 1050.0;
+    f.tl_pos = 550.0; f.tl_trigger_s = 100.0; f.tl_stop_duration = 20.0;
+    return f;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[2];
+    if (std::fread(hdr, sizeof(int), 2, f) != 2) return 2;
+    const int T = hdr[0], Tu = hdr[1];
+    std::vector<double> X(5 * (size_t)T), U(2 * (size_t)Tu);
+    if (std::fread(X.data(), 8, X.size(), f) != X.size() || std::fread(U.data(), 8, U.size(), f) != U.size()) return 2;
+    std::fclose(f);
+    mpcqp_host::HostTable table;
+    if (!mpcqp_host::build_host_table(X.data(), T, U.data(), Tu, table)) return 2;
+    mpcqp_cpu::Backend be(std::move(table));
+    be.threads = 3;
+    mpc_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.N = 5; p.max_obs = 0; p.dt = 0.2;
+    p.u_min[0] = -0.6; p.u_min[1] = -5.0; p.u_max[0] = 0.6; p.u_max[1] = 4.0;
+    p.vehicle_radius = 1.0; p.w_d = 10.0; p.w_o = 10.0; p.w_v = 5.0; p.w_u1 = 0.5; p.w_u2 = 0.5;
+    p.obstacle_safety_distance = 5.0; p.max_time_2_obs = 1.5; p.wheelbase = 2.8; p.lane_width = 3.0;
+    p.safe_lane_margin = 0.1; p.brake_distance = 40.0; p.brake_accel = -2.0; p.linearization = 1;
+    p.sqp_iters = 1; p.max_iter = 80; p.tol = 1e-9; p.tol_mu = 1e-10; p.elastic_rho = 1e5; p.polish = 2;
+    p.sqp_tol = 1e-10;
+
+    // the six scenarios of tests/sweep_cases.py, just ahead of s0 = 440
+    const int B = 6, ms = 400;
+    const double s0 = 440.0, s_stop = s0 + 60.0, far = 1.0e6;
+    std::vector<mpc_fsm> F(B);
+    F[0] = scenario(1, 0); F[0].obs_trigger_s = s0 + 10; F[0].obs_start_s = s0 + 40; F[0].obs_end_s = far;
+    F[1] = scenario(1, 0); F[1].obs_trigger_s = s0 + 5; F[1].obs_start_s = s0 + 30; F[1].obs_v = 2.0; F[1].obs_end_s = far;
+    F[2] = scenario(0, 1); F[2].tl_pos = s0 + 30; F[2].tl_stop_duration = 1.0;
+    F[3] = scenario(0, 1); F[3].tl_pos = s0 + 30; F[3].tl_stop_duration = 3.0;
+    F[4] = scenario(1, 1); F[4].tl_pos = s0 + 30; F[4].tl_stop_duration = 1.0; F[4].obs_trigger_s = s0 + 35;
+    F[4].obs_start_s = s0 + 70; F[4].obs_end_s = far;
+    F[5] = scenario(1, 1); F[5].obs_trigger_s = far; F[5].tl_pos = far;
+    std::vector<double> x0(5 * (size_t)B, 0.0);
+    for (int b = 0; b < B; ++b) {
+        double st[5];
+        be.ref->state(s0 + b, st);
+        x0[5 * b] = s0 + b; x0[5 * b + 1] = 0.01 * (b % 3); x0[5 * b + 3] = st[3]; x0[5 * b + 4] = 9.0;
+    }
+    const size_t ns = ms;
+    auto run = [&](int nh, const std::vector<int>& egos, std::vector<double>& quant, std::vector<double>& hx,
+                   std::vector<double>& hu, std::vector<double>& ho, std::vector<int>& ht, std::vector<int>& hs,
+                   bool with_counts) {
+        std::vector<int> slot(B, -1), n_steps(B);
+        for (int k = 0; k < nh; ++k) slot[egos[k]] = k;
+        std::vector<double> step_ms(ns);
+        quant.assign((size_t)B * MPC_CL_NQ, -1.0);
+        hx.assign((size_t)nh * (ns + 1) * 5, 0.0); hu.assign((size_t)nh * ns * 2, 0.0); ho.assign((size_t)nh * ns, 0.0);
+        ht.assign((size_t)nh * ns, 0); hs.assign((size_t)nh * ns, 0);
+        return be.closed_loop_sweep(p, B, x0.data(), F.data(), B, true, ms, s_stop, quant.data(), nh, slot.data(),
+                                    nh ? hx.data() : nullptr, nh ? hu.data() : nullptr, nh ? ho.data() : nullptr,
+                                    nh ? ht.data() : nullptr, nh ? hs.data() : nullptr,
+                                    with_counts ? n_steps.data() : nullptr, with_counts ? step_ms.data() : nullptr);
+    };
+    std::vector<double> q_all, q_two, q_none, hx, hu, ho, hx2, hu2, ho2, e1, e2, e3;
+    std::vector<int> ht, hs, ht2, hs2, i1, i2;
+    if (run(B, {0, 1, 2, 3, 4, 5}, q_all, hx, hu, ho, ht, hs, true)) return 1;
+    if (run(2, {4, 1}, q_two, hx2, hu2, ho2, ht2, hs2, true)) return 1;
+    if (run(0, {}, q_none, e1, e2, e3, i1, i2, false)) return 1;
+    int bad = 0;
+    // each ego alone through closed_loop with its scenario
+    for (int b = 0; b < B; ++b) {
+        std::vector<double> sx((ns + 1) * 5), su(ns * 2), so(ns), sm(ns);
+        std::vector<int> st(ns), ss(ns);
+        int n1 = 0;
+        be.closed_loop(p, 1, x0.data() + 5 * b, F[b], true, ms, s_stop, sx.data(), su.data(), so.data(), st.data(),
+                       ss.data(), &n1, sm.data());
+        bad += std::memcmp(sx.data(), hx.data() + (size_t)b * (ns + 1) * 5, sx.size() * 8) != 0;
+        bad += std::memcmp(su.data(), hu.data() + (size_t)b * ns * 2, su.size() * 8) != 0;
+        bad += std::memcmp(so.data(), ho.data() + (size_t)b * ns, so.size() * 8) != 0;
+        bad += std::memcmp(st.data(), ht.data() + (size_t)b * ns, st.size() * 4) != 0;
+        bad += std::memcmp(ss.data(), hs.data() + (size_t)b * ns, ss.size() * 4) != 0;
+        bad += q_all[(size_t)b * MPC_CL_NQ + MPC_CLQ_N_STEPS] != (double)n1 || n1 <= 0 || n1 >= ms;
+        bad += q_all[(size_t)b * MPC_CL_NQ + MPC_CLQ_S_FINAL] != sx[(size_t)n1 * 5];
+    }
+    bad += std::memcmp(hx2.data(), hx.data() + 4 * (ns + 1) * 5, (ns + 1) * 5 * 8) != 0;
+    bad += std::memcmp(hx2.data() + (ns + 1) * 5, hx.data() + 1 * (ns + 1) * 5, (ns + 1) * 5 * 8) != 0;
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < MPC_CL_NQ; ++k) {
+            if (k == MPC_CLQ_MAX_STEP_MS) continue;          // a wall-clock measurement of each run
+            const double a = q_all[(size_t)b * MPC_CL_NQ + k];
+            bad += std::memcmp(&a, &q_two[(size_t)b * MPC_CL_NQ + k], 8) != 0;
+            bad += std::memcmp(&a, &q_none[(size_t)b * MPC_CL_NQ + k], 8) != 0;
+        }
+    std::vector<int> verdicts(B);
+    int counts[8];
+    mpcqp_cpu::cl_verdicts(p, B, q_all.data(), 1.0e9, verdicts.data(), counts);
+    mpcqp_cpu::cl_verdicts(p, B, q_all.data(), 1.0e9, nullptr, nullptr);
+    bad += counts[0] != 0 || counts[7] != 0;                 // s_total far away: nobody arrives, nobody passes
+    for (int b = 0; b < B; ++b) bad += (verdicts[b] & MPC_CLV_DESTINATION) != 0;
+    std::printf("sweep_host_check: %d mismatches; n_steps", bad);
+    for (int b = 0; b < B; ++b) std::printf(" %d", (int)q_all[(size_t)b * MPC_CL_NQ + MPC_CLQ_N_STEPS]);
+    std::printf("\n");
+    return bad ? 1 : 0;
+}
