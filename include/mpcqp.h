@@ -32,8 +32,9 @@ extern "C" {
 /* 2: status[] / hist_status[] may carry the MPC_SQP_UNCONVERGED flag (16) OR-ed onto the code; mask with
  *    MPC_STATUS_MASK before comparing with MPC_OK .. MPC_NUMERICAL (version 1 returned 0-3 only).
  * 3: the ego-shard communicator (mpc_comm_*, mpc_gather*, MPC_E_COMM); nothing else changed.
- * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed. */
-#define MPCQP_VERSION 4
+ * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed.
+ * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed. */
+#define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
 
@@ -250,6 +251,65 @@ int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, const mpc_fsm
 /* Host only.  quant [B][MPC_CL_NQ]; verdicts [B] bitmask (may be NULL); counts[k] = egos with bit 1 << k set
  * (may be NULL).  The control bounds are the context's u_min / u_max. */
 int mpc_cl_verdicts(const mpc_ctx* c, int B, const double* quant, double s_total, int* verdicts, int counts[8]);
+
+/* Closed-loop traffic scripts: mpc_closed_loop_sweep with up to MPC_MAX_ACTORS obstacles per ego.  Each ego
+ * runs a script of A actors; an actor is a car or a light with the per-obstacle state machine of ObstaclesFSM
+ * (trajectory_tracking.py:338-372: "each obstacle has its own FSM") and its own state.  MPC_ACTOR_NONE is a
+ * placeholder that emits nothing and has no state. */
+#define MPC_ACTOR_NONE 0
+#define MPC_ACTOR_CAR 1
+#define MPC_ACTOR_LIGHT 2
+#define MPC_MAX_ACTORS 16
+typedef struct mpc_actor {
+    int kind;
+    double trigger_s;      /* car: obs_trigger_s (ego position that spawns it); light: tl_trigger_s (distance) */
+    double pos_s;          /* car: obs_start_s; light: tl_pos                                                   */
+    double v;              /* car: obs_v                                                                        */
+    double end_s;          /* car: obs_end_s                                                                    */
+    double stop_duration;  /* light: tl_stop_duration                                                           */
+} mpc_actor;
+
+/* The two actors that restate an mpc_fsm: out[0] the car (NONE if dynamic_obstacle is off), out[1] the light
+ * (NONE if traffic_light is off).  Fields an actor kind does not use are 0. */
+void mpc_actors_from_fsm(const mpc_fsm* f, mpc_actor out[2]);
+
+/* Columns of the optional per-ego extra [B][MPC_TR_NX] of mpc_closed_loop_traffic. */
+#define MPC_TRX_MAX_NOBS 0        /* largest slab count the ego saw                                          */
+#define MPC_TRX_N_RED_PASS 1      /* lights passed on red                                                    */
+#define MPC_TRX_MIN_GAP_ACTOR 2   /* index of the actor behind MPC_CLQ_MIN_OBS_DIST (-1.0: no car ever
+                                     emitted); on ties the earliest step, then the lowest index              */
+#define MPC_TR_NX 3
+
+/* Per step, for an ego still in the loop, the actors are visited in index order on the state before the step
+ * (s, v), with the arithmetic and tests of ObstaclesFSM.update applied to that actor's own state:
+ *   car    triggers once, when s >= trigger_s; while active its position advances by v * dt from pos_s; past
+ *          end_s it goes inactive for good, otherwise it appends (position, v) to the slab;
+ *   light  while RED and 0 < pos_s - s < trigger_s it appends (pos_s, 0) and sets its waiting flag when
+ *          v < 0.1 and the distance is < 10; while waiting its timer advances by dt; GREEN at
+ *          timer >= stop_duration.
+ * The slab holds the emitted entries in actor order and n_obs is their count.  When any actor of any script is
+ * not NONE the solver runs with max_obs = A on the obstacle kernels, otherwise with no slab (like the sweep
+ * without scenarios); an ego whose own actors are all NONE gets n_obs = 0.  The plant, the exit test, the list
+ * compaction every 8 steps and the step timing are mpc_closed_loop_sweep's.
+ *   actors, A, n_scripts   [n_scripts][A], 0 <= A <= MPC_MAX_ACTORS; n_scripts == B: a script per ego;
+ *                n_scripts == 1: one shared script; actors NULL with A == 0 and n_scripts == 0: none.
+ *   quant        [B][MPC_CL_NQ], required; the sweep's columns (mpc_cl_verdicts reads it unchanged).
+ *                MPC_CLQ_MIN_OBS_DIST is the running minimum of position - s over every step and every car
+ *                that emitted at that step (actor order within a step; the sweep's NaN rule; NaN if never);
+ *                MPC_CLQ_RED_PASS is 1.0 if any light was passed on red, each light decided once, at the first
+ *                step that starts with s > pos_s, with that light's colour after this step's update.
+ *   extra        [B][MPC_TR_NX], optional.
+ *   hist_egos .. as in the sweep.  hist_car_s [n_hist][max_steps]: the first car in the slab, NaN if none;
+ *                hist_tl [n_hist][max_steps]: bit a is set when actor a is a light that is GREEN after this
+ *                step's update; hist_nobs [n_hist][max_steps]; hist_slab [n_hist][max_steps][A][2]: this
+ *                step's slab, NaN past n_obs.  Tails are NaN / -1.  n_steps, step_ms: optional.
+ * Misuse (A out of range, n_scripts not in {0 with NULL, 1, B}, a kind outside 0..2, quant NULL, n_hist < 0,
+ * a history pointer with n_hist == 0, hist_slab with A == 0, an index out of range or repeated) is MPC_E_ARG.
+ * Device memory is O(B * A) + O(n_hist * max_steps * A). */
+int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, const mpc_actor* actors, int A, int n_scripts,
+                            int max_steps, double s_stop, double* quant, double* extra, int n_hist,
+                            const int* hist_egos, double* hist_x, double* hist_u, double* hist_car_s, int* hist_tl,
+                            int* hist_status, int* hist_nobs, double* hist_slab, int* n_steps, double* step_ms);
 
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no

@@ -47,13 +47,20 @@ class MpcFsm(C.Structure):
                 ("tl_stop_duration", C.c_double)]
 
 
+class MpcActor(C.Structure):
+    """`mpc_actor` of include/mpcqp.h: one car or light of a traffic script (mpc_closed_loop_traffic)."""
+    _fields_ = [("kind", C.c_int), ("trigger_s", C.c_double), ("pos_s", C.c_double), ("v", C.c_double),
+                ("end_s", C.c_double), ("stop_duration", C.c_double)]
+
+
 class MpcError(RuntimeError):
     pass
 
 
 EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_batch_device", "mpc_lookup",
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
-           "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
+           "mpc_closed_loop_traffic", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -63,6 +70,12 @@ CLQ_FIELDS = ("ego", "n_steps", "s_final", "max_dev", "u1_min", "u1_max", "u2_mi
               "min_obs_dist", "red_pass", "n_infeasible", "n_not_ok")
 # verdict bits of mpc_cl_verdicts (MPC_CLV_*), sanity_checks.check_verdicts' order
 CLV_NAMES = ("destination", "on_road", "steer_ok", "accel_ok", "realtime", "obstacle_ok", "light_ok", "passed")
+# mpc_closed_loop_traffic: actor kinds (MPC_ACTOR_*), the script width limit, the columns of `extra` (MPC_TRX_*)
+ACTOR_NONE, ACTOR_CAR, ACTOR_LIGHT = 0, 1, 2
+MAX_ACTORS = 16
+TRX_MAX_NOBS, TRX_N_RED_PASS, TRX_MIN_GAP_ACTOR = 0, 1, 2
+TR_NX = 3
+TRX_FIELDS = ("max_nobs", "n_red_pass", "min_gap_actor")
 
 _lib = None
 
@@ -107,6 +120,12 @@ def lib():
                                         C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp]
     L.mpc_cl_verdicts.restype = C.c_int
     L.mpc_cl_verdicts.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _ip]
+    L.mpc_actors_from_fsm.restype = None
+    L.mpc_actors_from_fsm.argtypes = [C.POINTER(MpcFsm), C.POINTER(MpcActor)]
+    L.mpc_closed_loop_traffic.restype = C.c_int
+    L.mpc_closed_loop_traffic.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(MpcActor), C.c_int, C.c_int, C.c_int,
+                                          C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp,
+                                          _ip, _dp]
     L.mpc_comm_unique_id.restype = C.c_int
     L.mpc_comm_unique_id.argtypes = [C.c_char_p]
     L.mpc_comm_create.restype = C.c_int
@@ -148,6 +167,26 @@ def default_fsm(**kw):
     for k, v in kw.items():
         setattr(f, k, v)
     return f
+
+
+def car(trigger_s, start_s, v, end_s):
+    """A car of a traffic script: spawned at start_s once the ego reaches trigger_s, driving at v until end_s."""
+    return MpcActor(kind=ACTOR_CAR, trigger_s=float(trigger_s), pos_s=float(start_s), v=float(v),
+                    end_s=float(end_s))
+
+
+def light(pos_s, trigger_s, stop_duration):
+    """A light of a traffic script at pos_s: an obstacle while RED and closer than trigger_s; GREEN after the
+    ego has stood in front of it for stop_duration seconds."""
+    return MpcActor(kind=ACTOR_LIGHT, trigger_s=float(trigger_s), pos_s=float(pos_s),
+                    stop_duration=float(stop_duration))
+
+
+def actors_from_fsm(fsm):
+    """mpc_actors_from_fsm: [car, light] restating an MpcFsm (ACTOR_NONE in place of a switch that is off)."""
+    out = (MpcActor * 2)()
+    lib().mpc_actors_from_fsm(C.byref(fsm), out)
+    return [MpcActor.from_buffer_copy(a) for a in out]
 
 
 def read_trajectory_json(path):
@@ -296,6 +335,50 @@ class Solver:
             ht = np.empty((0, max_steps), np.int32); hs = np.empty((0, max_steps), np.int32)
         return dict(quant=quant, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu, hist_obs_s=ho,
                     hist_tl=ht, hist_status=hs)
+
+    def closed_loop_traffic(self, x_init, scripts, max_steps, s_stop=None, s_max=None, hist_egos=(), lo=0):
+        """mpc_closed_loop_traffic: closed_loop_sweep with a traffic script of up to MAX_ACTORS actors per ego.
+        x_init [B,5]; scripts: None (no script), one sequence of MpcActor (shared by all egos), or a sequence of
+        B such sequences of one length A (ego b runs scripts[b]).
+        Returns closed_loop_sweep's dict with hist_car_s in place of hist_obs_s and hist_tl a bitmask (bit a:
+        actor a is a GREEN light), plus extra [B,3] (columns TRX_FIELDS), hist_nobs [n_hist,max_steps] and
+        hist_slab [n_hist,max_steps,A,2] (NaN past n_obs)."""
+        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
+        B = x_init.shape[0]
+        if s_stop is None:
+            if s_max is None:
+                raise ValueError("give s_stop or s_max")
+            s_stop = s_max - 1.0
+        if scripts is None:
+            arr, A, n_scripts = None, 0, 0
+        else:
+            scripts = list(scripts)
+            rows = [scripts] if all(isinstance(a, MpcActor) for a in scripts) else [list(r) for r in scripts]
+            n_scripts = len(rows)
+            A = len(rows[0]) if rows else 0
+            if any(len(r) != A for r in rows):
+                raise ValueError("every script must have the same number of actors (pad with ACTOR_NONE)")
+            buf = (MpcActor * max(n_scripts * A, 1))()
+            for i, r in enumerate(rows):
+                for a, act in enumerate(r):
+                    C.memmove(C.byref(buf, (i * A + a) * C.sizeof(MpcActor)), C.byref(act), C.sizeof(MpcActor))
+            arr = C.cast(buf, C.POINTER(MpcActor))
+        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
+        nh = he.size
+        quant = np.empty((B, CL_NQ)); extra = np.empty((B, TR_NX))
+        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
+        hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
+        ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
+        hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, A, 2))
+        g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
+        gi = (lambda a: _pi(a) if nh else None)
+        _check(lib().mpc_closed_loop_traffic(self.h, B, _p(x_init), arr, int(A), int(n_scripts), int(max_steps),
+                                             float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(hc),
+                                             gi(ht), gi(hs), gi(hn), g(hl) if A else None, _pi(ns), _p(sm)),
+               "mpc_closed_loop_traffic")
+        quant[:, 0] += lo
+        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
+                    hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl)
 
     def cl_verdicts(self, quant, s_total):
         """mpc_cl_verdicts: the restated acceptance verdicts (sanity_checks.check_verdicts, with this context's

@@ -357,6 +357,87 @@ def run_scenario_sweep(mpc, scenarios, trajectory, x_init, max_steps=2000, hist_
     return r
 
 
+class TrafficScript:
+    """A traffic script for one ego: a list of actors (mpcqp.car(...), mpcqp.light(...), or mpcqp.MpcActor() as a
+    placeholder), each running ObstaclesFSM's per-obstacle state machine on its own state.  update() is the host
+    restatement of one step of mpc_closed_loop_traffic for this ego, in the reference's update() shape, so the
+    one-ego loop (run_simulation's) can drive it; run_traffic_sweep runs many of them on the device."""
+
+    def __init__(self, actors=()):
+        self.actors = list(actors)
+        if len(self.actors) > mpcqp.MAX_ACTORS:
+            raise ValueError(f"at most {mpcqp.MAX_ACTORS} actors per script")
+        for a in self.actors:
+            if a.kind not in (mpcqp.ACTOR_NONE, mpcqp.ACTOR_CAR, mpcqp.ACTOR_LIGHT):
+                raise ValueError(f"actor kind {a.kind} outside ACTOR_NONE .. ACTOR_LIGHT")
+        # per actor: car [position, active, triggered]; light [timer, green, waiting]
+        self.state = [[a.pos_s if a.kind == mpcqp.ACTOR_CAR else 0.0, False, False] for a in self.actors]
+
+    @classmethod
+    def from_fsm(cls, fsm):
+        """[car, light] restating an ObstaclesFSM (a placeholder for a switch that is off; mpc_actors_from_fsm)."""
+        return cls(mpcqp.actors_from_fsm(_fsm_record(fsm)))
+
+    def padded(self, A):
+        """The actors padded with placeholders to A entries (every script of one call has the same length)."""
+        if len(self.actors) > A:
+            raise ValueError("script longer than the requested width")
+        return self.actors + [mpcqp.MpcActor() for _ in range(A - len(self.actors))]
+
+    def update(self, dt, s, v):
+        """One step on the ego state before the step.  Returns (active_obstacles, states): the obstacles in
+        actor order as ObstaclesFSM.update's dicts, and one state per actor ('WAITING' / 'ACTIVE' / 'COMPLETED'
+        for a car, 'RED' / 'GREEN' for a light, None for a placeholder)."""
+        active, states = [], []
+        for a, st in zip(self.actors, self.state):
+            if a.kind == mpcqp.ACTOR_CAR:
+                if s >= a.trigger_s and not st[2]:
+                    st[2] = st[1] = True
+                if st[1]:
+                    st[0] += a.v * dt
+                    if st[0] > a.end_s:
+                        st[1] = False
+                    else:
+                        active.append({"s": st[0], "v": a.v, "type": "car"})
+                states.append("ACTIVE" if st[1] else ("COMPLETED" if st[2] else "WAITING"))
+            elif a.kind == mpcqp.ACTOR_LIGHT:
+                if not st[1]:
+                    gap = a.pos_s - s
+                    if 0 < gap < a.trigger_s:
+                        active.append({"s": a.pos_s, "v": 0.0, "type": "light"})
+                        if v < 0.1 and gap < 10.0:
+                            st[2] = True
+                    if st[2]:
+                        st[0] += dt
+                        if st[0] >= a.stop_duration:
+                            st[1], st[2] = True, False
+                states.append("GREEN" if st[1] else "RED")
+            else:
+                states.append(None)
+        return active, states
+
+
+def run_traffic_sweep(mpc, scripts, trajectory, x_init, max_steps=2000, hist_egos=(), s_stop=None):
+    """run_scenario_sweep with a traffic script per ego (mpc_closed_loop_traffic): ego b starts at x_init[b] and
+    runs scripts[b], a TrafficScript, a sequence of actors, or None (no actor); shorter scripts are padded with
+    placeholders to the longest.  Returns mpcqp.Solver.closed_loop_traffic's dict plus 'verdicts' [B], 'counts'
+    and one boolean column [B] per verdict name, like run_scenario_sweep."""
+    x_init = np.asarray(x_init, np.float64).reshape(-1, 5)
+    scripts = [s if isinstance(s, TrafficScript) else TrafficScript(s or ()) for s in scripts]
+    if len(scripts) != x_init.shape[0]:
+        raise ValueError("one script (or None) per ego")
+    A = max((len(s.actors) for s in scripts), default=0)
+    rows = [s.padded(A) for s in scripts] if A else None
+    slv = mpc.solver(max_obs=0)
+    r = slv.closed_loop_traffic(x_init, rows, max_steps, s_stop=s_stop, s_max=trajectory.s_max, hist_egos=hist_egos)
+    v, counts = slv.cl_verdicts(r["quant"], trajectory.s_max)
+    r["verdicts"] = v
+    r["counts"] = {k: int(counts[i]) for i, k in enumerate(mpcqp.CLV_NAMES)}
+    for i, k in enumerate(mpcqp.CLV_NAMES):
+        r[k] = (v & (1 << i)) != 0
+    return r
+
+
 def closed_loop_checks(mpc, fsm, trajectory, r, verbose=False):
     """The restated trajectory_tracking_check (sanity_checks.py:79-184) on every ego of a closed_loop()
     result (mpcqp.Solver.closed_loop layout); returns the per-ego verdicts [B] (bool)."""

@@ -1,0 +1,193 @@
+// Stand-alone sanitizer check of the host backend's traffic loop (csrc/cpu_backend.h: closed_loop_traffic),
+// built and run by tools/traffic_host_check.py with -fsanitize=address,undefined:
+//   traffic_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
+// Runs on 3 worker threads, N = 5: (1) the six scenarios of tools/sweep_host_check.cpp as two-actor scripts
+// (what mpc_actors_from_fsm makes of them) and padded to A = 5, every history kept, against closed_loop_sweep:
+// the common histories and every quantity column but the step time must be equal byte for byte; (2) six scripts
+// of A = 8 (three cars, two lights, eight cars at once, an interleaved script, all placeholders, never
+// triggering), with two selected egos, with no history and no extras, with a shared script, and with A = 0.
+// Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/mpcqp.h"
+#include "../safe-autonomous-driving-mpc_amd/csrc/cpu_backend.h"
+
+static mpc_fsm scenario(int dyn, int tl) {
+    mpc_fsm f;
+    std::memset(&f, 0, sizeof(f));
+    f.dynamic_obstacle = dyn; f.traffic_light = tl;
+    f.obs_trigger_s = 710.0; f.obs_start_s = 780.0; f.obs_v = 4.0; f.obs_end_s = 1050.0;
+    f.tl_pos = 550.0; f.tl_trigger_s = 100.0; f.tl_stop_duration = 20.0;
+    return f;
+}
+
+static mpc_actor none() {
+    mpc_actor a;
+    std::memset(&a, 0, sizeof(a));
+    return a;
+}
+static mpc_actor car(double trigger_s, double start_s, double v, double end_s) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_CAR; a.trigger_s = trigger_s; a.pos_s = start_s; a.v = v; a.end_s = end_s;
+    return a;
+}
+static mpc_actor light(double pos_s, double trigger_s, double stop_duration) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_LIGHT; a.trigger_s = trigger_s; a.pos_s = pos_s; a.stop_duration = stop_duration;
+    return a;
+}
+// mpc_actors_from_fsm (csrc/mpcqp.hip) restated: the library itself is not linked here
+static void from_fsm(const mpc_fsm& f, mpc_actor* out) {
+    out[0] = f.dynamic_obstacle ? car(f.obs_trigger_s, f.obs_start_s, f.obs_v, f.obs_end_s) : none();
+    out[1] = f.traffic_light ? light(f.tl_pos, f.tl_trigger_s, f.tl_stop_duration) : none();
+}
+
+struct Run {
+    std::vector<double> quant, extra, hx, hu, hc, hl, step_ms;
+    std::vector<int> ht, hs, hn, n_steps;
+    int rc = 0;
+};
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[2];
+    if (std::fread(hdr, sizeof(int), 2, f) != 2) return 2;
+    const int T = hdr[0], Tu = hdr[1];
+    std::vector<double> X(5 * (size_t)T), U(2 * (size_t)Tu);
+    if (std::fread(X.data(), 8, X.size(), f) != X.size() || std::fread(U.data(), 8, U.size(), f) != U.size()) return 2;
+    std::fclose(f);
+    mpcqp_host::HostTable table;
+    if (!mpcqp_host::build_host_table(X.data(), T, U.data(), Tu, table)) return 2;
+    mpcqp_cpu::Backend be(std::move(table));
+    be.threads = 3;
+    mpc_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.N = 5; p.max_obs = 0; p.dt = 0.2;
+    p.u_min[0] = -0.6; p.u_min[1] = -5.0; p.u_max[0] = 0.6; p.u_max[1] = 4.0;
+    p.vehicle_radius = 1.0; p.w_d = 10.0; p.w_o = 10.0; p.w_v = 5.0; p.w_u1 = 0.5; p.w_u2 = 0.5;
+    p.obstacle_safety_distance = 5.0; p.max_time_2_obs = 1.5; p.wheelbase = 2.8; p.lane_width = 3.0;
+    p.safe_lane_margin = 0.1; p.brake_distance = 40.0; p.brake_accel = -2.0; p.linearization = 1;
+    p.sqp_iters = 1; p.max_iter = 80; p.tol = 1e-9; p.tol_mu = 1e-10; p.elastic_rho = 1e5; p.polish = 2;
+    p.sqp_tol = 1e-10;
+
+    const int B = 6, ms = 400;
+    const size_t ns = ms;
+    const double s0 = 440.0, far = 1.0e6;
+    std::vector<double> x0(5 * (size_t)B, 0.0);
+    for (int b = 0; b < B; ++b) {
+        double st[5];
+        be.ref->state(s0 + b, st);
+        x0[5 * b] = s0 + b; x0[5 * b + 1] = 0.01 * (b % 3); x0[5 * b + 3] = st[3]; x0[5 * b + 4] = 9.0;
+    }
+    auto run = [&](const std::vector<mpc_actor>& scripts, int A, int n_scripts, bool with_slab, double s_stop,
+                   const std::vector<int>& egos, bool extras) {
+        Run r;
+        const int nh = (int)egos.size();
+        std::vector<int> slot(B, -1);
+        for (int k = 0; k < nh; ++k) slot[egos[k]] = k;
+        r.quant.assign((size_t)B * MPC_CL_NQ, -1.0);
+        r.extra.assign((size_t)B * MPC_TR_NX, -7.0);
+        r.hx.assign((size_t)nh * (ns + 1) * 5, 0.0); r.hu.assign((size_t)nh * ns * 2, 0.0);
+        r.hc.assign((size_t)nh * ns, 0.0); r.hl.assign((size_t)nh * ns * A * 2, 0.0);
+        r.ht.assign((size_t)nh * ns, 0); r.hs.assign((size_t)nh * ns, 0); r.hn.assign((size_t)nh * ns, 0);
+        r.n_steps.assign(B, 0); r.step_ms.assign(ns, 0.0);
+        r.rc = be.closed_loop_traffic(p, B, x0.data(), scripts.empty() ? nullptr : scripts.data(), A, n_scripts,
+                                      with_slab, ms, s_stop, r.quant.data(), extras ? r.extra.data() : nullptr, nh,
+                                      slot.data(), nh ? r.hx.data() : nullptr, nh ? r.hu.data() : nullptr,
+                                      nh ? r.hc.data() : nullptr, nh ? r.ht.data() : nullptr,
+                                      nh ? r.hs.data() : nullptr, nh ? r.hn.data() : nullptr,
+                                      nh && A ? r.hl.data() : nullptr, extras ? r.n_steps.data() : nullptr,
+                                      extras ? r.step_ms.data() : nullptr);
+        return r;
+    };
+    auto quant_differs = [&](const std::vector<double>& a, const std::vector<double>& b) {
+        int bad = 0;
+        for (int e = 0; e < B; ++e)
+            for (int k = 0; k < MPC_CL_NQ; ++k) {
+                if (k == MPC_CLQ_MAX_STEP_MS) continue;          // a wall-clock measurement of each run
+                bad += std::memcmp(&a[(size_t)e * MPC_CL_NQ + k], &b[(size_t)e * MPC_CL_NQ + k], 8) != 0;
+            }
+        return bad;
+    };
+    const std::vector<int> all = {0, 1, 2, 3, 4, 5};
+    int bad = 0;
+
+    // (1) the six scenarios of the sweep check, through the sweep and as scripts
+    std::vector<mpc_fsm> F(B);
+    F[0] = scenario(1, 0); F[0].obs_trigger_s = s0 + 10; F[0].obs_start_s = s0 + 40; F[0].obs_end_s = far;
+    F[1] = scenario(1, 0); F[1].obs_trigger_s = s0 + 5; F[1].obs_start_s = s0 + 30; F[1].obs_v = 2.0; F[1].obs_end_s = far;
+    F[2] = scenario(0, 1); F[2].tl_pos = s0 + 30; F[2].tl_stop_duration = 1.0;
+    F[3] = scenario(0, 1); F[3].tl_pos = s0 + 30; F[3].tl_stop_duration = 3.0;
+    F[4] = scenario(1, 1); F[4].tl_pos = s0 + 30; F[4].tl_stop_duration = 1.0; F[4].obs_trigger_s = s0 + 35;
+    F[4].obs_start_s = s0 + 70; F[4].obs_end_s = far;
+    F[5] = scenario(1, 1); F[5].obs_trigger_s = far; F[5].tl_pos = far;
+    const double s_stop = s0 + 60.0;
+    std::vector<double> q_sw((size_t)B * MPC_CL_NQ), sx((size_t)B * (ns + 1) * 5), su((size_t)B * ns * 2),
+        so((size_t)B * ns), sm(ns);
+    std::vector<int> stl((size_t)B * ns), sst((size_t)B * ns), sn(B);
+    if (be.closed_loop_sweep(p, B, x0.data(), F.data(), B, true, ms, s_stop, q_sw.data(), B, all.data(), sx.data(),
+                             su.data(), so.data(), stl.data(), sst.data(), sn.data(), sm.data()))
+        return 1;
+    for (int padded = 0; padded < 2; ++padded) {
+        const int A = padded ? 5 : 2, ic = padded ? 1 : 0, il = padded ? 3 : 1;
+        std::vector<mpc_actor> scripts((size_t)B * A, none());
+        for (int b = 0; b < B; ++b) {
+            mpc_actor two[2];
+            from_fsm(F[b], two);
+            scripts[(size_t)b * A + ic] = two[0];
+            scripts[(size_t)b * A + il] = two[1];
+        }
+        Run r = run(scripts, A, B, true, s_stop, all, true);
+        bad += r.rc != 0;
+        bad += quant_differs(r.quant, q_sw);
+        bad += std::memcmp(r.hx.data(), sx.data(), sx.size() * 8) != 0;
+        bad += std::memcmp(r.hu.data(), su.data(), su.size() * 8) != 0;
+        bad += std::memcmp(r.hc.data(), so.data(), so.size() * 8) != 0;
+        bad += std::memcmp(r.hs.data(), sst.data(), sst.size() * 4) != 0;
+        bad += std::memcmp(r.n_steps.data(), sn.data(), sn.size() * 4) != 0;
+        for (size_t i = 0; i < stl.size(); ++i) bad += (r.ht[i] < 0 ? -1 : (r.ht[i] >> il) & 1) != stl[i];
+    }
+
+    // (2) scripts of A = 8
+    const int A = 8;
+    std::vector<mpc_actor> S((size_t)B * A, none());
+    S[0] = car(s0 + 5, s0 + 40, 4.0, far); S[1] = car(s0 + 10, s0 + 60, 6.0, s0 + 75); S[2] = car(s0 + 20, s0 + 90, 3.0, far);
+    S[A] = light(s0 + 30, 100.0, 1.0); S[A + 1] = light(s0 + 55, 20.0, 0.6);
+    for (int k = 0; k < A; ++k) S[2 * A + k] = car(s0 - 1, s0 + 30 + 6.0 * k, 5.0 + 0.5 * k, far);
+    S[3 * A] = light(s0 + 30, 100.0, 2.0); S[3 * A + 2] = car(s0 + 35, s0 + 75, 7.0, far);
+    S[3 * A + 4] = light(s0 + 60, 20.0, 0.4); S[3 * A + 5] = car(s0 + 40, s0 + 95, 6.0, far);
+    S[5 * A] = car(far, s0 + 30, 4.0, far); S[5 * A + 1] = light(far, 100.0, 1.0);
+    const double s_stop8 = s0 + 80.0;
+    Run full = run(S, A, B, true, s_stop8, all, true);
+    Run two = run(S, A, B, true, s_stop8, {4, 1}, true);
+    Run bare = run(S, A, B, true, s_stop8, {}, false);
+    bad += full.rc != 0 || two.rc != 0 || bare.rc != 0;
+    bad += quant_differs(full.quant, two.quant) + quant_differs(full.quant, bare.quant);
+    bad += std::memcmp(full.extra.data(), two.extra.data(), full.extra.size() * 8) != 0;
+    bad += bare.extra[0] != -7.0;                                // extra NULL: untouched
+    const size_t row = ns * A * 2;
+    bad += std::memcmp(two.hl.data(), full.hl.data() + 4 * row, row * 8) != 0;
+    bad += std::memcmp(two.hl.data() + row, full.hl.data() + 1 * row, row * 8) != 0;
+    bad += std::memcmp(two.hn.data() + ns, full.hn.data() + 1 * ns, ns * 4) != 0;
+    bad += full.extra[2 * MPC_TR_NX + MPC_TRX_MAX_NOBS] != 8.0;  // the eight cars were all in one slab
+    bad += full.extra[4 * MPC_TR_NX + MPC_TRX_MAX_NOBS] != 0.0 || full.extra[4 * MPC_TR_NX + MPC_TRX_MIN_GAP_ACTOR] != -1.0;
+    for (int b = 0; b < B; ++b) bad += full.n_steps[b] <= 0;
+    // one shared script == the same script for every ego
+    std::vector<mpc_actor> one(S.begin(), S.begin() + A), rep;
+    for (int b = 0; b < B; ++b) rep.insert(rep.end(), one.begin(), one.end());
+    Run sh = run(one, A, 1, true, s_stop8, all, true), pe = run(rep, A, B, true, s_stop8, all, true);
+    bad += sh.rc != 0 || pe.rc != 0 || quant_differs(sh.quant, pe.quant);
+    bad += std::memcmp(sh.hl.data(), pe.hl.data(), sh.hl.size() * 8) != 0;
+    bad += std::memcmp(sh.hx.data(), pe.hx.data(), sh.hx.size() * 8) != 0;
+    // no actors at all: A = 0, no slab
+    Run empty = run({}, 0, 1, false, s_stop8, {2}, true);
+    bad += empty.rc != 0 || empty.extra[MPC_TRX_MIN_GAP_ACTOR] != -1.0 || empty.hn[0] != 0;
+    std::printf("traffic_host_check: %d mismatches; n_steps", bad);
+    for (int b = 0; b < B; ++b) std::printf(" %d", full.n_steps[b]);
+    std::printf("\n");
+    return bad ? 1 : 0;
+}
