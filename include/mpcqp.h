@@ -33,7 +33,8 @@ extern "C" {
  *    MPC_STATUS_MASK before comparing with MPC_OK .. MPC_NUMERICAL (version 1 returned 0-3 only).
  * 3: the ego-shard communicator (mpc_comm_*, mpc_gather*, MPC_E_COMM); nothing else changed.
  * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed.
- * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed. */
+ * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
+ *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -310,6 +311,43 @@ int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, const mpc_a
                             int max_steps, double s_stop, double* quant, double* extra, int n_hist,
                             const int* hist_egos, double* hist_x, double* hist_u, double* hist_car_s, int* hist_tl,
                             int* hist_status, int* hist_nobs, double* hist_slab, int* n_steps, double* step_ms);
+
+/* Closed-loop convoys: mpc_closed_loop_traffic in which the egos of one world see each other.  Egos
+ * [w*W, (w+1)*W) form world w; every world drives the context's one reference line and egos of different worlds
+ * never see each other.  A world with fewer cars is made by starting the spare egos past s_stop.
+ *   ahead-of   within a world ego j is ahead of ego i iff s_j > s_i, or s_j == s_i and j < i, on the states
+ *              before the step: a strict total order.
+ *   leaders    per step, for an ego still in the loop: the egos of its world that are ahead of it and still in
+ *              the loop (an ego that passed s_stop or went NaN is gone from the next step on), nearest first in
+ *              that order, at most K, cut at the first one with s_j - s_i >= lead_range.  Each appends
+ *              (s_j, v_j), the leader's state before the step (v_j as it is, NaN included), to the slab after
+ *              the ego's script entries; n_obs counts both.  Followers are invisible to leaders.
+ *   actors, A, n_scripts   mpc_closed_loop_traffic's, the same state machines in the same order.
+ *   W, K, lead_range   1 <= W <= MPC_MAX_WORLD, B a multiple of W; 0 <= K, A + K <= MPC_MAX_ACTORS;
+ *              lead_range > 0 (+inf allowed).
+ * The solver runs with max_obs = A + K when any actor is not NONE or when K > 0 and W > 1, otherwise with no
+ * slab.  With W == 1 or K == 0 every output the traffic entry has equals mpc_closed_loop_traffic's bit for bit.
+ *   quant      [B][MPC_CL_NQ], required.  MPC_CLQ_MIN_OBS_DIST is the running minimum over scripted cars and
+ *              leaders (within a step the cars in actor order, then the leaders in slab order; strict <, the
+ *              sweep's NaN rule): a leader is a car for the obstacle verdict.
+ *   extra      [B][MPC_CV_NX], optional.  Columns 0..2 are the traffic extras, MPC_TRX_MAX_NOBS over the whole
+ *              slab and MPC_TRX_MIN_GAP_ACTOR -1.0 also when a leader holds the minimum.
+ *   hist_*     the traffic entry's, with hist_slab [n_hist][max_steps][A+K][2] and
+ *              hist_lead [n_hist][max_steps][K]: the leaders' batch indices in slab order, -1 past them and
+ *              past n_steps.  hist_car_s stays the first scripted car.
+ * Misuse: the traffic entry's cases, W out of range, B % W != 0, K out of range, A + K > MPC_MAX_ACTORS,
+ * lead_range <= 0 or NaN, hist_lead with K == 0 or n_hist == 0, hist_slab with A + K == 0: MPC_E_ARG.
+ * Device memory is O(B * (A + K)) + O(n_hist * max_steps * (A + K)). */
+#define MPC_MAX_WORLD 256
+#define MPC_CVX_MIN_LEAD_GAP 3    /* min (s_j - s_i) over leaders only; NaN if the ego never had a leader     */
+#define MPC_CVX_MIN_LEAD_EGO 4    /* batch index of the leader behind it (earliest step, then slab order); -1 */
+#define MPC_CVX_MAX_LEADERS 5     /* largest number of leaders in one step                                    */
+#define MPC_CV_NX 6
+int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                           const mpc_actor* actors, int A, int n_scripts, int max_steps, double s_stop,
+                           double* quant, double* extra, int n_hist, const int* hist_egos, double* hist_x,
+                           double* hist_u, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                           double* hist_slab, int* hist_lead, int* n_steps, double* step_ms);
 
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no

@@ -1430,6 +1430,226 @@ struct Backend {
         if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
         return MPC_SUCCESS;
     }
+
+    // mpc_closed_loop_convoy on the host: closed_loop_traffic above with the egos [w*W, (w+1)*W) of a world as
+    // each other's obstacles.  Per step every world's egos still in the loop are sorted by the ahead-of order
+    // (the larger s first, on equal s the lower index) on the states before the step; an ego's leaders are its
+    // predecessors in that order, nearest first, at most K, cut at the first gap >= lead_range, appended as
+    // (s, v) after its script entries.  The slab is A + K wide (hist_slab [n_hist][max_steps][A+K][2]),
+    // hist_lead [n_hist][max_steps][K] holds the leaders' batch indices, extra is [B][MPC_CV_NX]
+    int closed_loop_convoy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
+                           const mpc_actor* actors, int A, int n_scripts, bool with_slab, int max_steps,
+                           double s_stop, double* quant, double* extra, int n_hist, const int* slot, double* hist_x,
+                           double* hist_u, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                           double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
+        mpc_params p = p0;
+        const int AK = A + K;
+        p.max_obs = with_slab ? AK : 0;
+        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
+        const size_t nak = (size_t)AK;
+        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
+        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
+        if (hist_car_s) std::fill(hist_car_s, hist_car_s + nh * ns, NAN);
+        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
+        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
+        if (hist_nobs) std::fill(hist_nobs, hist_nobs + nh * ns, -1);
+        if (hist_slab) std::fill(hist_slab, hist_slab + nh * ns * nak * 2, NAN);
+        if (hist_lead) std::fill(hist_lead, hist_lead + nh * ns * nk, -1);
+        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
+        enum { CAR_ACTIVE = 1, CAR_TRIGGERED = 2, TL_GREEN = 4, TL_WAITING = 8, PASS_DECIDED = 16 };
+        std::vector<double> x(x_init, x_init + nb * 5), aval(nb * na, 0.0), ex(nb * MPC_CV_NX, 0.0), ms;
+        std::vector<int> aflags(nb * na, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
+        std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
+        std::vector<double> xa, obsa, u0a;
+        std::vector<int> nobsa, sta;
+        for (int b = 0; b < B; ++b) {
+            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+            for (int a = 0; a < A; ++a)
+                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
+            active[b] = x[5 * (size_t)b] <= s_stop;
+            if (hist_x && slot[b] >= 0)
+                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+            double* q = quant + (size_t)b * MPC_CL_NQ;
+            std::fill(q, q + MPC_CL_NQ, 0.0);
+            q[MPC_CLQ_EGO] = (double)b;
+            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
+            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
+            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
+            double* e = ex.data() + (size_t)b * MPC_CV_NX;
+            e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+            e[MPC_CVX_MIN_LEAD_GAP] = NAN;
+            e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
+        }
+        for (int step = 0; step < max_steps; ++step) {
+            const auto t0 = std::chrono::steady_clock::now();
+            alist.clear();
+            for (int b = 0; b < B; ++b)
+                if (active[b]) alist.push_back(b);
+            if (alist.empty()) break;
+            const int nl = (int)alist.size();
+            // alist is increasing, so each world's egos in the loop are one run of it: sort the run, and
+            // order[rank[b] - 1], order[rank[b] - 2], .. down to the run's start are ego b's leaders
+            order = alist;
+            for (int i = 0, w = 0; w <= B / W; ++w) {
+                while (i < nl && alist[i] < w * W) ++i;
+                wbeg[w] = i;
+            }
+            for (int w = 0; w < B / W; ++w)
+                std::sort(order.begin() + wbeg[w], order.begin() + wbeg[w + 1], [&](int a, int b) {
+                    const double sa = x[5 * (size_t)a], sb = x[5 * (size_t)b];
+                    return sa > sb || (sa == sb && a < b);
+                });
+            for (int i = 0; i < nl; ++i) rank[order[i]] = i;
+            xa.assign((size_t)nl * 5, 0.0);
+            obsa.assign((size_t)nl * nak * 2, 0.0);
+            nobsa.assign(nl, 0);
+            u0a.assign((size_t)nl * 2, 0.0);
+            sta.assign(nl, 0);
+            for (int i = 0; i < nl; ++i) {
+                const int b = alist[i];
+                const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
+                double* o = obsa.data() + (size_t)i * nak * 2;
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                double* e = ex.data() + (size_t)b * MPC_CV_NX;
+                int n = 0, green = 0, have_car = 0;
+                double car_s = NAN;
+                for (int a = 0; a < A; ++a) {
+                    const mpc_actor& M = sc[a];
+                    if (M.kind == MPC_ACTOR_NONE) continue;
+                    int& fl = aflags[(size_t)b * na + a];
+                    double& val = aval[(size_t)b * na + a];
+                    if (M.kind == MPC_ACTOR_CAR) {               // ObstaclesFSM.update, :335-349, this car's state
+                        if (!(fl & CAR_TRIGGERED) && s >= M.trigger_s) fl |= CAR_TRIGGERED | CAR_ACTIVE;
+                        if (fl & CAR_ACTIVE) {
+                            val = val + M.v * p.dt;
+                            if (val > M.end_s) {
+                                fl &= ~CAR_ACTIVE;
+                            } else {
+                                o[2 * n] = val;
+                                o[2 * n + 1] = M.v;
+                                ++n;
+                                if (!have_car) { have_car = 1; car_s = val; }
+                                if (val == val) {                // the gap of check_quantities, over every car
+                                    const double g = val - s;
+                                    if (!(qflags[b] & 1)) {
+                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
+                                        qflags[b] |= 1;
+                                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
+                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
+                                    }
+                                }
+                            }
+                        }
+                    } else {                                     // :351-372, this light's state
+                        if (!(fl & TL_GREEN)) {
+                            const double dist = M.pos_s - s;
+                            if (0.0 < dist && dist < M.trigger_s) {
+                                o[2 * n] = M.pos_s;
+                                o[2 * n + 1] = 0.0;
+                                ++n;
+                                if (v < 0.1 && dist < 10.0) fl |= TL_WAITING;
+                            }
+                            if (fl & TL_WAITING) {
+                                val += p.dt;
+                                if (val >= M.stop_duration) fl = (fl | TL_GREEN) & ~TL_WAITING;
+                            }
+                        }
+                        if (fl & TL_GREEN) green |= 1 << a;
+                        if (!(fl & PASS_DECIDED) && s > M.pos_s) {   // the first state past this light
+                            fl |= PASS_DECIDED;
+                            if (!(fl & TL_GREEN)) {
+                                q[MPC_CLQ_RED_PASS] = 1.0;
+                                e[MPC_TRX_N_RED_PASS] += 1.0;
+                            }
+                        }
+                    }
+                }
+                int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
+                const int r = rank[b], r0 = wbeg[b / W];
+                int nlead = 0;
+                for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {      // the leaders, nearest first
+                    const int j = order[r - 1 - nlead];
+                    const double sj = x[5 * (size_t)j], g = sj - s;
+                    if (g >= lead_range) break;
+                    o[2 * n] = sj;
+                    o[2 * n + 1] = x[5 * (size_t)j + 4];
+                    ++n;
+                    if (hlead) hlead[nlead] = j;
+                    if (!(qflags[b] & 1)) {                      // a leader is a car for the gap
+                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+                        qflags[b] |= 1;
+                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
+                        q[MPC_CLQ_MIN_OBS_DIST] = g;
+                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+                    }
+                    if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || g < e[MPC_CVX_MIN_LEAD_GAP] || g != g) {
+                        e[MPC_CVX_MIN_LEAD_GAP] = g;
+                        e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
+                    }
+                }
+                nobsa[i] = n;
+                if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
+                if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
+                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+                if (slot[b] >= 0) {
+                    const size_t h = (size_t)slot[b] * ns + step;
+                    if (hist_car_s) hist_car_s[h] = car_s;
+                    if (hist_tl) hist_tl[h] = green;
+                    if (hist_nobs) hist_nobs[h] = n;
+                    if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
+                }
+            }
+            solve_batch(p, nl, xa.data(), with_slab ? obsa.data() : nullptr, with_slab ? nobsa.data() : nullptr,
+                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
+            for (int i = 0; i < nl; ++i) {                   // plant step and plant-side quantities: the sweep's
+                const int b = alist[i];
+                double* xb = x.data() + 5 * (size_t)b;
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                double st[5];
+                ref->state(xb[0], st);
+                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
+                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
+                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
+                if (slot[b] >= 0) {
+                    const size_t h = (size_t)slot[b];
+                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
+                    if (hist_u) {
+                        hist_u[(h * ns + step) * 2] = u1;
+                        hist_u[(h * ns + step) * 2 + 1] = u2;
+                    }
+                    if (hist_status) hist_status[h * ns + step] = sta[i];
+                }
+                nrun[b] = step + 1;
+                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
+                q[MPC_CLQ_S_FINAL] = xb[0];
+                const double ad = std::fabs(xb[1]);
+                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
+                if (step == 0) {
+                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
+                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
+                } else {
+                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
+                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
+                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
+                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
+                }
+                const int code = sta[i] & MPC_STATUS_MASK;
+                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
+                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
+                if (!(xb[0] <= s_stop)) active[b] = 0;
+            }
+            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            if (step_ms) step_ms[step] = ms.back();
+        }
+        sweep_max_step_ms(B, nrun.data(), ms, quant);
+        if (extra) std::memcpy(extra, ex.data(), nb * MPC_CV_NX * sizeof(double));
+        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
+        return MPC_SUCCESS;
+    }
 };
 
 // MPC_CLQ_MAX_STEP_MS of every ego: the prefix max of the step times over the steps it ran, max(ms[:n]) with

@@ -60,7 +60,7 @@ class MpcError(RuntimeError):
 EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_batch_device", "mpc_lookup",
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
-           "mpc_closed_loop_traffic", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -76,6 +76,11 @@ MAX_ACTORS = 16
 TRX_MAX_NOBS, TRX_N_RED_PASS, TRX_MIN_GAP_ACTOR = 0, 1, 2
 TR_NX = 3
 TRX_FIELDS = ("max_nobs", "n_red_pass", "min_gap_actor")
+# mpc_closed_loop_convoy: the world size limit and the columns its `extra` adds to the traffic ones (MPC_CVX_*)
+MAX_WORLD = 256
+CVX_MIN_LEAD_GAP, CVX_MIN_LEAD_EGO, CVX_MAX_LEADERS = 3, 4, 5
+CV_NX = 6
+CVX_FIELDS = TRX_FIELDS + ("min_lead_gap", "min_lead_ego", "max_leaders")
 
 _lib = None
 
@@ -126,6 +131,10 @@ def lib():
     L.mpc_closed_loop_traffic.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(MpcActor), C.c_int, C.c_int, C.c_int,
                                           C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp,
                                           _ip, _dp]
+    L.mpc_closed_loop_convoy.restype = C.c_int
+    L.mpc_closed_loop_convoy.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.POINTER(MpcActor),
+                                         C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp,
+                                         _ip, _ip, _ip, _dp, _ip, _ip, _dp]
     L.mpc_comm_unique_id.restype = C.c_int
     L.mpc_comm_unique_id.argtypes = [C.c_char_p]
     L.mpc_comm_create.restype = C.c_int
@@ -212,6 +221,24 @@ def _pi(a):
 def _check(rc, what):
     if rc != 0:
         raise MpcError(f"{what} failed (rc={rc}): {last_error()}")
+
+
+def _script_array(scripts):
+    """(mpc_actor pointer, A, n_scripts) of closed_loop_traffic's `scripts` argument: None, one sequence of
+    MpcActor (shared), or a sequence of such sequences of one length."""
+    if scripts is None:
+        return None, 0, 0
+    scripts = list(scripts)
+    rows = [scripts] if all(isinstance(a, MpcActor) for a in scripts) else [list(r) for r in scripts]
+    n_scripts = len(rows)
+    A = len(rows[0]) if rows else 0
+    if any(len(r) != A for r in rows):
+        raise ValueError("every script must have the same number of actors (pad with ACTOR_NONE)")
+    buf = (MpcActor * max(n_scripts * A, 1))()
+    for i, r in enumerate(rows):
+        for a, act in enumerate(r):
+            C.memmove(C.byref(buf, (i * A + a) * C.sizeof(MpcActor)), C.byref(act), C.sizeof(MpcActor))
+    return C.cast(buf, C.POINTER(MpcActor)), A, n_scripts
 
 
 class Solver:
@@ -349,20 +376,7 @@ class Solver:
             if s_max is None:
                 raise ValueError("give s_stop or s_max")
             s_stop = s_max - 1.0
-        if scripts is None:
-            arr, A, n_scripts = None, 0, 0
-        else:
-            scripts = list(scripts)
-            rows = [scripts] if all(isinstance(a, MpcActor) for a in scripts) else [list(r) for r in scripts]
-            n_scripts = len(rows)
-            A = len(rows[0]) if rows else 0
-            if any(len(r) != A for r in rows):
-                raise ValueError("every script must have the same number of actors (pad with ACTOR_NONE)")
-            buf = (MpcActor * max(n_scripts * A, 1))()
-            for i, r in enumerate(rows):
-                for a, act in enumerate(r):
-                    C.memmove(C.byref(buf, (i * A + a) * C.sizeof(MpcActor)), C.byref(act), C.sizeof(MpcActor))
-            arr = C.cast(buf, C.POINTER(MpcActor))
+        arr, A, n_scripts = _script_array(scripts)
         he = np.ascontiguousarray(hist_egos, np.int32).ravel()
         nh = he.size
         quant = np.empty((B, CL_NQ)); extra = np.empty((B, TR_NX))
@@ -379,6 +393,43 @@ class Solver:
         quant[:, 0] += lo
         return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
                     hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl)
+
+    def closed_loop_convoy(self, x_init, W, K, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
+                           s_max=None, hist_egos=(), lo=0):
+        """mpc_closed_loop_convoy: closed_loop_traffic in which the egos [w*W, (w+1)*W) of a world see each other.
+        Per step an ego's slab holds its script's entries, then (s, v) of its up to K nearest leaders: the egos of
+        its world that are ahead (larger s, on equal s the lower index) and still in the loop, cut at the first
+        gap >= lead_range.  x_init [B,5], B a multiple of W; scripts as in closed_loop_traffic.
+        Returns closed_loop_traffic's dict with extra [B,6] (columns CVX_FIELDS; min_lead_ego is a batch index,
+        the shard offset `lo` is added to it), hist_slab [n_hist,max_steps,A+K,2] and hist_lead
+        [n_hist,max_steps,K] (the leaders' batch indices of this call in slab order, -1 past them)."""
+        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
+        B = x_init.shape[0]
+        if s_stop is None:
+            if s_max is None:
+                raise ValueError("give s_stop or s_max")
+            s_stop = s_max - 1.0
+        arr, A, n_scripts = _script_array(scripts)
+        K = int(K)
+        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
+        nh = he.size
+        quant = np.empty((B, CL_NQ)); extra = np.empty((B, CV_NX))
+        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
+        hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
+        ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
+        hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, max(A + K, 0), 2))
+        hd = np.empty((nh, max_steps, max(K, 0)), np.int32)
+        g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
+        gi = (lambda a: _pi(a) if nh else None)
+        _check(lib().mpc_closed_loop_convoy(self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A),
+                                            int(n_scripts), int(max_steps), float(s_stop), _p(quant), _p(extra), nh,
+                                            gi(he), g(hx), g(hu), g(hc), gi(ht), gi(hs), gi(hn),
+                                            g(hl) if A + K > 0 else None, gi(hd) if K > 0 else None, _pi(ns),
+                                            _p(sm)), "mpc_closed_loop_convoy")
+        quant[:, 0] += lo
+        extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
+        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
+                    hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl, hist_lead=hd)
 
     def cl_verdicts(self, quant, s_total):
         """mpc_cl_verdicts: the restated acceptance verdicts (sanity_checks.check_verdicts, with this context's

@@ -438,6 +438,40 @@ def run_traffic_sweep(mpc, scripts, trajectory, x_init, max_steps=2000, hist_ego
     return r
 
 
+def convoy_starts(traj, n_worlds, W, headway_m, v, s0=0.0):
+    """Start states [n_worlds * W, 5] of n_worlds identical convoys on the reference line of `traj` (a
+    TrajectoryLoader): in every world ego 0 starts at s0 and ego i `headway_m` metres ahead of ego i - 1 (the
+    last ego leads), on the line (d = o = 0) at speed v, with k taken from the table."""
+    s = s0 + headway_m * np.arange(W)
+    world = np.array([[si, 0.0, 0.0, traj.get_state(si)[3], v] for si in s])
+    return np.tile(world, (n_worlds, 1))
+
+
+def run_convoy_sweep(mpc, trajectory, x_init, W, K, lead_range=np.inf, scripts=None, max_steps=2000, hist_egos=(),
+                     s_stop=None):
+    """run_traffic_sweep with the egos [w*W, (w+1)*W) of a world seeing each other (mpc_closed_loop_convoy): per
+    step an ego's obstacles are its script's, then its up to K nearest leaders within lead_range.  scripts: None,
+    or one TrafficScript / sequence of actors / None per ego.  Returns mpcqp.Solver.closed_loop_convoy's dict plus
+    'verdicts' [B], 'counts' and one boolean column [B] per verdict name, like run_scenario_sweep."""
+    x_init = np.asarray(x_init, np.float64).reshape(-1, 5)
+    rows = None
+    if scripts is not None:
+        scripts = [s if isinstance(s, TrafficScript) else TrafficScript(s or ()) for s in scripts]
+        if len(scripts) != x_init.shape[0]:
+            raise ValueError("one script (or None) per ego")
+        A = max((len(s.actors) for s in scripts), default=0)
+        rows = [s.padded(A) for s in scripts] if A else None
+    slv = mpc.solver(max_obs=0)
+    r = slv.closed_loop_convoy(x_init, W, K, lead_range=lead_range, scripts=rows, max_steps=max_steps, s_stop=s_stop,
+                               s_max=trajectory.s_max, hist_egos=hist_egos)
+    v, counts = slv.cl_verdicts(r["quant"], trajectory.s_max)
+    r["verdicts"] = v
+    r["counts"] = {k: int(counts[i]) for i, k in enumerate(mpcqp.CLV_NAMES)}
+    for i, k in enumerate(mpcqp.CLV_NAMES):
+        r[k] = (v & (1 << i)) != 0
+    return r
+
+
 def closed_loop_checks(mpc, fsm, trajectory, r, verbose=False):
     """The restated trajectory_tracking_check (sanity_checks.py:79-184) on every ego of a closed_loop()
     result (mpcqp.Solver.closed_loop layout); returns the per-ego verdicts [B] (bool)."""

@@ -1,0 +1,155 @@
+// Stand-alone sanitizer check of the host backend's convoy loop (csrc/cpu_backend.h: closed_loop_convoy), built
+// and run by tools/convoy_host_check.py with -fsanitize=address,undefined:
+//   convoy_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
+// Runs on 3 worker threads, N = 5, 12 egos: (1) worlds of one ego with K = 3 and worlds of four with K = 0, each
+// ego with a script of a car and a light, against closed_loop_traffic: every quantity column but the step time,
+// extras 0..2 and n_steps must be equal byte for byte; (2) three worlds of four (a tie pair, an ego that starts
+// past s_stop, a leader that leaves mid-run) with K = 3, K = 14 beside the two actors (A + K = 16), a finite
+// lead_range, two selected egos, no history and no extras, and no script: every leader recorded must belong to
+// the ego's world and the leader counts must stay within K.
+// Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/mpcqp.h"
+#include "../safe-autonomous-driving-mpc_amd/csrc/cpu_backend.h"
+
+static mpc_actor none() {
+    mpc_actor a;
+    std::memset(&a, 0, sizeof(a));
+    return a;
+}
+static mpc_actor car(double trigger_s, double start_s, double v, double end_s) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_CAR; a.trigger_s = trigger_s; a.pos_s = start_s; a.v = v; a.end_s = end_s;
+    return a;
+}
+static mpc_actor light(double pos_s, double trigger_s, double stop_duration) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_LIGHT; a.trigger_s = trigger_s; a.pos_s = pos_s; a.stop_duration = stop_duration;
+    return a;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[2];
+    if (std::fread(hdr, sizeof(int), 2, f) != 2) return 2;
+    const int T = hdr[0], Tu = hdr[1];
+    std::vector<double> X(5 * (size_t)T), U(2 * (size_t)Tu);
+    if (std::fread(X.data(), 8, X.size(), f) != X.size() || std::fread(U.data(), 8, U.size(), f) != U.size()) return 2;
+    std::fclose(f);
+    mpcqp_host::HostTable table;
+    if (!mpcqp_host::build_host_table(X.data(), T, U.data(), Tu, table)) return 2;
+    mpcqp_cpu::Backend be(std::move(table));
+    be.threads = 3;
+    mpc_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.N = 5; p.max_obs = 0; p.dt = 0.2;
+    p.u_min[0] = -0.6; p.u_min[1] = -5.0; p.u_max[0] = 0.6; p.u_max[1] = 4.0;
+    p.vehicle_radius = 1.0; p.w_d = 10.0; p.w_o = 10.0; p.w_v = 5.0; p.w_u1 = 0.5; p.w_u2 = 0.5;
+    p.obstacle_safety_distance = 5.0; p.max_time_2_obs = 1.5; p.wheelbase = 2.8; p.lane_width = 3.0;
+    p.safe_lane_margin = 0.1; p.brake_distance = 40.0; p.brake_accel = -2.0; p.linearization = 1;
+    p.sqp_iters = 1; p.max_iter = 80; p.tol = 1e-9; p.tol_mu = 1e-10; p.elastic_rho = 1e5; p.polish = 2;
+    p.sqp_tol = 1e-10;
+
+    const int B = 12, W = 4, ms = 120;
+    const size_t ns = ms;
+    const double s0 = 440.0, s_stop = 500.0, far = 1.0e6;
+    // world 0: a platoon with a tie pair; world 1: the front ego leaves within a few steps; world 2: one spare ego
+    const double start[B] = {s0, s0 + 8.0, s0 + 8.0, s0 + 20.0, s0 + 30.0, s0 + 38.0, s0 + 45.0, s_stop - 3.0,
+                             s0 + 5.0, s0, s_stop + 2.0, s0 + 12.0};
+    std::vector<double> x0(5 * (size_t)B, 0.0);
+    for (int b = 0; b < B; ++b) {
+        double st[5];
+        be.ref->state(start[b], st);
+        x0[5 * b] = start[b]; x0[5 * b + 1] = 0.01 * (b % 3); x0[5 * b + 3] = st[3]; x0[5 * b + 4] = 6.0 + 0.5 * (b % 4);
+    }
+    const int A = 2;
+    std::vector<mpc_actor> scripts;
+    for (int b = 0; b < B; ++b) {
+        scripts.push_back(car(s0 + 5.0 + b, s0 + 40.0 + 3.0 * b, 4.0, b % 2 ? far : s0 + 70.0));
+        scripts.push_back(light(s0 + 50.0, 100.0, 0.6 + 0.2 * (b % 3)));
+    }
+    int bad = 0;
+    auto convoy = [&](int Wc, int K, double range, const std::vector<mpc_actor>& sc, int Ac, int n_scripts,
+                      const std::vector<int>& egos, bool extras, std::vector<double>& quant,
+                      std::vector<double>& extra, std::vector<int>& n_steps) {
+        const int nh = (int)egos.size(), AK = Ac + K;
+        std::vector<int> slot(B, -1);
+        for (int k = 0; k < nh; ++k) slot[egos[k]] = k;
+        quant.assign((size_t)B * MPC_CL_NQ, -1.0);
+        extra.assign((size_t)B * MPC_CV_NX, -7.0);
+        n_steps.assign(B, -1);
+        std::vector<double> hx((size_t)nh * (ns + 1) * 5), hu((size_t)nh * ns * 2), hc((size_t)nh * ns),
+            hl((size_t)nh * ns * AK * 2), step_ms(ns);
+        std::vector<int> ht((size_t)nh * ns), hs((size_t)nh * ns), hn((size_t)nh * ns), hd((size_t)nh * ns * K);
+        bool with_slab = K > 0 && Wc > 1;
+        for (const mpc_actor& a : sc) with_slab = with_slab || a.kind != MPC_ACTOR_NONE;
+        const int rc = be.closed_loop_convoy(
+            p, B, Wc, K, range, x0.data(), sc.empty() ? nullptr : sc.data(), Ac, n_scripts, with_slab, ms, s_stop,
+            quant.data(), extras ? extra.data() : nullptr, nh, slot.data(), nh ? hx.data() : nullptr,
+            nh ? hu.data() : nullptr, nh ? hc.data() : nullptr, nh ? ht.data() : nullptr, nh ? hs.data() : nullptr,
+            nh ? hn.data() : nullptr, nh && AK ? hl.data() : nullptr, nh && K ? hd.data() : nullptr,
+            extras ? n_steps.data() : nullptr, extras ? step_ms.data() : nullptr);
+        if (rc != MPC_SUCCESS) ++bad;
+        for (int k = 0; k < nh; ++k)                       // recorded leaders: this ego's world, counts within K
+            for (size_t t = 0; t < ns; ++t) {
+                int n = 0;
+                for (int m = 0; m < K; ++m) {
+                    const int j = hd[((size_t)k * ns + t) * K + m];
+                    if (j < 0) continue;
+                    ++n;
+                    if (j / Wc != egos[k] / Wc || j == egos[k]) ++bad;
+                }
+                if (n > K || (n > 0 && hn[(size_t)k * ns + t] < n)) ++bad;
+            }
+        if (extras)
+            for (int b = 0; b < B; ++b) {
+                const double e = extra[(size_t)b * MPC_CV_NX + MPC_CVX_MIN_LEAD_EGO];
+                if (e >= 0.0 && ((int)e / Wc != b / Wc)) ++bad;
+                if (extra[(size_t)b * MPC_CV_NX + MPC_CVX_MAX_LEADERS] > (double)K) ++bad;
+            }
+    };
+    std::vector<int> all(B), two = {9, 2}, nobody;
+    for (int b = 0; b < B; ++b) all[b] = b;
+
+    // (1) the anchor: the traffic loop on the same inputs
+    std::vector<double> tq((size_t)B * MPC_CL_NQ), tx((size_t)B * MPC_TR_NX), step_ms(ns);
+    std::vector<int> tn(B), slot(B, -1);
+    if (be.closed_loop_traffic(p, B, x0.data(), scripts.data(), A, B, true, ms, s_stop, tq.data(), tx.data(), 0,
+                               slot.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tn.data(),
+                               step_ms.data()) != MPC_SUCCESS)
+        ++bad;
+    std::vector<double> q, ex;
+    std::vector<int> n;
+    const int anchors[2][2] = {{1, 3}, {4, 0}};
+    for (const auto& wk : anchors) {
+        convoy(wk[0], wk[1], INFINITY, scripts, A, B, all, true, q, ex, n);
+        for (int b = 0; b < B; ++b) {
+            for (int k = 0; k < MPC_CL_NQ; ++k)
+                if (k != MPC_CLQ_MAX_STEP_MS &&
+                    std::memcmp(&q[(size_t)b * MPC_CL_NQ + k], &tq[(size_t)b * MPC_CL_NQ + k], 8) != 0)
+                    ++bad;
+            if (std::memcmp(&ex[(size_t)b * MPC_CV_NX], &tx[(size_t)b * MPC_TR_NX], MPC_TR_NX * 8) != 0) ++bad;
+            if (n[b] != tn[b]) ++bad;
+            if (ex[(size_t)b * MPC_CV_NX + MPC_CVX_MIN_LEAD_EGO] != -1.0) ++bad;
+        }
+    }
+    // (2) the convoy paths
+    convoy(W, 3, INFINITY, scripts, A, B, all, true, q, ex, n);
+    double most = 0.0;
+    for (int b = 0; b < B; ++b) most = std::fmax(most, ex[(size_t)b * MPC_CV_NX + MPC_CVX_MAX_LEADERS]);
+    if (most != 3.0 || n[10] != 0 || n[7] >= n[6]) ++bad;
+    convoy(W, 14, INFINITY, scripts, A, B, all, true, q, ex, n);
+    convoy(W, 3, 9.0, scripts, A, B, two, true, q, ex, n);
+    convoy(W, 2, INFINITY, scripts, A, B, nobody, false, q, ex, n);
+    convoy(W, 3, INFINITY, {scripts[0], scripts[1]}, A, 1, two, true, q, ex, n);
+    convoy(W, 3, 25.0, {}, 0, 1, all, true, q, ex, n);
+    convoy(B, 11, INFINITY, {}, 0, 1, all, true, q, ex, n);
+    std::printf("convoy_host_check: %s\n", bad ? "MISMATCH" : "clean and equal");
+    return bad ? 1 : 0;
+}
