@@ -349,6 +349,75 @@ int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double lead_range, c
                            double* hist_u, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
                            double* hist_slab, int* hist_lead, int* n_steps, double* step_ms);
 
+/* Closed-loop disturbance sweeps: mpc_closed_loop_convoy with seeded, reproducible noise between the world and
+ * the solver.  The world keeps the truth: the actors' state machines, the leader ranking, the exit test, every
+ * MPC_CLQ_* quantity, the slab of hist_slab and the gap quantities use the true states exactly as in the convoy
+ * entry.  Only the state and the slab copy handed to the solver are perturbed, and the control the plant
+ * integrates.
+ *
+ * Noise source: counter-based Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl key increments 0x9E3779B9,
+ * 0xBB67AE85), no generator state.  One draw:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (g & 0xffffffff, g >> 32, (unsigned)step, channel), g = ego_offset + b as a 64-bit integer
+ *   words   w0..w3 of that one block; S = w0 + w1 + w2 + w3 (exact, < 2^34)
+ *   z       = ((double)S - 8589934590.0) * c, c = 1.7320508075688772 * 2^-32: mean 0, variance 1,
+ *             |z| <= 2 sqrt(3) (Irwin-Hall of four uniforms); the multiply is the only rounding
+ * so an ego's noise depends on (seed, global ego index, step, channel) only: not on B, on the compaction of the
+ * solver's list, on the backend or on the shard.  Channels: j = 0..4 measurement noise of state component j;
+ * 5, 6 actuation noise of u1, u2; 7 + j process noise of state component j; 16 + 2j, 17 + 2j perception noise
+ * of (s, v) of slab entry j < MPC_MAX_ACTORS.  A channel whose sigma is 0 draws nothing and leaves its value
+ * untouched (no + 0 * z, no clamp).
+ *
+ * Per step, for an ego still in the loop, with x the true state before the step and (u1, u2) the solver's
+ * first control:
+ *   measure  the solver receives xm[j] = x[j] + meas_sigma[j] * z(j), and of slab entry j the pair
+ *            (s + perc_sigma[0] * z(16 + 2j), v + perc_sigma[1] * z(17 + 2j)); zeros past n_obs as before
+ *   actuate  ua[k] = clamp(u[k] + act_sigma[k] * z(5 + k), u_min[k], u_max[k]) with the context's bounds
+ *            (t < u_min ? u_min : t > u_max ? u_max : t: a NaN stays)
+ *   plant    x_next[j] = (x[j] + dt * xd[j]) + (dt * proc_sigma[j]) * z(7 + j), xd the convoy's with (ua1, ua2)
+ *            for (u1, u2) and k_ref looked up at the true s
+ * MPC_CLQ_U* and hist_u stay the commanded controls: the controls verdict judges the solver, not the actuator.
+ *   noise, n_noise   n_noise == B: noise[b] is ego b's; n_noise == 1: one struct shared by all; noise NULL with
+ *                n_noise == 0: no noise (every sigma 0)
+ *   seed, ego_offset   ego_offset >= 0 is the global index of ego 0 (a shard's offset)
+ *   extra        [B][MPC_NZ_NX], optional: columns 0..5 the convoy's, then the MPC_NZX_* columns
+ *   hist_ua      [n_hist][max_steps][2] applied controls; hist_xm [n_hist][max_steps][5] the state the solver was
+ *                given; NaN past n_steps.  Every other argument is mpc_closed_loop_convoy's.
+ * With every sigma 0 every output the convoy entry has equals mpc_closed_loop_convoy's bit for bit, hist_ua equals
+ * hist_u, hist_xm the states before the steps, the applied extremes the commanded ones and N_CLAMPED is 0.
+ * Misuse: the convoy entry's cases, a sigma that is negative or NaN, n_noise not in {0 with NULL, 1, B},
+ * ego_offset < 0, hist_ua or hist_xm with n_hist == 0: MPC_E_ARG.
+ * Device memory is O(B * (A + K)) + O(n_hist * max_steps * (A + K)). */
+typedef struct mpc_noise {
+    double meas_sigma[5];   /* the solver sees x + sigma*z per component (s, d, o, k, v)         */
+    double act_sigma[2];    /* the plant applies clamp(u0 + sigma*z, u_min, u_max) per component */
+    double proc_sigma[5];   /* x_next[j] = (x[j] + dt*xd[j]) + (dt*sigma[j])*z                   */
+    double perc_sigma[2];   /* every slab entry handed to the solver: (s + sigma0*z, v + sigma1*z') */
+} mpc_noise;
+void mpc_default_noise(mpc_noise* n);           /* all zero */
+#define MPC_NZ_CH_MEAS 0          /* + j, j < 5                                                              */
+#define MPC_NZ_CH_ACT 5           /* + k, k < 2                                                              */
+#define MPC_NZ_CH_PROC 7          /* + j, j < 5                                                              */
+#define MPC_NZ_CH_PERC 16         /* + 2 * entry (s), + 2 * entry + 1 (v)                                    */
+#define MPC_NZ_CHANNELS 48
+#define MPC_NZX_U1A_MIN 6         /* extremes of the applied controls, the sweep's NaN rule                  */
+#define MPC_NZX_U1A_MAX 7
+#define MPC_NZX_U2A_MIN 8
+#define MPC_NZX_U2A_MAX 9
+#define MPC_NZX_N_CLAMPED 10      /* steps at which the clamp changed a component                            */
+#define MPC_NZ_NX 11
+int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                          const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
+                          unsigned long long seed, long long ego_offset, int max_steps, double s_stop, double* quant,
+                          double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u,
+                          double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                          int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms);
+/* The draws themselves, on the context's backend: words [n][4] (may be NULL) and z [n] (may be NULL) of
+ * (seed, ego[i], step[i], channel[i]).  The public way to regenerate or audit the noise of a run offline.
+ * n < 0, a NULL index array with n > 0, ego[i] < 0, or a channel outside 0 .. MPC_NZ_CHANNELS - 1: MPC_E_ARG. */
+int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const long long* ego, const int* step,
+                   const int* channel, unsigned* words, double* z);
+
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no
  * per-step exchange.  The one collective returns what the reference's run_simulation returns

@@ -934,6 +934,47 @@ private:
 // ---------------------------------------------------------------------------------------------
 inline void sweep_max_step_ms(int B, const int* n_steps, const std::vector<double>& ms, double* quant);
 
+// The noise source of mpc_closed_loop_noisy (include/mpcqp.h): Philox4x32-10 and the four-word variate, the
+// arithmetic of noise_kernels.h's nz_philox / nz_variate (the high halves from 64-bit products)
+inline void noise_words(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0;
+        c1 = (unsigned)p1;
+        c2 = n2;
+        c3 = (unsigned)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+inline double noise_variate(const unsigned w[4]) {
+    const unsigned long long s = (unsigned long long)w[0] + w[1] + w[2] + w[3];
+    return ((double)s - 8589934590.0) * (1.7320508075688772 * 0x1p-32);
+}
+
+inline double noise_z(unsigned long long seed, unsigned long long g, int step, int channel) {
+    unsigned w[4];
+    noise_words((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)channel, (unsigned)seed,
+                (unsigned)(seed >> 32), w);
+    return noise_variate(w);
+}
+
+// mpc_noise_draw on the host; words and z may be null
+inline void noise_draw(unsigned long long seed, int n, const long long* ego, const int* step, const int* channel,
+                       unsigned* words, double* z) {
+    for (int i = 0; i < n; ++i) {
+        const unsigned long long g = (unsigned long long)ego[i];
+        unsigned w[4];
+        noise_words((unsigned)g, (unsigned)(g >> 32), (unsigned)step[i], (unsigned)channel[i], (unsigned)seed,
+                    (unsigned)(seed >> 32), w);
+        if (words) std::memcpy(words + 4 * (size_t)i, w, sizeof(w));
+        if (z) z[i] = noise_variate(w);
+    }
+}
+
 struct Backend {
     HostTable table;
     std::unique_ptr<Ref> ref;
@@ -1647,6 +1688,270 @@ struct Backend {
         }
         sweep_max_step_ms(B, nrun.data(), ms, quant);
         if (extra) std::memcpy(extra, ex.data(), nb * MPC_CV_NX * sizeof(double));
+        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
+        return MPC_SUCCESS;
+    }
+
+    // mpc_closed_loop_noisy on the host: closed_loop_convoy above with seeded noise between the world and the
+    // solver (include/mpcqp.h).  The FSMs, the leader ranking, the gap quantities, hist_slab and the exit test use
+    // the true states; the solver receives x + meas_sigma * z and a perturbed copy of the slab; the plant
+    // integrates the clamped u + act_sigma * z and adds (dt * proc_sigma) * z.  noise is [n_noise], n_noise 1
+    // (shared) or B; extra is [B][MPC_NZ_NX]; ego b draws as global ego ego_offset + b
+    int closed_loop_noisy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
+                          const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
+                          int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
+                          double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
+                          double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                          int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
+        mpc_params p = p0;
+        const int AK = A + K;
+        p.max_obs = with_slab ? AK : 0;
+        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
+        const size_t nak = (size_t)AK;
+        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
+        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
+        if (hist_ua) std::fill(hist_ua, hist_ua + nh * ns * 2, NAN);
+        if (hist_xm) std::fill(hist_xm, hist_xm + nh * ns * 5, NAN);
+        if (hist_car_s) std::fill(hist_car_s, hist_car_s + nh * ns, NAN);
+        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
+        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
+        if (hist_nobs) std::fill(hist_nobs, hist_nobs + nh * ns, -1);
+        if (hist_slab) std::fill(hist_slab, hist_slab + nh * ns * nak * 2, NAN);
+        if (hist_lead) std::fill(hist_lead, hist_lead + nh * ns * nk, -1);
+        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
+        enum { CAR_ACTIVE = 1, CAR_TRIGGERED = 2, TL_GREEN = 4, TL_WAITING = 8, PASS_DECIDED = 16 };
+        std::vector<double> x(x_init, x_init + nb * 5), aval(nb * na, 0.0), ex(nb * MPC_NZ_NX, 0.0), ms;
+        std::vector<int> aflags(nb * na, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
+        std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
+        std::vector<double> xa, obsa, u0a;
+        std::vector<int> nobsa, sta;
+        for (int b = 0; b < B; ++b) {
+            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+            for (int a = 0; a < A; ++a)
+                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
+            active[b] = x[5 * (size_t)b] <= s_stop;
+            if (hist_x && slot[b] >= 0)
+                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+            double* q = quant + (size_t)b * MPC_CL_NQ;
+            std::fill(q, q + MPC_CL_NQ, 0.0);
+            q[MPC_CLQ_EGO] = (double)b;
+            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
+            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
+            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
+            double* e = ex.data() + (size_t)b * MPC_NZ_NX;
+            e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+            e[MPC_CVX_MIN_LEAD_GAP] = NAN;
+            e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
+        }
+        for (int step = 0; step < max_steps; ++step) {
+            const auto t0 = std::chrono::steady_clock::now();
+            alist.clear();
+            for (int b = 0; b < B; ++b)
+                if (active[b]) alist.push_back(b);
+            if (alist.empty()) break;
+            const int nl = (int)alist.size();
+            order = alist;                                   // the ranking of closed_loop_convoy, on the true s
+            for (int i = 0, w = 0; w <= B / W; ++w) {
+                while (i < nl && alist[i] < w * W) ++i;
+                wbeg[w] = i;
+            }
+            for (int w = 0; w < B / W; ++w)
+                std::sort(order.begin() + wbeg[w], order.begin() + wbeg[w + 1], [&](int a, int b) {
+                    const double sa = x[5 * (size_t)a], sb = x[5 * (size_t)b];
+                    return sa > sb || (sa == sb && a < b);
+                });
+            for (int i = 0; i < nl; ++i) rank[order[i]] = i;
+            xa.assign((size_t)nl * 5, 0.0);
+            obsa.assign((size_t)nl * nak * 2, 0.0);
+            nobsa.assign(nl, 0);
+            u0a.assign((size_t)nl * 2, 0.0);
+            sta.assign(nl, 0);
+            for (int i = 0; i < nl; ++i) {
+                const int b = alist[i];
+                const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+                const mpc_noise& Z = noise[n_noise == 1 ? 0 : b];
+                const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
+                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
+                double o[2 * MPC_MAX_ACTORS];                // the true slab of this step
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                double* e = ex.data() + (size_t)b * MPC_NZ_NX;
+                int n = 0, green = 0, have_car = 0;
+                double car_s = NAN;
+                for (int a = 0; a < A; ++a) {
+                    const mpc_actor& M = sc[a];
+                    if (M.kind == MPC_ACTOR_NONE) continue;
+                    int& fl = aflags[(size_t)b * na + a];
+                    double& val = aval[(size_t)b * na + a];
+                    if (M.kind == MPC_ACTOR_CAR) {
+                        if (!(fl & CAR_TRIGGERED) && s >= M.trigger_s) fl |= CAR_TRIGGERED | CAR_ACTIVE;
+                        if (fl & CAR_ACTIVE) {
+                            val = val + M.v * p.dt;
+                            if (val > M.end_s) {
+                                fl &= ~CAR_ACTIVE;
+                            } else {
+                                o[2 * n] = val;
+                                o[2 * n + 1] = M.v;
+                                ++n;
+                                if (!have_car) { have_car = 1; car_s = val; }
+                                if (val == val) {
+                                    const double gap = val - s;
+                                    if (!(qflags[b] & 1)) {
+                                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
+                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
+                                        qflags[b] |= 1;
+                                    } else if (gap < q[MPC_CLQ_MIN_OBS_DIST] || gap != gap) {
+                                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
+                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
+                                    }
+                                }
+                            }
+                        }
+                    } else {
+                        if (!(fl & TL_GREEN)) {
+                            const double dist = M.pos_s - s;
+                            if (0.0 < dist && dist < M.trigger_s) {
+                                o[2 * n] = M.pos_s;
+                                o[2 * n + 1] = 0.0;
+                                ++n;
+                                if (v < 0.1 && dist < 10.0) fl |= TL_WAITING;
+                            }
+                            if (fl & TL_WAITING) {
+                                val += p.dt;
+                                if (val >= M.stop_duration) fl = (fl | TL_GREEN) & ~TL_WAITING;
+                            }
+                        }
+                        if (fl & TL_GREEN) green |= 1 << a;
+                        if (!(fl & PASS_DECIDED) && s > M.pos_s) {
+                            fl |= PASS_DECIDED;
+                            if (!(fl & TL_GREEN)) {
+                                q[MPC_CLQ_RED_PASS] = 1.0;
+                                e[MPC_TRX_N_RED_PASS] += 1.0;
+                            }
+                        }
+                    }
+                }
+                int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
+                const int r = rank[b], r0 = wbeg[b / W];
+                int nlead = 0;
+                for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {
+                    const int j = order[r - 1 - nlead];
+                    const double sj = x[5 * (size_t)j], gap = sj - s;
+                    if (gap >= lead_range) break;
+                    o[2 * n] = sj;
+                    o[2 * n + 1] = x[5 * (size_t)j + 4];
+                    ++n;
+                    if (hlead) hlead[nlead] = j;
+                    if (!(qflags[b] & 1)) {
+                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
+                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+                        qflags[b] |= 1;
+                    } else if (gap < q[MPC_CLQ_MIN_OBS_DIST] || gap != gap) {
+                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
+                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+                    }
+                    if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || gap < e[MPC_CVX_MIN_LEAD_GAP] || gap != gap) {
+                        e[MPC_CVX_MIN_LEAD_GAP] = gap;
+                        e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
+                    }
+                }
+                nobsa[i] = n;
+                if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
+                if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
+                // what the solver receives: the measured state and the perceived slab
+                double* xm = xa.data() + 5 * (size_t)i;
+                for (int j = 0; j < 5; ++j) {
+                    xm[j] = x[5 * (size_t)b + j];
+                    if (Z.meas_sigma[j] != 0.0)
+                        xm[j] = xm[j] + Z.meas_sigma[j] * noise_z(seed, g, step, MPC_NZ_CH_MEAS + j);
+                }
+                double* oa = obsa.data() + (size_t)i * nak * 2;
+                for (int j = 0; j < n; ++j) {
+                    oa[2 * j] = o[2 * j];
+                    oa[2 * j + 1] = o[2 * j + 1];
+                    if (Z.perc_sigma[0] != 0.0)
+                        oa[2 * j] = oa[2 * j] + Z.perc_sigma[0] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j);
+                    if (Z.perc_sigma[1] != 0.0)
+                        oa[2 * j + 1] = oa[2 * j + 1] + Z.perc_sigma[1] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j + 1);
+                }
+                if (slot[b] >= 0) {
+                    const size_t h = (size_t)slot[b] * ns + step;
+                    if (hist_car_s) hist_car_s[h] = car_s;
+                    if (hist_tl) hist_tl[h] = green;
+                    if (hist_nobs) hist_nobs[h] = n;
+                    if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
+                    if (hist_xm) std::memcpy(hist_xm + h * 5, xm, 5 * sizeof(double));
+                }
+            }
+            solve_batch(p, nl, xa.data(), with_slab ? obsa.data() : nullptr, with_slab ? nobsa.data() : nullptr,
+                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
+            for (int i = 0; i < nl; ++i) {                   // the convoy's plant step with the applied control
+                const int b = alist[i];
+                const mpc_noise& Z = noise[n_noise == 1 ? 0 : b];
+                const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
+                double* xb = x.data() + 5 * (size_t)b;
+                double* q = quant + (size_t)b * MPC_CL_NQ;
+                double* e = ex.data() + (size_t)b * MPC_NZ_NX;
+                double st[5];
+                ref->state(xb[0], st);
+                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
+                double ua[2] = {u1, u2};
+                bool clamped = false;
+                for (int k = 0; k < 2; ++k)
+                    if (Z.act_sigma[k] != 0.0) {
+                        const double t = ua[k] + Z.act_sigma[k] * noise_z(seed, g, step, MPC_NZ_CH_ACT + k);
+                        ua[k] = t < p.u_min[k] ? p.u_min[k] : (t > p.u_max[k] ? p.u_max[k] : t);
+                        clamped = clamped || t < p.u_min[k] || t > p.u_max[k];
+                    }
+                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), ua[0], ua[1]};
+                for (int j = 0; j < 5; ++j) {
+                    xb[j] = xb[j] + p.dt * xd[j];
+                    if (Z.proc_sigma[j] != 0.0)
+                        xb[j] = xb[j] + (p.dt * Z.proc_sigma[j]) * noise_z(seed, g, step, MPC_NZ_CH_PROC + j);
+                }
+                if (slot[b] >= 0) {
+                    const size_t h = (size_t)slot[b];
+                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
+                    if (hist_u) {
+                        hist_u[(h * ns + step) * 2] = u1;
+                        hist_u[(h * ns + step) * 2 + 1] = u2;
+                    }
+                    if (hist_ua) {
+                        hist_ua[(h * ns + step) * 2] = ua[0];
+                        hist_ua[(h * ns + step) * 2 + 1] = ua[1];
+                    }
+                    if (hist_status) hist_status[h * ns + step] = sta[i];
+                }
+                nrun[b] = step + 1;
+                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
+                q[MPC_CLQ_S_FINAL] = xb[0];
+                const double ad = std::fabs(xb[1]);
+                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
+                if (step == 0) {
+                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
+                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
+                    e[MPC_NZX_U1A_MIN] = e[MPC_NZX_U1A_MAX] = ua[0];
+                    e[MPC_NZX_U2A_MIN] = e[MPC_NZX_U2A_MAX] = ua[1];
+                } else {
+                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
+                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
+                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
+                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
+                    if (ua[0] < e[MPC_NZX_U1A_MIN] || ua[0] != ua[0]) e[MPC_NZX_U1A_MIN] = ua[0];
+                    if (ua[0] > e[MPC_NZX_U1A_MAX] || ua[0] != ua[0]) e[MPC_NZX_U1A_MAX] = ua[0];
+                    if (ua[1] < e[MPC_NZX_U2A_MIN] || ua[1] != ua[1]) e[MPC_NZX_U2A_MIN] = ua[1];
+                    if (ua[1] > e[MPC_NZX_U2A_MAX] || ua[1] != ua[1]) e[MPC_NZX_U2A_MAX] = ua[1];
+                }
+                if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
+                const int code = sta[i] & MPC_STATUS_MASK;
+                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
+                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
+                if (!(xb[0] <= s_stop)) active[b] = 0;
+            }
+            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            if (step_ms) step_ms[step] = ms.back();
+        }
+        sweep_max_step_ms(B, nrun.data(), ms, quant);
+        if (extra) std::memcpy(extra, ex.data(), nb * MPC_NZ_NX * sizeof(double));
         if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
         return MPC_SUCCESS;
     }

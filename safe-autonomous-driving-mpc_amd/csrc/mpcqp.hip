@@ -23,6 +23,8 @@
 //   closed_loop_kernels.h  closed-loop FSM / plant / compaction kernels, pose kernel
 //   sweep_kernels.h        the scenario sweep's FSM / plant kernels (a scenario per ego, check quantities)
 //   traffic_kernels.h      the traffic scripts' FSM / gather kernels (up to 16 actors per ego)
+//   convoy_kernels.h       the convoys' leader-ranking kernel (a workgroup per world)
+//   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points) and, last, the comm layer (comm.h).
 #include <hip/hip_runtime.h>
@@ -45,6 +47,7 @@
 #include "sweep_kernels.h"
 #include "traffic_kernels.h"
 #include "convoy_kernels.h"
+#include "noise_kernels.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -1455,6 +1458,362 @@ extern "C" int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double le
     }
     cleanup();
     return rc;
+}
+
+extern "C" void mpc_default_noise(mpc_noise* n) { std::memset(n, 0, sizeof(*n)); }
+
+// mpc_closed_loop_convoy with seeded noise between the world and the solver (include/mpcqp.h): the same loop with
+// nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel; tr_fsm_kernel, cv_lead_kernel,
+// cl_compact_kernel and launch_solve are reused untouched and see the true states.  noise == NULL runs the same
+// kernels on an all-zero shared struct.  Device allocations: the convoy entry's, extras MPC_NZ_NX wide, the
+// field-major sigma table [14][B] for per-ego noise, hist_ua and hist_xm:
+// O(B * (A + K)) + O(n_hist * max_steps * (A + K))
+extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                                     const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise,
+                                     int n_noise, unsigned long long seed, long long ego_offset, int max_steps,
+                                     double s_stop, double* quant, double* extra, int n_hist, const int* hist_egos,
+                                     double* hist_x, double* hist_u, double* hist_ua, double* hist_xm,
+                                     double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                                     double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
+    if (W < 1 || W > MPC_MAX_WORLD) return fail(MPC_E_ARG, "W out of range [1, 256]");
+    if (B % W != 0) return fail(MPC_E_ARG, "B is not a multiple of W");
+    if (A < 0 || A > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A out of range [0, 16]");
+    if (K < 0 || K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "K out of range [0, 16]");
+    if (A + K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A + K > 16");
+    if (!(lead_range > 0.0)) return fail(MPC_E_ARG, "lead_range must be > 0 (+inf allowed)");
+    if (actors ? !(n_scripts == 1 || n_scripts == B) : n_scripts != 0)
+        return fail(MPC_E_ARG, "n_scripts must be B (a script per ego), 1 (shared) or 0 with actors NULL");
+    if (!actors && A != 0) return fail(MPC_E_ARG, "actors is NULL but A > 0");
+    if (noise ? !(n_noise == 1 || n_noise == B) : n_noise != 0)
+        return fail(MPC_E_ARG, "n_noise must be B (a struct per ego), 1 (shared) or 0 with noise NULL");
+    if (ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
+    if (!quant) return fail(MPC_E_ARG, "quant is required");
+    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
+    if (n_hist == 0 && (hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status || hist_nobs ||
+                        hist_slab || hist_lead))
+        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
+    if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
+    if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
+    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
+    bool with_slab = K > 0 && W > 1;
+    for (size_t k = 0; k < (size_t)n_scripts * (size_t)A; ++k) {
+        if (actors[k].kind < MPC_ACTOR_NONE || actors[k].kind > MPC_ACTOR_LIGHT)
+            return fail(MPC_E_ARG, "actor kind outside MPC_ACTOR_NONE .. MPC_ACTOR_LIGHT");
+        with_slab = with_slab || actors[k].kind != MPC_ACTOR_NONE;
+    }
+    for (size_t k = 0; k < (size_t)n_noise * NZ_NSIG; ++k)       // mpc_noise is NZ_NSIG doubles, no padding
+        if (!(reinterpret_cast<const double*>(noise)[k] >= 0.0))
+            return fail(MPC_E_ARG, "a noise sigma is negative or NaN");
+    std::vector<int> slot;
+    try {
+        slot.assign((size_t)B, -1);
+    } catch (const std::bad_alloc&) {
+        return fail(MPC_E_ALLOC, "history slot map");
+    }
+    for (int k = 0; k < n_hist; ++k) {
+        const int e = hist_egos[k];
+        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
+        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
+        slot[e] = k;
+    }
+    if (B == 0) return MPC_SUCCESS;
+    if (!x_init) return fail(MPC_E_ARG, "x_init is required");
+    int rc = check_params(&c->p);
+    if (rc) return rc;
+    const bool per_ego = n_scripts == B && B > 1;    // n_scripts == B == 1 is the shared case
+    const int nsc = per_ego ? B : (actors ? 1 : 0);
+    const bool nz_per_ego = n_noise == B && B > 1;
+    mpc_noise zero;
+    mpc_default_noise(&zero);
+    if (!noise) noise = &zero;
+    const int AK = A + K;
+    if (c->cpu) {
+        int hrc = MPC_SUCCESS;
+        const int erc = host_call([&] {
+            hrc = c->cpu->closed_loop_noisy(c->p, B, W, K, lead_range, x_init, actors, A, nsc == 0 ? 1 : nsc, with_slab,
+                                            noise, nz_per_ego ? B : 1, seed, ego_offset, max_steps, s_stop, quant,
+                                            extra, n_hist, slot.data(), hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
+                                            hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms);
+        });
+        return erc != MPC_SUCCESS ? erc : hrc;
+    }
+    KParams kp = kparams(&c->p);
+    kp.max_obs = with_slab ? AK : 0;         // every actor and every leader adds at most one entry
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
+    const size_t nak = (size_t)AK;
+    const size_t na1 = na ? na : 1, nak1 = nak ? nak : 1;    // no zero-sized allocation
+    std::vector<double> hsig;                // per-ego sigmas, field-major: the loads of a wave coalesce
+    if (nz_per_ego) {
+        try {
+            hsig.resize(nb * NZ_NSIG);
+        } catch (const std::bad_alloc&) {
+            return fail(MPC_E_ALLOC, "noise table");
+        }
+        for (size_t b = 0; b < nb; ++b)
+            for (size_t f = 0; f < NZ_NSIG; ++f) hsig[f * nb + b] = reinterpret_cast<const double*>(noise + b)[f];
+    }
+    std::vector<void*> bufs;
+    auto dalloc = [&](size_t bytes) -> void* {
+        void* ptr = nullptr;
+        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
+        bufs.push_back(ptr);
+        return ptr;
+    };
+    auto release = [&]() { for (void* q : bufs) hipFree(q); };
+    ClState C = {};                          // obs, obs_s, tl_timer, fsm_flags stay null: TrState holds them
+    C.x = (double*)dalloc(nb * 5 * 8);
+    C.nobs = (int*)dalloc(nb * 4);
+    C.active = (int*)dalloc(nb * 4);
+    C.n_active = (int*)dalloc(4);
+    C.alist = (int*)dalloc(nb * 4);
+    C.n_list = (int*)dalloc(4);
+    C.xa = (double*)dalloc(nb * 5 * 8);
+    C.obsa = (double*)dalloc(nb * nak1 * 2 * 8);
+    C.nobsa = (int*)dalloc(nb * 4);
+    C.u0a = (double*)dalloc(nb * 2 * 8);
+    C.sta = (int*)dalloc(nb * 4);
+    double* d_xinit = (double*)dalloc(nb * 5 * 8);
+    SwState S = {};
+    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
+    S.qflags = (int*)dalloc(nb * 4);
+    int* d_hslot = (int*)dalloc(nb * 4);
+    S.hslot = d_hslot;
+    S.n_steps = (int*)dalloc(nb * 4);
+    TrState T = {};
+    mpc_actor* d_actors = (mpc_actor*)dalloc((per_ego ? nb : 1) * na1 * sizeof(mpc_actor));
+    T.actors = d_actors;
+    T.per_ego = per_ego ? 1 : 0;
+    T.aval = (double*)dalloc(nb * na1 * 8);
+    T.aflags = (int*)dalloc(nb * na1 * 4);
+    T.slab = (double*)dalloc(nb * nak1 * 2 * 8);
+    T.ex = (double*)dalloc(nb * MPC_NZ_NX * 8);
+    double* d_sig = nz_per_ego ? (double*)dalloc(nb * NZ_NSIG * 8) : nullptr;
+    if (!C.x || !C.nobs || !C.active || !C.n_active || !C.alist || !C.n_list || !C.xa || !C.obsa || !C.nobsa ||
+        !C.u0a || !C.sta || !d_xinit || !S.q || !S.qflags || !d_hslot || !S.n_steps || !d_actors || !T.aval ||
+        !T.aflags || !T.slab || !T.ex || (nz_per_ego && !d_sig)) {
+        release();
+        return fail(MPC_E_ALLOC, "hipMalloc noisy-loop buffers");
+    }
+    CvState V = {};
+    V.W = W;
+    V.K = K;
+    V.lead_range = lead_range;
+    NzState Z = {};
+    Z.sig = d_sig;
+    Z.shared = nz_per_ego ? zero : noise[0];
+    Z.k0 = (unsigned)(seed & 0xffffffffull);
+    Z.k1 = (unsigned)(seed >> 32);
+    Z.g0 = (unsigned long long)ego_offset;
+    Z.u_min0 = c->p.u_min[0];
+    Z.u_min1 = c->p.u_min[1];
+    Z.u_max0 = c->p.u_max[0];
+    Z.u_max1 = c->p.u_max[1];
+    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
+    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
+    Z.hist_ua = hist_ua ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
+    Z.hist_xm = hist_xm ? (double*)dalloc(nh * ns * 5 * 8) : nullptr;
+    S.hist_obs_s = hist_car_s ? (double*)dalloc(nh * ns * 8) : nullptr;
+    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
+    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
+    T.hist_nobs = hist_nobs ? (int*)dalloc(nh * ns * 4) : nullptr;
+    T.hist_slab = nullptr;                   // tr_fsm_kernel's rows are A wide: cv_lead_kernel writes the rows
+    V.hist_slab = hist_slab ? (double*)dalloc(nh * ns * nak * 2 * 8) : nullptr;
+    V.hist_lead = hist_lead ? (int*)dalloc(nh * ns * nk * 4) : nullptr;
+    if ((hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_ua && !Z.hist_ua) || (hist_xm && !Z.hist_xm) ||
+        (hist_car_s && !S.hist_obs_s) || (hist_tl && !S.hist_tl) || (hist_status && !S.hist_status) ||
+        (hist_nobs && !T.hist_nobs) || (hist_slab && !V.hist_slab) || (hist_lead && !V.hist_lead)) {
+        release();
+        return fail(MPC_E_ALLOC, "hipMalloc noisy-loop histories");
+    }
+    hipStream_t st = c->stream;
+    hipEvent_t ev[SW_EVENTS] = {};
+    auto cleanup = [&]() {
+        hipStreamSynchronize(st);
+        for (auto& e : ev)
+            if (e) hipEventDestroy(e);
+        release();
+    };
+    // steps that never run stay NaN / -1 (all-ones bytes)
+    bool ok0 = true;
+    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
+    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
+    if (Z.hist_ua) ok0 = ok0 && hipMemsetAsync(Z.hist_ua, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
+    if (Z.hist_xm) ok0 = ok0 && hipMemsetAsync(Z.hist_xm, 0xff, nh * ns * 5 * 8, st) == hipSuccess;
+    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
+    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
+    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
+    if (T.hist_nobs) ok0 = ok0 && hipMemsetAsync(T.hist_nobs, 0xff, nh * ns * 4, st) == hipSuccess;
+    if (V.hist_slab) ok0 = ok0 && hipMemsetAsync(V.hist_slab, 0xff, nh * ns * nak * 2 * 8, st) == hipSuccess;
+    if (V.hist_lead) ok0 = ok0 && hipMemsetAsync(V.hist_lead, 0xff, nh * ns * nk * 4, st) == hipSuccess;
+    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (nsc > 0 && A > 0)
+        ok0 = ok0 && hipMemcpyAsync(d_actors, actors, (size_t)nsc * na * sizeof(mpc_actor), hipMemcpyHostToDevice,
+                                    st) == hipSuccess;
+    if (nz_per_ego)
+        ok0 = ok0 && hipMemcpyAsync(d_sig, hsig.data(), nb * NZ_NSIG * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok0) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "noisy-loop buffer initialisation");
+    }
+    const dim3 tb(256), tg((B + 255) / 256);
+    const dim3 wb(64 * ((W + 63) / 64)), wg(B / W);          // a workgroup per world
+    hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, d_xinit, s_stop, max_steps);
+    hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
+    hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+            cleanup();
+            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
+        }
+    if (hipEventRecord(ev[0], st) != hipSuccess) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
+    }
+    // the sweep's ring: step i ran between events i and i + 1, read at a host sync at most 8 steps later
+    std::vector<double> ms;
+    auto read_times = [&](int upto) {
+        for (int i = (int)ms.size(); i < upto; ++i) {
+            float t = NAN;
+            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
+            ms.push_back(t);
+        }
+    };
+    rc = MPC_SUCCESS;
+    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
+    int nl = 0;
+    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        cleanup();
+        return fail(MPC_E_DEVICE, "noisy-loop initial ego list");
+    }
+    try {
+        for (int step = 0; step < max_steps && nl > 0; ++step) {
+            hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
+            hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
+            const dim3 lg((nl + 255) / 256);
+            hipLaunchKernelGGL(nz_measure_kernel, lg, tb, 0, st, nl, B, AK, C, S, T, Z, step, max_steps);
+            rc = launch_solve(c, kp, nl, C.xa, with_slab ? C.obsa : nullptr, with_slab ? C.nobsa : nullptr, nullptr,
+                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
+            if (rc) break;
+            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
+                rc = fail(MPC_E_DEVICE, "noisy-loop active-count reset");
+                break;
+            }
+            hipLaunchKernelGGL(nz_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, T, Z, s_stop, step,
+                               max_steps);
+            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
+                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
+                break;
+            }
+            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
+                int nact = 0;
+                if (hipMemcpyAsync(&nact, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipStreamSynchronize(st) != hipSuccess) {
+                    rc = fail(MPC_E_DEVICE, "noisy-loop step sync");
+                    break;
+                }
+                read_times(step + 1);
+                if (nact == 0) break;
+                if (nact < nl) {                                // egos left: shrink the solver's list
+                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
+                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess) {
+                        rc = fail(MPC_E_DEVICE, "noisy-loop ego list");
+                        break;
+                    }
+                }
+            }
+        }
+        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "noisy-loop kernel launch");
+        if (rc == MPC_SUCCESS) {
+            std::vector<double> hq(nb * MPC_CL_NQ), hx(extra ? nb * MPC_NZ_NX : 0);
+            std::vector<int> hn(nb);
+            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (extra) ok = ok && hipMemcpyAsync(hx.data(), T.ex, nb * MPC_NZ_NX * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_ua) ok = ok && hipMemcpyAsync(hist_ua, Z.hist_ua, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_xm) ok = ok && hipMemcpyAsync(hist_xm, Z.hist_xm, nh * ns * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_car_s) ok = ok && hipMemcpyAsync(hist_car_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_nobs) ok = ok && hipMemcpyAsync(hist_nobs, T.hist_nobs, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_slab) ok = ok && hipMemcpyAsync(hist_slab, V.hist_slab, nh * ns * nak * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (hist_lead) ok = ok && hipMemcpyAsync(hist_lead, V.hist_lead, nh * ns * nk * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = ok && hipStreamSynchronize(st) == hipSuccess;
+            if (!ok) {
+                rc = fail(MPC_E_DEVICE, "noisy-loop copy-back");
+            } else {
+                for (size_t b = 0; b < nb; ++b) {             // column-major on the device -> one row per ego
+                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
+                    if (extra)
+                        for (int k = 0; k < MPC_NZ_NX; ++k) extra[b * MPC_NZ_NX + k] = hx[(size_t)k * nb + b];
+                }
+                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
+                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
+                if (step_ms)
+                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        rc = fail(MPC_E_ALLOC, "noisy-loop host buffers");
+    }
+    cleanup();
+    return rc;
+}
+
+// the draws of mpc_closed_loop_noisy on their own (include/mpcqp.h), on the context's backend
+extern "C" int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const long long* ego, const int* step,
+                              const int* channel, unsigned* words, double* z) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!ego || !step || !channel))) return fail(MPC_E_ARG, "bad noise-draw arguments");
+    for (int i = 0; i < n; ++i) {
+        if (ego[i] < 0) return fail(MPC_E_ARG, "noise draw: ego index < 0");
+        if (channel[i] < 0 || channel[i] >= MPC_NZ_CHANNELS) return fail(MPC_E_ARG, "noise draw: channel outside 0 .. 47");
+    }
+    if (n == 0 || (!words && !z)) return MPC_SUCCESS;
+    if (c->cpu) {
+        mpcqp_cpu::noise_draw(seed, n, ego, step, channel, words, z);
+        return MPC_SUCCESS;
+    }
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const size_t nn = (size_t)n;
+    std::vector<void*> bufs;
+    auto dalloc = [&](size_t bytes) -> void* {
+        void* ptr = nullptr;
+        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
+        bufs.push_back(ptr);
+        return ptr;
+    };
+    auto release = [&]() { for (void* q : bufs) hipFree(q); };
+    long long* d_ego = (long long*)dalloc(nn * 8);
+    int* d_step = (int*)dalloc(nn * 4);
+    int* d_ch = (int*)dalloc(nn * 4);
+    unsigned* d_w = words ? (unsigned*)dalloc(nn * 16) : nullptr;
+    double* d_z = z ? (double*)dalloc(nn * 8) : nullptr;
+    if (!d_ego || !d_step || !d_ch || (words && !d_w) || (z && !d_z)) {
+        release();
+        return fail(MPC_E_ALLOC, "hipMalloc noise-draw buffers");
+    }
+    hipStream_t st = c->stream;
+    bool ok = hipMemcpyAsync(d_ego, ego, nn * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d_step, step, nn * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d_ch, channel, nn * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(nz_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (unsigned)(seed & 0xffffffffull),
+                           (unsigned)(seed >> 32), d_ego, d_step, d_ch, d_w, d_z);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (words) ok = ok && hipMemcpyAsync(words, d_w, nn * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (z) ok = ok && hipMemcpyAsync(z, d_z, nn * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    release();
+    return ok ? MPC_SUCCESS : fail(MPC_E_DEVICE, "noise draw");
 }
 
 extern "C" int mpc_global_pose(mpc_ctx* c, int n, const double* s, const double* d, double* out) {

@@ -53,6 +53,12 @@ class MpcActor(C.Structure):
                 ("end_s", C.c_double), ("stop_duration", C.c_double)]
 
 
+class MpcNoise(C.Structure):
+    """`mpc_noise` of include/mpcqp.h: the sigmas of mpc_closed_loop_noisy (all zero: no noise)."""
+    _fields_ = [("meas_sigma", C.c_double * 5), ("act_sigma", C.c_double * 2), ("proc_sigma", C.c_double * 5),
+                ("perc_sigma", C.c_double * 2)]
+
+
 class MpcError(RuntimeError):
     pass
 
@@ -60,7 +66,8 @@ class MpcError(RuntimeError):
 EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_batch_device", "mpc_lookup",
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
-           "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
+           "mpc_noise_draw", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -81,6 +88,11 @@ MAX_WORLD = 256
 CVX_MIN_LEAD_GAP, CVX_MIN_LEAD_EGO, CVX_MAX_LEADERS = 3, 4, 5
 CV_NX = 6
 CVX_FIELDS = TRX_FIELDS + ("min_lead_gap", "min_lead_ego", "max_leaders")
+# mpc_closed_loop_noisy: the noise channels (MPC_NZ_CH_*) and the columns its `extra` adds (MPC_NZX_*)
+NZ_CH_MEAS, NZ_CH_ACT, NZ_CH_PROC, NZ_CH_PERC, NZ_CHANNELS = 0, 5, 7, 16, 48
+NZX_U1A_MIN, NZX_U1A_MAX, NZX_U2A_MIN, NZX_U2A_MAX, NZX_N_CLAMPED = 6, 7, 8, 9, 10
+NZ_NX = 11
+NZX_FIELDS = CVX_FIELDS + ("u1a_min", "u1a_max", "u2a_min", "u2a_max", "n_clamped")
 
 _lib = None
 
@@ -135,6 +147,16 @@ def lib():
     L.mpc_closed_loop_convoy.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.POINTER(MpcActor),
                                          C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp,
                                          _ip, _ip, _ip, _dp, _ip, _ip, _dp]
+    L.mpc_default_noise.restype = None
+    L.mpc_default_noise.argtypes = [C.POINTER(MpcNoise)]
+    L.mpc_closed_loop_noisy.restype = C.c_int
+    L.mpc_closed_loop_noisy.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.POINTER(MpcActor),
+                                        C.c_int, C.c_int, C.POINTER(MpcNoise), C.c_int, C.c_ulonglong, C.c_longlong,
+                                        C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _ip,
+                                        _ip, _ip, _dp, _ip, _ip, _dp]
+    L.mpc_noise_draw.restype = C.c_int
+    L.mpc_noise_draw.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.POINTER(C.c_longlong), _ip, _ip,
+                                 C.POINTER(C.c_uint), _dp]
     L.mpc_comm_unique_id.restype = C.c_int
     L.mpc_comm_unique_id.argtypes = [C.c_char_p]
     L.mpc_comm_create.restype = C.c_int
@@ -176,6 +198,19 @@ def default_fsm(**kw):
     for k, v in kw.items():
         setattr(f, k, v)
     return f
+
+
+def default_noise(**kw):
+    """mpc_default_noise (every sigma 0) with the given fields set: meas_sigma [5], act_sigma [2], proc_sigma [5],
+    perc_sigma [2]; a scalar sets every component of its field."""
+    n = MpcNoise()
+    lib().mpc_default_noise(C.byref(n))
+    for k, v in kw.items():
+        arr = getattr(n, k)
+        vals = np.broadcast_to(np.asarray(v, np.float64), (len(arr),))
+        for i, x in enumerate(vals):
+            arr[i] = float(x)
+    return n
 
 
 def car(trigger_s, start_s, v, end_s):
@@ -430,6 +465,73 @@ class Solver:
         extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
         return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
                     hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl, hist_lead=hd)
+
+    def closed_loop_noisy(self, x_init, W=1, K=0, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
+                          s_max=None, hist_egos=(), noise=None, seed=0, lo=0):
+        """mpc_closed_loop_noisy: closed_loop_convoy with seeded noise between the world and the solver.  noise:
+        None (no noise), one MpcNoise (shared), or a sequence of B MpcNoise.  Ego b draws as global ego lo + b
+        (`lo` is passed as ego_offset and added to the index columns like closed_loop_convoy's), so a row depends
+        on (seed, lo + b) and its world only.
+        Returns closed_loop_convoy's dict with extra [B,11] (columns NZX_FIELDS), hist_ua [n_hist,max_steps,2] (the
+        applied controls; hist_u stays the commanded ones) and hist_xm [n_hist,max_steps,5] (the state the solver
+        was given)."""
+        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
+        B = x_init.shape[0]
+        if s_stop is None:
+            if s_max is None:
+                raise ValueError("give s_stop or s_max")
+            s_stop = s_max - 1.0
+        arr, A, n_scripts = _script_array(scripts)
+        if noise is None:
+            nz, n_noise = None, 0
+        elif isinstance(noise, MpcNoise):
+            nz, n_noise = C.pointer(noise), 1
+        else:
+            n_noise = len(noise)
+            if isinstance(noise, C.Array):
+                buf = noise
+            else:
+                buf = (MpcNoise * max(n_noise, 1))()
+                for i, z in enumerate(noise):
+                    C.memmove(C.byref(buf, i * C.sizeof(MpcNoise)), C.byref(z), C.sizeof(MpcNoise))
+            nz = C.cast(buf, C.POINTER(MpcNoise))
+        K = int(K)
+        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
+        nh = he.size
+        quant = np.empty((B, CL_NQ)); extra = np.empty((B, NZ_NX))
+        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
+        hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
+        ha = np.empty((nh, max_steps, 2)); hm = np.empty((nh, max_steps, 5))
+        ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
+        hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, max(A + K, 0), 2))
+        hd = np.empty((nh, max_steps, max(K, 0)), np.int32)
+        g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
+        gi = (lambda a: _pi(a) if nh else None)
+        _check(lib().mpc_closed_loop_noisy(self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A),
+                                           int(n_scripts), nz, int(n_noise), int(seed), int(lo), int(max_steps),
+                                           float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(ha),
+                                           g(hm), g(hc), gi(ht), gi(hs), gi(hn), g(hl) if A + K > 0 else None,
+                                           gi(hd) if K > 0 else None, _pi(ns), _p(sm)), "mpc_closed_loop_noisy")
+        quant[:, 0] += lo
+        extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
+        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
+                    hist_ua=ha, hist_xm=hm, hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl,
+                    hist_lead=hd)
+
+    def noise_draw(self, seed, ego, step, channel):
+        """mpc_noise_draw on this context's backend: the Philox words [n,4] (uint32) and the variates z [n] of
+        (seed, ego[i], step[i], channel[i]); the index arrays broadcast against each other."""
+        ego, step, channel = np.broadcast_arrays(np.asarray(ego, np.int64), np.asarray(step, np.int32),
+                                                 np.asarray(channel, np.int32))
+        ego = np.ascontiguousarray(ego.ravel(), np.int64)
+        step = np.ascontiguousarray(step.ravel(), np.int32)
+        channel = np.ascontiguousarray(channel.ravel(), np.int32)
+        n = ego.size
+        words = np.empty((n, 4), np.uint32); z = np.empty(n)
+        _check(lib().mpc_noise_draw(self.h, int(seed), n, ego.ctypes.data_as(C.POINTER(C.c_longlong)), _pi(step),
+                                    _pi(channel), words.ctypes.data_as(C.POINTER(C.c_uint)), _p(z)),
+               "mpc_noise_draw")
+        return words, z
 
     def cl_verdicts(self, quant, s_total):
         """mpc_cl_verdicts: the restated acceptance verdicts (sanity_checks.check_verdicts, with this context's

@@ -472,6 +472,90 @@ def run_convoy_sweep(mpc, trajectory, x_init, W, K, lead_range=np.inf, scripts=N
     return r
 
 
+_NZ_M0, _NZ_M1, _NZ_W0, _NZ_W1 = (np.uint64(c) for c in (0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85))
+_NZ_MASK, _NZ_32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+NOISE_C = 1.7320508075688772 * 2.0 ** -32          # the double nearest sqrt(3), scaled exactly
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 in numpy uint64 arithmetic: counter (c0, c1, c2, c3) and key (k0, k1) of 32-bit words
+    (arrays broadcast) -> the four output words [..., 4] (uint32)."""
+    c = [np.asarray(x, np.uint64) & _NZ_MASK for x in counter]
+    k = [np.asarray(x, np.uint64) & _NZ_MASK for x in key]
+    for _ in range(10):
+        p0, p1 = _NZ_M0 * c[0], _NZ_M1 * c[2]       # 32 x 32 -> 64 bits: no overflow
+        c = [(p1 >> _NZ_32) ^ c[1] ^ k[0], p1 & _NZ_MASK, (p0 >> _NZ_32) ^ c[3] ^ k[1], p0 & _NZ_MASK]
+        k = [(k[0] + _NZ_W0) & _NZ_MASK, (k[1] + _NZ_W1) & _NZ_MASK]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def noise_variates(seed, ego, step, channel):
+    """The draws of mpc_closed_loop_noisy restated (include/mpcqp.h; what Solver.noise_draw returns, bit for bit):
+    key (seed & 0xffffffff, seed >> 32), counter (ego & 0xffffffff, ego >> 32, step, channel), one Philox4x32-10
+    block per draw, z = (w0 + w1 + w2 + w3 - 8589934590) * sqrt(3) * 2^-32.  ego, step, channel broadcast.
+    Returns (words [..., 4] uint32, z [...])."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    g = np.asarray(ego).astype(np.uint64)                    # int64 or uint64 (egos past 2^63 in the known answers)
+    step = np.asarray(step, np.int64).astype(np.uint64) & _NZ_MASK
+    ch = np.asarray(channel, np.int64).astype(np.uint64) & _NZ_MASK
+    w = philox4x32((g & _NZ_MASK, g >> _NZ_32, step, ch), (np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)))
+    total = w.astype(np.uint64).sum(axis=-1)                 # < 2^34: exact as a double
+    return w, (total.astype(np.float64) - 8589934590.0) * NOISE_C
+
+
+def run_noisy_sweep(mpc, trajectory, x_init, noise, seeds, W=1, K=0, lead_range=np.inf, scripts=None,
+                    max_steps=2000, hist_egos=(), s_stop=None, seed=0):
+    """A Monte Carlo disturbance sweep (mpc_closed_loop_noisy): the scenario x_init [W,5] (one ego, or one world of
+    W egos with run_convoy_sweep's scripts, one per ego of the world) replicated once per entry of `seeds` and run
+    under `noise` (an mpcqp.MpcNoise shared by all).  A seed is a stream index under the key `seed`: replica s runs
+    as the global egos s*W .. s*W + W - 1, so its rows equal Solver.closed_loop_noisy(x_init, ..., seed=seed,
+    lo=s*W) whatever else shares the batch; runs of consecutive seeds go into one library call each.  hist_egos
+    index the replicated batch (replica r, ego i of the world: r*W + i).  Returns closed_loop_noisy's dict over
+    all replicas in `seeds` order plus 'seeds' [n], 'verdicts' [n*W], 'counts', one boolean column per verdict
+    name and 'pass_rate' {name: fraction of the n*W egos passing}."""
+    x_world = np.asarray(x_init, np.float64).reshape(-1, 5)
+    W = int(W)
+    if x_world.shape[0] != W:
+        raise ValueError("x_init holds one world: W start states")
+    seeds = [int(s) for s in seeds]
+    if not seeds or min(seeds) < 0:
+        raise ValueError("seeds: a non-empty sequence of integers >= 0")
+    rows = None
+    if scripts is not None:
+        scripts = [s if isinstance(s, TrafficScript) else TrafficScript(s or ()) for s in scripts]
+        if len(scripts) != W:
+            raise ValueError("one script (or None) per ego of the world")
+        A = max((len(s.actors) for s in scripts), default=0)
+        rows = [s.padded(A) for s in scripts] if A else None
+    slv = mpc.solver(max_obs=0)
+    hist_egos = np.asarray(hist_egos, np.int64).ravel()
+    parts, r0 = [], 0
+    while r0 < len(seeds):                                   # runs of consecutive seeds: one call each
+        r1 = r0 + 1
+        while r1 < len(seeds) and seeds[r1] == seeds[r1 - 1] + 1:
+            r1 += 1
+        n = r1 - r0
+        he = hist_egos[(hist_egos >= r0 * W) & (hist_egos < r1 * W)] - r0 * W
+        parts.append(slv.closed_loop_noisy(np.tile(x_world, (n, 1)), W, K, lead_range=lead_range,
+                                           scripts=None if rows is None else rows * n, max_steps=max_steps,
+                                           s_stop=s_stop, s_max=trajectory.s_max, hist_egos=he, noise=noise,
+                                           seed=seed, lo=seeds[r0] * W))
+        p = parts[-1]
+        p["hist_egos"] = p["hist_egos"] + r0 * W
+        p["hist_lead"] = p["hist_lead"] + np.where(p["hist_lead"] >= 0, r0 * W, 0).astype(np.int32)
+        r0 = r1
+    r = {k: (np.fmax.reduce([p[k] for p in parts]) if k == "step_ms" else np.concatenate([p[k] for p in parts]))
+         for k in parts[0]}
+    r["seeds"] = np.asarray(seeds, np.int64)
+    v, counts = slv.cl_verdicts(r["quant"], trajectory.s_max)
+    r["verdicts"] = v
+    r["counts"] = {k: int(counts[i]) for i, k in enumerate(mpcqp.CLV_NAMES)}
+    r["pass_rate"] = {k: float(counts[i]) / v.size for i, k in enumerate(mpcqp.CLV_NAMES)}
+    for i, k in enumerate(mpcqp.CLV_NAMES):
+        r[k] = (v & (1 << i)) != 0
+    return r
+
+
 def closed_loop_checks(mpc, fsm, trajectory, r, verbose=False):
     """The restated trajectory_tracking_check (sanity_checks.py:79-184) on every ego of a closed_loop()
     result (mpcqp.Solver.closed_loop layout); returns the per-ego verdicts [B] (bool)."""

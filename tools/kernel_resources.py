@@ -1,5 +1,6 @@
 """Per-kernel resources of the built libmpcqp.so, read from the gfx950 code object's metadata notes
-(no GPU needed): scratch bytes per lane (.private_segment_fixed_size), VGPRs and AGPRs.
+(no GPU needed): scratch bytes per lane (.private_segment_fixed_size), LDS bytes per workgroup
+(.group_segment_fixed_size), VGPRs, SGPRs and AGPRs.
 
   python tools/kernel_resources.py [path/to/libmpcqp.so]      -> JSON list on stdout
 
@@ -29,7 +30,7 @@ def kernel_resources(so_path):
     out, cur = [], None
     for line in notes.splitlines():
         t = line.strip().lstrip("- ").strip()
-        m = re.match(r"\.(name|private_segment_fixed_size|vgpr_count|agpr_count):\s+(\S+)", t)
+        m = re.match(r"\.(name|private_segment_fixed_size|group_segment_fixed_size|vgpr_count|sgpr_count|agpr_count):\s+(\S+)", t)
         if not m:
             continue
         key, val = m.groups()
@@ -37,7 +38,8 @@ def kernel_resources(so_path):
             cur = {"agpr": int(val)}
             out.append(cur)
         elif cur is not None:
-            cur[{"name": "name", "private_segment_fixed_size": "scratch", "vgpr_count": "vgpr"}[key]] = (
+            cur[{"name": "name", "private_segment_fixed_size": "scratch", "group_segment_fixed_size": "lds",
+                 "vgpr_count": "vgpr", "sgpr_count": "sgpr"}[key]] = (
                 val if key == "name" else int(val))
     return [k for k in out if "name" in k]
 

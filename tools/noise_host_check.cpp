@@ -1,0 +1,232 @@
+// Stand-alone sanitizer check of the host backend's noisy loop (csrc/cpu_backend.h: closed_loop_noisy, noise_draw),
+// built and run by tools/noise_host_check.py with -fsanitize=address,undefined:
+//   noise_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
+// Runs on 3 worker threads, N = 5, 12 egos in worlds of 4, each ego with a script of a car and a light:
+// (1) the known answer of Philox4x32-10 for the all-zero counter and key, and the variate's bound over 4096 draws;
+// (2) an all-zero shared struct and all-zero per-ego structs against closed_loop_convoy: every quantity column but
+//     the step time, extras 0..5 and n_steps equal byte for byte, the applied extremes equal to the commanded ones
+//     and no clamped step;
+// (3) noisy runs over every argument variant (shared and per-ego structs, K = 14 beside the two actors, a finite
+//     lead_range, two selected egos with every history, no history and no extras, no script, a large ego_offset,
+//     an actuator that clamps): recorded leaders belong to the ego's world, the applied controls stay inside the
+//     bounds, hist_xm and hist_ua are written for exactly the steps that ran, and a run repeated is identical.
+// Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/mpcqp.h"
+#include "../safe-autonomous-driving-mpc_amd/csrc/cpu_backend.h"
+
+static mpc_actor none() {
+    mpc_actor a;
+    std::memset(&a, 0, sizeof(a));
+    return a;
+}
+static mpc_actor car(double trigger_s, double start_s, double v, double end_s) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_CAR; a.trigger_s = trigger_s; a.pos_s = start_s; a.v = v; a.end_s = end_s;
+    return a;
+}
+static mpc_actor light(double pos_s, double trigger_s, double stop_duration) {
+    mpc_actor a = none();
+    a.kind = MPC_ACTOR_LIGHT; a.trigger_s = trigger_s; a.pos_s = pos_s; a.stop_duration = stop_duration;
+    return a;
+}
+static mpc_noise quiet() {
+    mpc_noise n;
+    std::memset(&n, 0, sizeof(n));
+    return n;
+}
+static mpc_noise mild(double scale) {
+    mpc_noise n = quiet();
+    const double m[5] = {0.05, 0.02, 0.005, 0.0005, 0.05}, pr[5] = {0.02, 0.01, 0.005, 0.0005, 0.05};
+    for (int j = 0; j < 5; ++j) { n.meas_sigma[j] = scale * m[j]; n.proc_sigma[j] = scale * pr[j]; }
+    n.act_sigma[0] = scale * 0.02; n.act_sigma[1] = scale * 0.2;
+    n.perc_sigma[0] = scale * 0.3; n.perc_sigma[1] = scale * 0.2;
+    return n;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[2];
+    if (std::fread(hdr, sizeof(int), 2, f) != 2) return 2;
+    const int T = hdr[0], Tu = hdr[1];
+    std::vector<double> X(5 * (size_t)T), U(2 * (size_t)Tu);
+    if (std::fread(X.data(), 8, X.size(), f) != X.size() || std::fread(U.data(), 8, U.size(), f) != U.size()) return 2;
+    std::fclose(f);
+    mpcqp_host::HostTable table;
+    if (!mpcqp_host::build_host_table(X.data(), T, U.data(), Tu, table)) return 2;
+    mpcqp_cpu::Backend be(std::move(table));
+    be.threads = 3;
+    mpc_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.N = 5; p.max_obs = 0; p.dt = 0.2;
+    p.u_min[0] = -0.6; p.u_min[1] = -5.0; p.u_max[0] = 0.6; p.u_max[1] = 4.0;
+    p.vehicle_radius = 1.0; p.w_d = 10.0; p.w_o = 10.0; p.w_v = 5.0; p.w_u1 = 0.5; p.w_u2 = 0.5;
+    p.obstacle_safety_distance = 5.0; p.max_time_2_obs = 1.5; p.wheelbase = 2.8; p.lane_width = 3.0;
+    p.safe_lane_margin = 0.1; p.brake_distance = 40.0; p.brake_accel = -2.0; p.linearization = 1;
+    p.sqp_iters = 1; p.max_iter = 80; p.tol = 1e-9; p.tol_mu = 1e-10; p.elastic_rho = 1e5; p.polish = 2;
+    p.sqp_tol = 1e-10;
+    int bad = 0;
+
+    // (1) the noise source
+    {
+        const long long ego0 = 0;
+        const int zero = 0;
+        unsigned w[4];
+        double z = 0.0;
+        mpcqp_cpu::noise_draw(0, 1, &ego0, &zero, &zero, w, &z);
+        const unsigned want[4] = {0x6627e8d5u, 0xe169c58du, 0xbc57ac4cu, 0x9b00dbd8u};
+        if (std::memcmp(w, want, sizeof(w)) != 0) ++bad;
+        std::vector<long long> ego(4096);
+        std::vector<int> step(4096), ch(4096);
+        std::vector<double> zs(4096);
+        for (int i = 0; i < 4096; ++i) { ego[i] = (1ll << 33) + i; step[i] = i % 24; ch[i] = i % MPC_NZ_CHANNELS; }
+        mpcqp_cpu::noise_draw(0xfedcba9876543210ull, 4096, ego.data(), step.data(), ch.data(), nullptr, zs.data());
+        double sum = 0.0;
+        for (double v : zs) {
+            if (!(std::fabs(v) <= 2.0 * std::sqrt(3.0))) ++bad;
+            sum += v;
+        }
+        if (std::fabs(sum / 4096.0) > 5.0 / 64.0) ++bad;       // five standard errors of 1 / sqrt(4096)
+        mpcqp_cpu::noise_draw(1, 4096, ego.data(), step.data(), ch.data(), nullptr, nullptr);
+    }
+
+    const int B = 12, W = 4, ms = 60;
+    const size_t ns = ms;
+    const double s0 = 440.0, s_stop = 500.0, far = 1.0e6;
+    const double start[B] = {s0, s0 + 8.0, s0 + 8.0, s0 + 20.0, s0 + 30.0, s0 + 38.0, s0 + 45.0, s_stop - 3.0,
+                             s0 + 5.0, s0, s_stop + 2.0, s0 + 12.0};
+    std::vector<double> x0(5 * (size_t)B, 0.0);
+    for (int b = 0; b < B; ++b) {
+        double st[5];
+        be.ref->state(start[b], st);
+        x0[5 * b] = start[b]; x0[5 * b + 1] = 0.01 * (b % 3); x0[5 * b + 3] = st[3]; x0[5 * b + 4] = 6.0 + 0.5 * (b % 4);
+    }
+    const int A = 2;
+    std::vector<mpc_actor> scripts;
+    for (int b = 0; b < B; ++b) {
+        scripts.push_back(car(s0 + 5.0 + b, s0 + 40.0 + 3.0 * b, 4.0, b % 2 ? far : s0 + 70.0));
+        scripts.push_back(light(s0 + 50.0, 100.0, 0.6 + 0.2 * (b % 3)));
+    }
+
+    struct Out {
+        std::vector<double> quant, extra, hx, hu, ha, hm, hl;
+        std::vector<int> n_steps, hd, hn;
+    };
+    auto noisy = [&](int Wc, int K, double range, const std::vector<mpc_actor>& sc, int Ac, int n_scripts,
+                     const std::vector<mpc_noise>& nz, unsigned long long seed, long long offset,
+                     const std::vector<int>& egos, bool extras, Out& o) {
+        const int nh = (int)egos.size(), AK = Ac + K;
+        std::vector<int> slot(B, -1);
+        for (int k = 0; k < nh; ++k) slot[egos[k]] = k;
+        o.quant.assign((size_t)B * MPC_CL_NQ, -1.0);
+        o.extra.assign((size_t)B * MPC_NZ_NX, -7.0);
+        o.n_steps.assign(B, -1);
+        o.hx.assign((size_t)nh * (ns + 1) * 5, 0.0); o.hu.assign((size_t)nh * ns * 2, 0.0);
+        o.ha.assign((size_t)nh * ns * 2, 0.0); o.hm.assign((size_t)nh * ns * 5, 0.0);
+        o.hl.assign((size_t)nh * ns * AK * 2, 0.0);
+        o.hd.assign((size_t)nh * ns * K, 0); o.hn.assign((size_t)nh * ns, 0);
+        std::vector<double> hc((size_t)nh * ns), step_ms(ns);
+        std::vector<int> ht((size_t)nh * ns), hs((size_t)nh * ns);
+        bool with_slab = K > 0 && Wc > 1;
+        for (const mpc_actor& a : sc) with_slab = with_slab || a.kind != MPC_ACTOR_NONE;
+        const int rc = be.closed_loop_noisy(
+            p, B, Wc, K, range, x0.data(), sc.empty() ? nullptr : sc.data(), Ac, n_scripts, with_slab, nz.data(),
+            (int)nz.size(), seed, offset, ms, s_stop, o.quant.data(), extras ? o.extra.data() : nullptr, nh,
+            slot.data(), nh ? o.hx.data() : nullptr, nh ? o.hu.data() : nullptr, nh ? o.ha.data() : nullptr,
+            nh ? o.hm.data() : nullptr, nh ? hc.data() : nullptr, nh ? ht.data() : nullptr, nh ? hs.data() : nullptr,
+            nh ? o.hn.data() : nullptr, nh && AK ? o.hl.data() : nullptr, nh && K ? o.hd.data() : nullptr,
+            o.n_steps.data(), extras ? step_ms.data() : nullptr);
+        if (rc != MPC_SUCCESS) ++bad;
+        for (int k = 0; k < nh; ++k) {
+            const int e = egos[k], n = o.n_steps[e];
+            for (size_t t = 0; t < ns; ++t) {
+                const bool ran = (int)t < n;
+                for (int j = 0; j < 5; ++j)                // hist_xm: a number for a step that ran, NaN after
+                    if (std::isnan(o.hm[((size_t)k * ns + t) * 5 + j]) == ran) ++bad;
+                for (int j = 0; j < 2; ++j) {
+                    const double ua = o.ha[((size_t)k * ns + t) * 2 + j];
+                    if (std::isnan(ua) == ran) ++bad;
+                    if (ran && (ua < p.u_min[j] - 1e-12 || ua > p.u_max[j] + 1e-12) &&
+                        nz[nz.size() == 1 ? 0 : e].act_sigma[j] != 0.0)
+                        ++bad;                             // a perturbed control is clamped to the bounds
+                }
+                int nlead = 0;
+                for (int m = 0; m < K; ++m) {
+                    const int j = o.hd[((size_t)k * ns + t) * K + m];
+                    if (j < 0) continue;
+                    ++nlead;
+                    if (j / Wc != e / Wc || j == e) ++bad;
+                }
+                if (nlead > K || (nlead > 0 && o.hn[(size_t)k * ns + t] < nlead)) ++bad;
+            }
+        }
+        if (extras)
+            for (int b = 0; b < B; ++b) {
+                const double* e = &o.extra[(size_t)b * MPC_NZ_NX];
+                if (e[MPC_CVX_MIN_LEAD_EGO] >= 0.0 && ((int)e[MPC_CVX_MIN_LEAD_EGO] / Wc != b / Wc)) ++bad;
+                if (e[MPC_CVX_MAX_LEADERS] > (double)K) ++bad;
+                if (e[MPC_NZX_N_CLAMPED] < 0.0 || e[MPC_NZX_N_CLAMPED] > (double)o.n_steps[b]) ++bad;
+            }
+    };
+    std::vector<int> all(B), two = {9, 2}, nobody;
+    for (int b = 0; b < B; ++b) all[b] = b;
+
+    // (2) the anchor: the convoy loop on the same inputs
+    const int K = 3;
+    std::vector<double> cq((size_t)B * MPC_CL_NQ), cx((size_t)B * MPC_CV_NX), step_ms(ns);
+    std::vector<int> cn(B), slot(B, -1);
+    if (be.closed_loop_convoy(p, B, W, K, INFINITY, x0.data(), scripts.data(), A, B, true, ms, s_stop, cq.data(),
+                              cx.data(), 0, slot.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, cn.data(), step_ms.data()) != MPC_SUCCESS)
+        ++bad;
+    Out o, o2;
+    const std::vector<mpc_noise> shared_quiet(1, quiet()), each_quiet(B, quiet());
+    for (const auto* nz : {&shared_quiet, &each_quiet}) {
+        noisy(W, K, INFINITY, scripts, A, B, *nz, 5, 0, all, true, o);
+        for (int b = 0; b < B; ++b) {
+            const double* q = &o.quant[(size_t)b * MPC_CL_NQ];
+            const double* e = &o.extra[(size_t)b * MPC_NZ_NX];
+            for (int k = 0; k < MPC_CL_NQ; ++k)
+                if (k != MPC_CLQ_MAX_STEP_MS && std::memcmp(&q[k], &cq[(size_t)b * MPC_CL_NQ + k], 8) != 0) ++bad;
+            if (std::memcmp(e, &cx[(size_t)b * MPC_CV_NX], MPC_CV_NX * 8) != 0) ++bad;
+            if (o.n_steps[b] != cn[b]) ++bad;
+            if (std::memcmp(&e[MPC_NZX_U1A_MIN], &q[MPC_CLQ_U1_MIN], 4 * 8) != 0 || e[MPC_NZX_N_CLAMPED] != 0.0) ++bad;
+        }
+        if (std::memcmp(o.ha.data(), o.hu.data(), o.hu.size() * 8) != 0) ++bad;
+        for (int k = 0; k < B; ++k)
+            for (int t = 0; t < o.n_steps[k]; ++t)
+                if (std::memcmp(&o.hm[((size_t)k * ns + t) * 5], &o.hx[((size_t)k * (ns + 1) + t) * 5], 5 * 8) != 0) ++bad;
+    }
+    // (3) the noisy paths
+    std::vector<mpc_noise> each(B);
+    for (int b = 0; b < B; ++b) each[b] = b % 3 == 0 ? quiet() : mild(0.5 * b);
+    const std::vector<mpc_noise> shared(1, mild(1.0));
+    mpc_noise sloppy = quiet();
+    sloppy.act_sigma[0] = 0.6; sloppy.act_sigma[1] = 6.0;
+    noisy(W, K, INFINITY, scripts, A, B, shared, 7, 0, all, true, o);
+    noisy(W, K, INFINITY, scripts, A, B, shared, 7, 0, all, true, o2);
+    if (o.quant.size() != o2.quant.size() || o.n_steps != o2.n_steps || std::memcmp(o.hx.data(), o2.hx.data(), o.hx.size() * 8) != 0 ||
+        std::memcmp(o.hm.data(), o2.hm.data(), o.hm.size() * 8) != 0 || std::memcmp(o.extra.data(), o2.extra.data(), o.extra.size() * 8) != 0)
+        ++bad;
+    noisy(W, K, INFINITY, scripts, A, B, shared, 8, 0, all, true, o2);
+    if (std::memcmp(o.hm.data(), o2.hm.data(), 5 * 8) == 0) ++bad;         // another seed: another measurement
+    noisy(W, K, INFINITY, scripts, A, B, each, 7, 1ll << 40, all, true, o);
+    noisy(W, 14, INFINITY, scripts, A, B, each, 7, 0, all, true, o);
+    noisy(W, K, 9.0, scripts, A, B, shared, 7, 3, two, true, o);
+    noisy(W, 2, INFINITY, scripts, A, B, each, 7, 0, nobody, false, o);
+    noisy(W, K, INFINITY, {scripts[0], scripts[1]}, A, 1, shared, 7, 0, two, true, o);
+    noisy(W, K, 25.0, {}, 0, 1, each, 7, 0, all, true, o);
+    noisy(1, 0, INFINITY, {}, 0, 1, shared, 7, 0, all, true, o);
+    noisy(B, 11, INFINITY, {}, 0, 1, std::vector<mpc_noise>(1, sloppy), 7, 0, all, true, o);
+    double clamped = 0.0;
+    for (int b = 0; b < B; ++b) clamped += o.extra[(size_t)b * MPC_NZ_NX + MPC_NZX_N_CLAMPED];
+    if (clamped == 0.0) ++bad;
+    std::printf("noise_host_check: %s\n", bad ? "MISMATCH" : "clean and equal");
+    return bad ? 1 : 0;
+}
