@@ -34,7 +34,8 @@ extern "C" {
  * 3: the ego-shard communicator (mpc_comm_*, mpc_gather*, MPC_E_COMM); nothing else changed.
  * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed.
  * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
- *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol. */
+ *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
+ *    So were mpc_closed_loop_noisy / mpc_noise_draw and mpc_evaluate_batch / mpc_evaluate_batch_device. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -139,6 +140,57 @@ int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double* obs, cons
 int mpc_solve_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                            const double* ubar, double* u0, double* U, double* Xpred, int* status,
                            int* iters, void* stream);
+
+/* Batched evaluation of the reference's own measures for ANY control sequence U (it need not come from a solve):
+ * the nonlinear rollout TrajectoryTracker.predict (trajectory_tracking.py:87-114), TrajectoryTracker.cost(U, x0)
+ * (:116-152) and the rows of constraints(x0, obstacles) (:155-211), with a per-instance summary.  The evaluator
+ * uses the context's N, dt, weights, u_min / u_max, wheelbase, lane_width, vehicle_radius, safe_lane_margin,
+ * obstacle_safety_distance and max_time_2_obs, and ignores the solver knobs.  No version step: detect it by the
+ * presence of its symbol.
+ *   x0 [B][5], obs [B][max_obs][2] or NULL, n_obs [B] or NULL: mpc_solve_batch's contract (obs with
+ *              max_obs == 0 is MPC_E_ARG; NULL n_obs = all max_obs rows; n_obs[b] is clamped to [0, max_obs])
+ *   U  [B][N][2]   required (NULL is MPC_E_ARG)
+ * outputs (any may be NULL; all NULL is allowed and launches nothing):
+ *   Xpred   [B][N+1][5]      predict(x0, U): the bits a solve that returned this U wrote to its Xpred
+ *   summary [B][MPC_EV_NQ]   the MPC_EVQ_* columns below
+ *   terms   [B][5]           the cost shares (d, o, v, u1, u2), each summed over its stages in order; informative:
+ *                            they need not add up to MPC_EVQ_COST bit for bit
+ *   rows    [B][N][7 + max_obs]   stage k = 1..N is row k - 1; columns 0..5 the six lane rows in the reference's
+ *                            order (sl - d, d + sl, sl - f, f + sl, sl - l, l + sl with f = d + (wheelbase / 2) o,
+ *                            l = d + wheelbase o, sl = lane_width / 2 - vehicle_radius - safe_lane_margin);
+ *                            column 6 is v; column 7 + i is obstacle i:
+ *                            (s_obs + v_obs * (k * dt) - s) - max(obstacle_safety_distance, v * max_time_2_obs)
+ *                            with the reference's max (the first argument unless the second is greater); NaN past
+ *                            n_obs.  The reference's vector has, per stage, the lane rows, the obstacle rows, then v.
+ * Summation orders (the results do not depend on the backend, the lane-group width or B):
+ *   cost   one running sum from 0: for k = 1..N  + w_d (d - d_ref)^2, + w_o (o - o_ref)^2, + w_v (v - v_ref)^2
+ *          with the references looked up at the rolled-out s_k; then for k = 0..N-1  + w_u1 u1^2, + w_u2 u2^2
+ *   L1     per stage the sum of max(-g, 0) over its rows in the reference's order, from 0; the stage partials are
+ *          then added for k = 1..N, from 0
+ * Misuse is MPC_E_ARG with a message; B == 0 succeeds. */
+#define MPC_EVQ_COST 0           /* TrajectoryTracker.cost(U, x0)                                              */
+#define MPC_EVQ_MIN_ROW 1        /* np.min over the reference-order row vector (NaN if a row is NaN)           */
+#define MPC_EVQ_ARGMIN_STAGE 2   /* its stage 1..N: np.argmin's row (the first minimum; the first NaN row)     */
+#define MPC_EVQ_ARGMIN_KIND 3    /* its kind: 0..5 the lane rows, 6 the v >= 0 row, 7 + i obstacle i           */
+#define MPC_EVQ_L1 4             /* sum of max(-g, 0) over all rows (NaN if a row is NaN)                      */
+#define MPC_EVQ_N_NEG 5          /* rows with g < 0                                                            */
+#define MPC_EVQ_MIN_LANE 6       /* minima per row family, numpy's min (NaN if a row of the family is NaN);    */
+#define MPC_EVQ_MIN_OBS 7        /*   MIN_OBS is NaN when the instance has no obstacle                         */
+#define MPC_EVQ_MIN_V 8
+#define MPC_EVQ_BOX 9            /* max over k and component of max(u_min - u, u - u_max, 0): the excess over
+                                    the bounds the reference hands SLSQP (:249-252); NaN if a control is NaN    */
+#define MPC_EV_NQ 10
+int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs, const double* U,
+                       double* Xpred, double* summary, double* terms, double* rows);
+/* Same, with device pointers, launched asynchronously on `stream` (a hipStream_t; 0 = null stream): one kernel,
+ * no host synchronisation, no allocation, graph-capturable.  The double arrays must be 8-byte aligned (MPC_E_ARG
+ * otherwise); n_obs without obs is MPC_E_ARG like mpc_solve_batch_device.  The call shares no state with the
+ * solver's work list or stage cache, so it may overlap a solve on another stream of the same context.  On a host
+ * context (device = -1) the pointers are host memory and the call is synchronous; every output equals the
+ * device's bit for bit. */
+int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                              const double* U, double* Xpred, double* summary, double* terms, double* rows,
+                              void* stream);
 
 /* Reference-signal service on the device table: TrajectoryLoader.get_state / get_control
  * (trajectory_loader.py:86-102), batched. Host buffers, synchronous.  out_state [n][5], out_control [n][2]. */

@@ -975,6 +975,118 @@ inline void noise_draw(unsigned long long seed, int n, const long long* ego, con
     }
 }
 
+// mpc_evaluate_batch for one instance (include/mpcqp.h): the operation order of mpc_evaluate_kernel
+// (evaluate_kernel.h), stage by stage, so every output equals the device's bit for bit.  X is the rollout
+// predict(x0, U) [N+1][5]; mo the slab width (0 without obstacles), rw the row width 7 + params.max_obs;
+// summary [MPC_EV_NQ], terms [5] and rows [N][rw] may be null.
+inline void evaluate_nmin(double& m, bool& nan, double r) {
+    if (!nan) {
+        if (r != r) nan = true;
+        else if (r < m) m = r;
+    }
+}
+inline void evaluate_one(const Ref& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
+                         int rw, const double* U, double* summary, double* terms, double* rows) {
+    const int N = p.N;
+    const double inf = __builtin_inf(), qnan = __builtin_nan("");
+    const double sl = p.lane_width / 2.0 - p.vehicle_radius - p.safe_lane_margin;   // trajectory_tracking.py:169
+    const double osd = p.obstacle_safety_distance, tgap = p.max_time_2_obs, L = p.wheelbase;
+    double ct[kMaxN][5], part[kMaxN];
+    // group summary: np.argmin takes the first NaN row if there is one, else the first minimum
+    double gmin = inf, fl = inf, fo = inf, fv = inf, bx = 0.0, cnt = 0.0;
+    bool gnan = false, flnan = false, fonan = false, fvnan = false, bxnan = false;
+    int astage = 0, akind = 0;
+    for (int k = 0; k < N; ++k) {
+        const double u1 = U[2 * k], u2 = U[2 * k + 1];
+        ct[k][3] = p.w_u1 * (u1 * u1);
+        ct[k][4] = p.w_u2 * (u2 * u2);
+        const double e[4] = {p.u_min[0] - u1, u1 - p.u_max[0], p.u_min[1] - u2, u2 - p.u_max[1]};
+        for (int a = 0; a < 4; ++a) {
+            if (e[a] != e[a]) bxnan = true;
+            else if (e[a] > bx) bx = e[a];
+        }
+    }
+    for (int j = 1; j <= N; ++j) {
+        double st[5];
+        R.state(X[j][0], st);
+        const double s = X[j][0], d = X[j][1], o = X[j][2], v = X[j][4];
+        const double ed = d - st[1], eo = o - st[2], ev = v - st[4];
+        ct[j - 1][0] = p.w_d * (ed * ed);
+        ct[j - 1][1] = p.w_o * (eo * eo);
+        ct[j - 1][2] = p.w_v * (ev * ev);
+        double smin = inf, p1 = 0.0;
+        bool snan = false;
+        int skind = 0, nneg = 0;
+        double* ro = rows ? rows + (size_t)(j - 1) * rw : nullptr;
+        auto visit = [&](double r, int kind) {
+            if (!snan && (r != r || r < smin)) {
+                smin = r;
+                skind = kind;
+                snan = r != r;
+            }
+            p1 = p1 + (r != r ? r : (r < 0.0 ? -r : 0.0));
+            nneg += r < 0.0 ? 1 : 0;
+            if (ro) ro[kind] = r;
+        };
+        const double vf = d + (L / 2.0) * o, vl = d + L * o;
+        const double g[6] = {sl - d, d + sl, sl - vf, vf + sl, sl - vl, vl + sl};
+        for (int a = 0; a < 6; ++a) {
+            visit(g[a], a);
+            evaluate_nmin(fl, flnan, g[a]);
+        }
+        if (nobs > 0) {
+            const double tk = (double)j * p.dt;
+            const double vt = v * tgap;
+            const double safe = vt > osd ? vt : osd;             // the reference's max(osd, v * tgap)
+            for (int i = 0; i < nobs; ++i) {
+                const double sop = obs[2 * i] + obs[2 * i + 1] * tk;
+                const double r = (sop - s) - safe;
+                visit(r, 7 + i);
+                evaluate_nmin(fo, fonan, r);
+            }
+        }
+        if (ro)
+            for (int i = 7 + nobs; i < rw; ++i) ro[i] = qnan;
+        visit(v, 6);
+        evaluate_nmin(fv, fvnan, v);
+        part[j - 1] = p1;
+        cnt += (double)nneg;
+        if (!gnan && (astage == 0 || snan || smin < gmin)) {
+            gmin = smin;
+            gnan = snan;
+            astage = j;
+            akind = skind;
+        }
+    }
+    double cost = 0.0, t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, l1 = 0.0;
+    for (int j = 0; j < N; ++j) {
+        for (int a = 0; a < 3; ++a) {
+            cost = cost + ct[j][a];
+            t[a] = t[a] + ct[j][a];
+        }
+        l1 = l1 + part[j];
+    }
+    for (int j = 0; j < N; ++j)
+        for (int a = 3; a < 5; ++a) {
+            cost = cost + ct[j][a];
+            t[a] = t[a] + ct[j][a];
+        }
+    if (summary) {
+        summary[MPC_EVQ_COST] = cost;
+        summary[MPC_EVQ_MIN_ROW] = gnan ? qnan : gmin;
+        summary[MPC_EVQ_ARGMIN_STAGE] = (double)astage;
+        summary[MPC_EVQ_ARGMIN_KIND] = (double)akind;
+        summary[MPC_EVQ_L1] = l1;
+        summary[MPC_EVQ_N_NEG] = cnt;
+        summary[MPC_EVQ_MIN_LANE] = flnan ? qnan : fl + 0.0;
+        summary[MPC_EVQ_MIN_OBS] = (fonan || nobs == 0) ? qnan : fo + 0.0;
+        summary[MPC_EVQ_MIN_V] = fvnan ? qnan : fv + 0.0;
+        summary[MPC_EVQ_BOX] = bxnan ? qnan : bx + 0.0;
+    }
+    if (terms)
+        for (int a = 0; a < 5; ++a) terms[a] = t[a];
+}
+
 struct Backend {
     HostTable table;
     std::unique_ptr<Ref> ref;
@@ -1034,6 +1146,25 @@ struct Backend {
                                    Xpred ? Xpred + (size_t)b * 5 * (N + 1) : nullptr, &it);
             if (status) status[b] = st;
             if (iters) iters[b] = it;
+        });
+    }
+
+    // mpc_evaluate_batch on host buffers (the device entry's argument contract); rows are [B][N][7 + p.max_obs]
+    void evaluate_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                        const double* U, double* Xpred, double* summary, double* terms, double* rows) const {
+        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
+        parallel(p, B, [&](Worker& w, int b) {
+            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
+            no = no < 0 ? 0 : (no > mo ? mo : no);
+            double X[kMaxN + 1][5];
+            const double* Ub = U + (size_t)b * 2 * N;
+            w.predict(x0 + 5 * (size_t)b, Ub, X);
+            if (Xpred) std::memcpy(Xpred + (size_t)b * 5 * (N + 1), X, sizeof(double) * 5 * (N + 1));
+            if (summary || terms || rows)
+                evaluate_one(*ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
+                             summary ? summary + (size_t)b * MPC_EV_NQ : nullptr,
+                             terms ? terms + 5 * (size_t)b : nullptr,
+                             rows ? rows + (size_t)b * N * rw : nullptr);
         });
     }
 

@@ -25,6 +25,7 @@
 //   traffic_kernels.h      the traffic scripts' FSM / gather kernels (up to 16 actors per ego)
 //   convoy_kernels.h       the convoys' leader-ranking kernel (a workgroup per world)
 //   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
+//   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points) and, last, the comm layer (comm.h).
 #include <hip/hip_runtime.h>
@@ -48,6 +49,7 @@
 #include "traffic_kernels.h"
 #include "convoy_kernels.h"
 #include "noise_kernels.h"
+#include "evaluate_kernel.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -96,6 +98,9 @@ struct mpc_ctx {
     int *nobs, *status, *iters;
     double *ls, *lst, *lct;
     size_t cap_lookup;
+    // mpc_evaluate_batch's output staging (summary, terms, rows), grown on demand
+    double* ev;
+    size_t cap_ev;      // doubles
     hipStream_t stream;
     // work list of the two-phase launch: wl[0], wl[1] = counts of the eager calls (alternating), wl[2] = count
     // of a call captured into a graph, wl[3..cap_wl + 2] = deferred instance ids
@@ -334,6 +339,7 @@ extern "C" void mpc_destroy(mpc_ctx* c) {
     hipStreamSynchronize(c->stream);
     free_staging(c);
     hipFree(c->ls); hipFree(c->lst); hipFree(c->lct);
+    hipFree(c->ev);
     if (c->wl) hipEventDestroy(c->wl_done);
     hipFree(c->wl);
     hipFree(c->stc);
@@ -491,6 +497,24 @@ static int grow(T** ptr, size_t n) {
     return hipMalloc(ptr, n * sizeof(T)) == hipSuccess ? 0 : -1;
 }
 
+// the host entries' staging buffers for a batch of B instances, horizon N and slab width mo (grow only)
+static int ensure_staging(mpc_ctx* c, int B, int N, int mo) {
+    if ((size_t)B > c->cap_B || N > c->cap_N || mo > c->cap_obs) {
+        size_t nb = (size_t)B > c->cap_B ? (size_t)B : c->cap_B;
+        int nn = N > c->cap_N ? N : c->cap_N;
+        int no = mo > c->cap_obs ? mo : c->cap_obs;
+        free_staging(c);
+        if (grow(&c->x0, nb * 5) || grow(&c->obs, nb * (no > 0 ? no : 1) * 2) || grow(&c->ub, nb * 2 * nn) ||
+            grow(&c->u0, nb * 2) || grow(&c->U, nb * 2 * nn) || grow(&c->X, nb * 5 * (nn + 1)) ||
+            grow(&c->nobs, nb) || grow(&c->status, nb) || grow(&c->iters, nb))
+            return fail(MPC_E_ALLOC, "hipMalloc staging");
+        c->cap_B = nb;
+        c->cap_N = nn;
+        c->cap_obs = no;
+    }
+    return MPC_SUCCESS;
+}
+
 extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                const double* ubar, double* u0, double* U, double* Xpred, int* status, int* iters) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
@@ -506,19 +530,8 @@ extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double
             c->cpu->solve_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, ubar, u0, U, Xpred, status, iters);
         });
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    if ((size_t)B > c->cap_B || N > c->cap_N || mo > c->cap_obs) {
-        size_t nb = (size_t)B > c->cap_B ? (size_t)B : c->cap_B;
-        int nn = N > c->cap_N ? N : c->cap_N;
-        int no = mo > c->cap_obs ? mo : c->cap_obs;
-        free_staging(c);
-        if (grow(&c->x0, nb * 5) || grow(&c->obs, nb * (no > 0 ? no : 1) * 2) || grow(&c->ub, nb * 2 * nn) ||
-            grow(&c->u0, nb * 2) || grow(&c->U, nb * 2 * nn) || grow(&c->X, nb * 5 * (nn + 1)) ||
-            grow(&c->nobs, nb) || grow(&c->status, nb) || grow(&c->iters, nb))
-            return fail(MPC_E_ALLOC, "hipMalloc staging");
-        c->cap_B = nb;
-        c->cap_N = nn;
-        c->cap_obs = no;
-    }
+    rc = ensure_staging(c, B, N, mo);
+    if (rc) return rc;
     hipStream_t s = c->stream;
     HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
     const bool use_obs = mo > 0 && obs;
@@ -536,6 +549,93 @@ extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double
         HIPCHK(hipMemcpyAsync(Xpred, c->X, sizeof(double) * 5 * (N + 1) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     if (status) HIPCHK(hipMemcpyAsync(status, c->status, sizeof(int) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     if (iters) HIPCHK(hipMemcpyAsync(iters, c->iters, sizeof(int) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
+    return MPC_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------
+// batched evaluator (evaluate_kernel.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                         const double* U, double* Xpred, double* summary, double* terms,
+                                         double* rows, void* stream) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(MPC_E_ARG, "B < 0");
+    if (B == 0) return MPC_SUCCESS;
+    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
+    if (!U) return fail(MPC_E_ARG, "U is NULL (the evaluator needs the control sequence to evaluate)");
+    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
+    if (obs && c->p.max_obs == 0)
+        return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
+    int rc = check_params(&c->p);
+    if (rc) return rc;
+    if (((uintptr_t)x0 | (uintptr_t)obs | (uintptr_t)U | (uintptr_t)Xpred | (uintptr_t)summary | (uintptr_t)terms |
+         (uintptr_t)rows) & 7)
+        return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); });
+    KParams kp = kparams(&c->p);
+    const int rw = 7 + c->p.max_obs;       // the row width keeps the context's slab width without obstacles too
+    if (!obs) kp.max_obs = 0;
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const int GL = kp.N + 1 <= 16 ? 16 : (kp.N + 1 <= 32 ? 32 : 64);     // launch_solve's rule
+    const dim3 grid((B + WAVE / GL - 1) / (WAVE / GL));
+    hipStream_t st = (hipStream_t)stream;
+#define MPC_EV_LAUNCH(GLV, OBSV)                                                                              \
+    hipLaunchKernelGGL((mpc_evaluate_kernel<GLV, OBSV>), grid, dim3(WAVE), 0, st, c->tab, kp, B, rw, x0, obs, \
+                       obs ? n_obs : nullptr, U, Xpred, summary, terms, rows)
+    if (GL == 16) { if (obs) MPC_EV_LAUNCH(16, true); else MPC_EV_LAUNCH(16, false); }
+    else if (GL == 32) { if (obs) MPC_EV_LAUNCH(32, true); else MPC_EV_LAUNCH(32, false); }
+    else { if (obs) MPC_EV_LAUNCH(64, true); else MPC_EV_LAUNCH(64, false); }
+#undef MPC_EV_LAUNCH
+    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                  const double* U, double* Xpred, double* summary, double* terms, double* rows) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(MPC_E_ARG, "B < 0");
+    if (B == 0) return MPC_SUCCESS;
+    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
+    if (!U) return fail(MPC_E_ARG, "U is NULL (the evaluator needs the control sequence to evaluate)");
+    int rc = check_params(&c->p);
+    if (rc) return rc;
+    const int N = c->p.N, mo = c->p.max_obs, rw = 7 + mo;
+    if (obs && mo == 0) return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
+    if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->evaluate_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, U, Xpred, summary, terms, rows);
+        });
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    rc = ensure_staging(c, B, N, mo);
+    if (rc) return rc;
+    const size_t n_sum = (size_t)B * MPC_EV_NQ, n_terms = (size_t)B * 5, n_rows = (size_t)B * N * rw;
+    if (n_sum + n_terms + n_rows > c->cap_ev) {
+        c->cap_ev = 0;
+        if (grow(&c->ev, n_sum + n_terms + n_rows)) return fail(MPC_E_ALLOC, "hipMalloc evaluator staging");
+        c->cap_ev = n_sum + n_terms + n_rows;
+    }
+    double *d_sum = c->ev, *d_terms = c->ev + n_sum, *d_rows = c->ev + n_sum + n_terms;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    const bool use_obs = obs != nullptr;
+    if (use_obs) {
+        HIPCHK(hipMemcpyAsync(c->obs, obs, sizeof(double) * 2 * mo * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+        if (n_obs) HIPCHK(hipMemcpyAsync(c->nobs, n_obs, sizeof(int) * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    }
+    HIPCHK(hipMemcpyAsync(c->ub, U, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    rc = mpc_evaluate_batch_device(c, B, c->x0, use_obs ? c->obs : nullptr, use_obs && n_obs ? c->nobs : nullptr,
+                                   c->ub, Xpred ? c->X : nullptr, summary ? d_sum : nullptr,
+                                   terms ? d_terms : nullptr, rows ? d_rows : nullptr, (void*)s);
+    if (rc) return rc;
+    if (Xpred)
+        HIPCHK(hipMemcpyAsync(Xpred, c->X, sizeof(double) * 5 * (N + 1) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, sizeof(double) * n_sum, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (terms) HIPCHK(hipMemcpyAsync(terms, d_terms, sizeof(double) * n_terms, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (rows) HIPCHK(hipMemcpyAsync(rows, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
     return MPC_SUCCESS;
 }

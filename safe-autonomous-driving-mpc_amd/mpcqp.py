@@ -67,7 +67,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_noise_draw", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -93,6 +93,11 @@ NZ_CH_MEAS, NZ_CH_ACT, NZ_CH_PROC, NZ_CH_PERC, NZ_CHANNELS = 0, 5, 7, 16, 48
 NZX_U1A_MIN, NZX_U1A_MAX, NZX_U2A_MIN, NZX_U2A_MAX, NZX_N_CLAMPED = 6, 7, 8, 9, 10
 NZ_NX = 11
 NZX_FIELDS = CVX_FIELDS + ("u1a_min", "u1a_max", "u2a_min", "u2a_max", "n_clamped")
+# mpc_evaluate_batch: the columns of its per-instance summary (MPC_EVQ_*)
+EVQ_COST, EVQ_MIN_ROW, EVQ_ARGMIN_STAGE, EVQ_ARGMIN_KIND, EVQ_L1, EVQ_N_NEG = 0, 1, 2, 3, 4, 5
+EVQ_MIN_LANE, EVQ_MIN_OBS, EVQ_MIN_V, EVQ_BOX = 6, 7, 8, 9
+EV_NQ = 10
+EVQ_FIELDS = ("cost", "min_row", "argmin_stage", "argmin_kind", "l1", "n_neg", "min_lane", "min_obs", "min_v", "box")
 
 _lib = None
 
@@ -113,6 +118,10 @@ def lib():
     L.mpc_solve_batch_device.restype = C.c_int
     L.mpc_solve_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mpc_evaluate_batch.restype = C.c_int
+    L.mpc_evaluate_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]
+    L.mpc_evaluate_batch_device.restype = C.c_int
+    L.mpc_evaluate_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
     L.mpc_lookup.restype = C.c_int
     L.mpc_lookup.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.mpc_set_params.restype = C.c_int
@@ -333,6 +342,41 @@ class Solver:
         """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr())."""
         _check(lib().mpc_solve_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, ubar_ptr, u0_ptr, U_ptr,
                                             X_ptr, st_ptr, it_ptr, C.c_void_p(stream)), "mpc_solve_batch_device")
+
+    def evaluate_batch(self, x0, U, obs=None, n_obs=None, rows=False):
+        """mpc_evaluate_batch: the reference's measures of ANY control sequences U [B,N,2] from x0 [B,5] (obs, n_obs
+        as in solve_batch).  Returns dict(Xpred [B,N+1,5] = predict(x0, U), summary [B,10] (columns EVQ_FIELDS:
+        cost, min / argmin of the constraint rows, L1 violation, negative rows, minima per row family, box
+        excess), terms [B,5] (cost shares d, o, v, u1, u2)) and, with rows=True, rows [B,N,7+max_obs] (columns:
+        six lane rows, v, the obstacles, NaN past n_obs; constraint_rows() gives the reference's vector)."""
+        p = self.params
+        N, mo = p.N, p.max_obs
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        if U is None:
+            raise ValueError("U is required: the control sequences to evaluate")
+        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
+        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
+            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
+        if obs is not None and mo > 0:
+            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
+            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
+        else:
+            obs, n_obs = None, None
+        X = np.empty((B, N + 1, 5)); summary = np.empty((B, EV_NQ)); terms = np.empty((B, 5))
+        R = np.empty((B, N, 7 + mo)) if rows else None
+        _check(lib().mpc_evaluate_batch(self.h, B, _p(x0), _p(obs), _pi(n_obs), _p(U), _p(X), _p(summary), _p(terms),
+                                        _p(R)), "mpc_evaluate_batch")
+        out = dict(Xpred=X, summary=summary, terms=terms)
+        if rows:
+            out["rows"] = R
+        return out
+
+    def evaluate_batch_device(self, B, x0_ptr, obs_ptr, nobs_ptr, U_ptr, X_ptr, summary_ptr, terms_ptr, rows_ptr,
+                              stream=0):
+        """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr(); 0 / None = NULL)."""
+        _check(lib().mpc_evaluate_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, X_ptr, summary_ptr,
+                                               terms_ptr, rows_ptr, C.c_void_p(stream)), "mpc_evaluate_batch_device")
 
     def closed_loop(self, x_init, fsm=None, max_steps=1000, s_stop=None, s_max=None):
         """Batched run_simulation (trajectory_tracking.py:377-443) on the device.

@@ -191,6 +191,57 @@ class TrajectoryTracker:
         slv = self.solver(max_obs=0 if obs is None else obs.shape[1])
         return slv.solve_batch(x0, obs, n, ubar)
 
+    def evaluate_batch(self, x0, U, obstacles=None):
+        """cost(U, x0), the rows of constraints(x0, obstacles) and predict(x0, U) for a batch, on the library
+        (mpc_evaluate_batch): x0 [B,5], U [B,N,2] any control sequences; obstacles as in solve_batch.  Returns
+        mpcqp.Solver.evaluate_batch's dict with rows, plus 'n_obs' [B]; constraint_rows(r, b) is instance b's
+        vector in the reference's order."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        obs, n = _obstacle_slab(B, obstacles)
+        slv = self.solver(max_obs=0 if obs is None else obs.shape[1])
+        r = slv.evaluate_batch(x0, U, obs, n, rows=True)
+        r["n_obs"] = np.zeros(B, np.int32) if n is None else n
+        return r
+
+
+def _obstacle_slab(B, obstacles):
+    """(obs [B,M,2], n_obs [B]) of solve_batch's obstacle forms: None, an array [B,M,2], or a list (len B) of
+    obstacle lists; (None, None) when there is no obstacle at all."""
+    if obstacles is None:
+        return None, None
+    if isinstance(obstacles, np.ndarray):
+        obs = np.asarray(obstacles, np.float64).reshape(B, -1, 2)
+        return (obs, np.full(B, obs.shape[1], np.int32)) if obs.shape[1] else (None, None)
+    mo = max((len(o) for o in obstacles), default=0)
+    if not mo:
+        return None, None
+    obs = np.zeros((B, mo, 2))
+    n = np.zeros(B, np.int32)
+    for b, lst in enumerate(obstacles):
+        n[b] = len(lst)
+        for i, o in enumerate(lst):
+            obs[b, i] = (o["s"], o["v"])
+    return obs, n
+
+
+def constraint_rows(result_or_rows, b=0, n_obs=None):
+    """The reference-order constraint vector of one instance (constraints(x0, obstacles)['fun'](U),
+    trajectory_tracking.py:155-211: per stage the six lane rows, one row per obstacle, then v) from
+    evaluate_batch's rows.  result_or_rows: the dict evaluate_batch returned (instance b, n_obs from its 'n_obs'
+    unless given), or a rows array [B,N,7+M] / [N,7+M]; without n_obs the obstacle columns that are not NaN in
+    the first stage are taken."""
+    if isinstance(result_or_rows, dict):
+        R = np.asarray(result_or_rows["rows"])[b]
+        if n_obs is None and "n_obs" in result_or_rows:
+            n_obs = int(np.asarray(result_or_rows["n_obs"])[b])
+    else:
+        R = np.asarray(result_or_rows, np.float64)
+        R = R[b] if R.ndim == 3 else R
+    if n_obs is None:
+        n_obs = int(np.sum(~np.isnan(R[0, 7:])))
+    return np.concatenate([R[:, :6], R[:, 7:7 + int(n_obs)], R[:, 6:7]], axis=1).ravel()
+
 
 # ---------------------------------------------------------------------------------------------
 # obstacle scenario state machine (trajectory_tracking.py:266-374)

@@ -50,6 +50,12 @@ def solver_kernel_key(name):
     return tuple(int(x) for x in m.groups()) if m else None
 
 
+def evaluate_kernel_key(name):
+    """(GL, OBS) of a mangled mpc_evaluate_kernel<GL, OBS> name, else None."""
+    m = re.search(r"mpc_evaluate_kernelILi(\d+)ELb([01])E", name)
+    return tuple(int(x) for x in m.groups()) if m else None
+
+
 if __name__ == "__main__":
     so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "safe-autonomous-driving-mpc_amd", "libmpcqp.so")
     print(json.dumps(kernel_resources(so), indent=1))
