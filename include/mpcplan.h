@@ -83,7 +83,8 @@ void plan_default_params(plan_params* p);
  * IEEE double on std::thread workers (PLAN_CPU_THREADS, default every hardware thread), no HIP call; it serves
  * plan_solve_chunks, plan_optimize (the chunk loop on the CPU, one plan per worker), plan_route_eval,
  * plan_set_params and plan_destroy, and the device-pointer entries (plan_solve_chunks_device,
- * plan_optimize_device, plan_chunks_per_cu) fail on it with PLAN_E_DEVICE.  The reference's planner is CPU
+ * plan_optimize_device, plan_chunks_per_cu) fail on it with PLAN_E_DEVICE; the evaluator's entries all work on it
+ * (plan_evaluate_chunks_device takes host pointers there, mpcplan_evaluate.h).  The reference's planner is CPU
  * code (scipy SLSQP, :381-387); this is the library's CPU path behind the same entries. */
 int plan_create(const double* s, int M, const double* cx, const double* cy, const double* vmax,
                 const plan_params* p, int device, plan_ctx** out);
@@ -151,6 +152,10 @@ int plan_optimize(plan_ctx* c, int B, int Nmax, const double* starts, double max
 /* Route functions, for tests: kappa(s) and dkappa/ds (k_ref_fun, :445-459), v_max(s); on the device, or on the
  * CPU for a host context. */
 int plan_route_eval(plan_ctx* c, int n, const double* s, double* kappa, double* dkappa, double* vmax);
+
+/* The evaluator (plan_evaluate_chunks, plan_evaluate_chunks_device, plan_check_verdicts: the reference NLP's cost,
+ * defects and rows at any given z, no solve) is declared in the companion header include/mpcplan_evaluate.h; the
+ * same library exports it and callers detect it by the presence of the symbols. */
 
 int plan_set_params(plan_ctx* c, const plan_params* p);
 const char* plan_last_error(void);   /* thread-local */

@@ -31,8 +31,11 @@
 
 
 #include "../../include/mpcplan.h"
+#include "../../include/mpcplan_evaluate.h"
 #include "plan_kernel.h"
+#include "plan_evaluate_kernel.h"
 #include "plan_host.h"
+#include "plan_evaluate_host.h"
 
 namespace {
 
@@ -493,6 +496,134 @@ int plan_optimize(plan_ctx* c, int B, int Nmax, const double* starts, double max
                     hipMemcpy(sqp, d_sqp, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
                     hipMemcpy(nchunks, d_nch, sizeof(int) * B, hipMemcpyDeviceToHost) == hipSuccess;
     if (!ok) return fail(PLAN_E_DEVICE, "output download failed");
+    return PLAN_SUCCESS;
+}
+
+// ---- the evaluator (plan_evaluate_kernel.h; host backend: plan_evaluate_host.h) ----
+static int evaluate_args(plan_ctx* c, int B, int Nmax, const int* N, const double* x0, const double* s_target,
+                         const double* X, const double* U) {
+    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
+    if (B == 0) return PLAN_SUCCESS;
+    if (!x0 || !s_target || !X || !U) return fail(PLAN_E_ARG, "plan_evaluate_chunks: x0, s_target, X and U are required");
+    if (Nmax < 1) return fail(PLAN_E_ARG, "Nmax must be >= 1");
+    if ((size_t)Nmax > ((size_t)1 << 26)) return fail(PLAN_E_ARG, "Nmax too large");
+    if (!N && Nmax < c->p.N) return fail(PLAN_E_ARG, "Nmax must be >= params N when N is NULL (Nmax is the row stride)");
+    return PLAN_SUCCESS;
+}
+
+int plan_evaluate_chunks_device(plan_ctx* c, int B, int Nmax, const int* N, const double* x0, const double* s_target,
+                                const int* is_final, const double* X, const double* U, const double* S, double* summary,
+                                double* defects, double* rows, void* stream) {
+    if (int rc = evaluate_args(c, B, Nmax, N, x0, s_target, X, U)) return rc;
+    if (B == 0 || (!summary && !defects && !rows)) return PLAN_SUCCESS;
+    if (c->host) {
+        // the host backend: host pointers, synchronous (include/mpcplan_evaluate.h documents the exception)
+        plan_host::evaluate_batch(c->host, &c->p, B, Nmax, N, x0, s_target, is_final, X, U, S, summary, defects, rows,
+                                  c->host_threads);
+        return PLAN_SUCCESS;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
+    EArgs a;
+    a.R = c->R;
+    a.P = c->p;
+    a.B = B;
+    a.Nmax = Nmax;
+    a.Nfixed = c->p.N;
+    a.N = N;
+    a.x0 = x0;
+    a.st = s_target;
+    a.fin = is_final;
+    a.X = X;
+    a.U = U;
+    a.S = S;
+    a.sum = summary;
+    a.def = defects;
+    a.rows = rows;
+    hipLaunchKernelGGL(plan_evaluate_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return fail(PLAN_E_LAUNCH, std::string("plan evaluate kernel launch failed: ") + hipGetErrorString(e));
+    return PLAN_SUCCESS;
+}
+
+int plan_evaluate_chunks(plan_ctx* c, int B, int Nmax, const int* N, const double* x0, const double* s_target,
+                         const int* is_final, const double* X, const double* U, const double* S, double* summary,
+                         double* defects, double* rows) {
+    if (int rc = evaluate_args(c, B, Nmax, N, x0, s_target, X, U)) return rc;
+    if (B == 0 || (!summary && !defects && !rows)) return PLAN_SUCCESS;
+    if (c->host)
+        return plan_evaluate_chunks_device(c, B, Nmax, N, x0, s_target, is_final, X, U, S, summary, defects, rows, nullptr);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
+    const size_t nX = (size_t)B * (Nmax + 1) * 5, nU = (size_t)B * Nmax * 2, nS = (size_t)B * Nmax;
+    const size_t nQ = (size_t)B * PLAN_EV_NQ, nD = (size_t)B * Nmax * 5, nR = (size_t)B * (Nmax + 1) * PLAN_EV_NR;
+    const size_t bytes = sizeof(double) * (5 * (size_t)B + B + nX + nU + nS + nQ + nD + nR) + sizeof(int) * (2 * (size_t)B);
+    if (bytes > c->io_bytes) {
+        if (c->io) (void)hipFree(c->io);
+        c->io = nullptr;
+        c->io_bytes = 0;
+        if (hipMalloc(&c->io, bytes) != hipSuccess) return fail(PLAN_E_ALLOC, "staging allocation failed");
+        c->io_bytes = bytes;
+    }
+    double* d_x0 = (double*)c->io;
+    double* d_st = d_x0 + 5 * (size_t)B;
+    double* d_X = d_st + B;
+    double* d_U = d_X + nX;
+    double* d_S = d_U + nU;
+    double* d_Q = d_S + nS;
+    double* d_D = d_Q + nQ;
+    double* d_R = d_D + nD;
+    int* d_N = (int*)(d_R + nR);
+    int* d_fin = d_N + B;
+    bool ok = hipMemcpy(d_x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_st, s_target, sizeof(double) * B, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_X, X, sizeof(double) * nX, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_U, U, sizeof(double) * nU, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && S) ok = hipMemcpy(d_S, S, sizeof(double) * nS, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && N) ok = hipMemcpy(d_N, N, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && is_final) ok = hipMemcpy(d_fin, is_final, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) return fail(PLAN_E_DEVICE, "input upload failed");
+    int rc = plan_evaluate_chunks_device(c, B, Nmax, N ? d_N : nullptr, d_x0, d_st, is_final ? d_fin : nullptr, d_X, d_U,
+                                         S ? d_S : nullptr, summary ? d_Q : nullptr, defects ? d_D : nullptr,
+                                         rows ? d_R : nullptr, nullptr);
+    if (rc != PLAN_SUCCESS) return rc;
+    if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
+        return fail(PLAN_E_DEVICE, std::string("plan evaluate kernel failed: ") + hipGetErrorString(e));
+    // a chunk whose N[b] is out of range leaves its rows and defects unwritten on the device; the caller's buffers
+    // keep their contents there, as with device pointers
+    bool all_in = true;
+    for (int b = 0; b < B && N && all_in; ++b) all_in = N[b] >= 1 && N[b] <= Nmax;
+    ok = true;
+    if (all_in) {
+        if (defects) ok = hipMemcpy(defects, d_D, sizeof(double) * nD, hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && rows) ok = hipMemcpy(rows, d_R, sizeof(double) * nR, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    for (int b = 0; b < B && ok && !all_in; ++b) {
+        const int n = N[b];
+        if (n < 1 || n > Nmax) continue;
+        if (defects)
+            ok = hipMemcpy(defects + (size_t)b * Nmax * 5, d_D + (size_t)b * Nmax * 5, sizeof(double) * Nmax * 5,
+                           hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && rows)
+            ok = hipMemcpy(rows + (size_t)b * (Nmax + 1) * PLAN_EV_NR, d_R + (size_t)b * (Nmax + 1) * PLAN_EV_NR,
+                           sizeof(double) * (Nmax + 1) * PLAN_EV_NR, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (ok && summary) ok = hipMemcpy(summary, d_Q, sizeof(double) * nQ, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail(PLAN_E_DEVICE, "output download failed");
+    return PLAN_SUCCESS;
+}
+
+int plan_check_verdicts(const plan_ctx* c, int B, const double* summary, int* verdicts, int counts[8]) {
+    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
+    if (B > 0 && !summary) return fail(PLAN_E_ARG, "summary is NULL");
+    if (counts)
+        for (int k = 0; k < 8; ++k) counts[k] = 0;
+    for (int b = 0; b < B; ++b) {
+        const int v = plan_host::check_verdict(&c->p, summary + (size_t)b * PLAN_EV_NQ);
+        if (verdicts) verdicts[b] = v;
+        if (counts)
+            for (int k = 0; k < 8; ++k) counts[k] += (v >> k) & 1;
+    }
     return PLAN_SUCCESS;
 }
 

@@ -34,6 +34,21 @@ class PlanError(RuntimeError):
 
 EXPORTS = ["plan_default_params", "plan_create", "plan_solve_chunks", "plan_solve_chunks_device", "plan_optimize_device",
            "plan_optimize", "plan_route_eval", "plan_chunks_per_cu", "plan_set_params", "plan_last_error", "plan_version", "plan_destroy"]
+# the entry points of the companion header include/mpcplan_evaluate.h (the same library)
+EVALUATE_EXPORTS = ["plan_evaluate_chunks", "plan_evaluate_chunks_device", "plan_check_verdicts"]
+
+# the evaluator (include/mpcplan_evaluate.h): rows' columns PLAN_EVR_*, summary columns PLAN_EVQ_*, verdict bits PLAN_CHKB_*
+PLAN_EV_NR = 12
+EV_ROW_NAMES = ("vmin", "vmax", "latp", "latm", "kmin", "kmax", "u1min", "u1max", "u2min", "u2max", "slack", "sterm")
+EV_SUMMARY_NAMES = ("cost", "max_defect", "l1_eq", "x0_res", "term_s", "term_v", "min_row", "argmin_stage", "argmin_kind",
+                    "l1_ineq", "n_neg", "s_final", "s_total", "v_final", "min_v", "max_abs_d", "max_abs_slack", "u1_min",
+                    "u1_max", "u2_min", "u2_max")
+PLAN_EV_NQ = len(EV_SUMMARY_NAMES)
+EVQ = {n: i for i, n in enumerate(EV_SUMMARY_NAMES)}
+CHECK_NAMES = ("destination", "full_stop", "forward", "u1_ok", "u2_ok", "lateral_ok", "slack_ok", "passed")
+PLAN_EV_LDS_BYTES = 3584
+PLAN_CHK_DISTANCE_TOL, PLAN_CHK_VELOCITY_TOL, PLAN_CHK_CONTROLS_TOL = 0.5, 0.1, 0.1
+PLAN_CHK_LATERAL_DEV_TOL, PLAN_CHK_SLACK_TOL = 1.5, 0.1
 
 _lib = None
 
@@ -63,6 +78,12 @@ def lib():
     L.plan_route_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     L.plan_chunks_per_cu.restype = C.c_int
     L.plan_chunks_per_cu.argtypes = [C.c_void_p, C.c_int, _ip]
+    L.plan_evaluate_chunks.restype = C.c_int
+    L.plan_evaluate_chunks.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip] + [_dp] * 6
+    L.plan_evaluate_chunks_device.restype = C.c_int
+    L.plan_evaluate_chunks_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
+    L.plan_check_verdicts.restype = C.c_int
+    L.plan_check_verdicts.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _ip]
     L.plan_set_params.restype = C.c_int
     L.plan_set_params.argtypes = [C.c_void_p, C.POINTER(PlanParams)]
     L.plan_last_error.restype = C.c_char_p
@@ -190,6 +211,68 @@ class Planner:
                                    *[_p(out[k]) for k in ("X", "U", "S")],
                                    *[_pi(out[k]) for k in ("N", "is_final", "status", "iters", "sqp", "nchunks")]),
                "plan_optimize")
+        return out
+
+    def evaluate_chunks(self, x0, s_target, is_final, X, U, S=None, N=None, Nmax=None,
+                        want=("summary", "defects", "rows")):
+        """plan_evaluate_chunks: the reference NLP's cost, defects and rows of B given chunk plans.  x0 [B,5],
+        s_target [B], is_final [B] (scalar, or None: all intermediate), X [B,Nmax+1,5], U [B,Nmax,2], S [B,Nmax] or
+        None (all zero), N [B] (scalar, or None: params.N; any 1..Nmax, not limited by PLAN_MAX_N).  Nmax defaults to
+        X's row count - 1.  Returns a dict with the arrays named in `want`: summary [B,PLAN_EV_NQ] (columns
+        EV_SUMMARY_NAMES), defects [B,Nmax,5], rows [B,Nmax+1,12] (columns EV_ROW_NAMES).  Entries the library
+        does not write (a chunk with N out of range) are NaN."""
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        X = np.ascontiguousarray(X, np.float64)
+        X = X.reshape(B, -1, 5) if B else X.reshape(0, 1, 5)
+        Nm = int(X.shape[1] - 1 if Nmax is None else Nmax)
+        if X.shape[1] != Nm + 1:
+            raise PlanError(f"X must be [B, Nmax+1, 5] with Nmax = {Nm}")
+        U = np.ascontiguousarray(U, np.float64).reshape(B, -1, 2) if B else np.zeros((0, Nm, 2))
+        if U.shape[1] != Nm:
+            raise PlanError(f"U must be [B, Nmax, 2] with Nmax = {Nm}")
+        if S is not None:
+            S = np.ascontiguousarray(S, np.float64).reshape(B, -1) if B else np.zeros((0, Nm))
+            if S.shape[1] != Nm:
+                raise PlanError(f"S must be [B, Nmax] with Nmax = {Nm}")
+        st = np.ascontiguousarray(np.broadcast_to(np.asarray(s_target, np.float64), (B,)))
+        fin = None if is_final is None else np.ascontiguousarray(np.broadcast_to(np.asarray(is_final, np.int32), (B,)))
+        Nv = None if N is None else np.ascontiguousarray(np.broadcast_to(np.asarray(N, np.int32), (B,)))
+        unknown = set(want) - {"summary", "defects", "rows"}
+        if unknown:
+            raise PlanError(f"unknown outputs {sorted(unknown)}")
+        out = {}
+        if "summary" in want:
+            out["summary"] = np.full((B, PLAN_EV_NQ), np.nan)
+        if "defects" in want:
+            out["defects"] = np.full((B, Nm, 5), np.nan)
+        if "rows" in want:
+            out["rows"] = np.full((B, Nm + 1, PLAN_EV_NR), np.nan)
+        _check(lib().plan_evaluate_chunks(self.h, B, Nm, _pi(Nv), _p(x0), _p(st), _pi(fin), _p(X), _p(U), _p(S),
+                                          _p(out.get("summary")), _p(out.get("defects")), _p(out.get("rows"))),
+               "plan_evaluate_chunks")
+        return out
+
+    def evaluate_chunks_device(self, B, Nmax, N_ptr, x0_ptr, st_ptr, fin_ptr, X_ptr, U_ptr, S_ptr, summary_ptr,
+                               defects_ptr, rows_ptr, stream=0):
+        """plan_evaluate_chunks_device: raw device addresses (0 = NULL), asynchronous on `stream`.  On a host
+        context (device = -1) the addresses are host addresses and the call is synchronous."""
+        _check(lib().plan_evaluate_chunks_device(self.h, int(B), int(Nmax), N_ptr or None, x0_ptr or None, st_ptr or None,
+                                                 fin_ptr or None, X_ptr or None, U_ptr or None, S_ptr or None,
+                                                 summary_ptr or None, defects_ptr or None, rows_ptr or None,
+                                                 C.c_void_p(stream)), "plan_evaluate_chunks_device")
+
+    def check_verdicts(self, summary):
+        """plan_check_verdicts: sanity_checks.plan_check_summary's verdicts from summary rows [B,PLAN_EV_NQ].
+        Returns dict(verdicts [B] int32 bit masks (bit k = CHECK_NAMES[k]), counts [8], and one bool array [B] per
+        name of CHECK_NAMES)."""
+        q = np.ascontiguousarray(summary, np.float64).reshape(-1, PLAN_EV_NQ)
+        v = np.zeros(q.shape[0], np.int32)
+        cnt = np.zeros(8, np.int32)
+        _check(lib().plan_check_verdicts(self.h, q.shape[0], _p(q), _pi(v), _pi(cnt)), "plan_check_verdicts")
+        out = dict(verdicts=v, counts=cnt)
+        for k, n in enumerate(CHECK_NAMES):
+            out[n] = ((v >> k) & 1).astype(bool)
         return out
 
     def route_eval(self, s):

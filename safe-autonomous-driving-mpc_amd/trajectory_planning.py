@@ -231,6 +231,31 @@ def release_planners():
             _PLANNERS.popitem()[1].close()
 
 
+def evaluate_plan(route, X, U, S=None, device=0, params=None):
+    """A whole committed trajectory (X [n+1,5], U [n,2], S [n] or None: zero slacks) on the reference NLP's own
+    scale, through libmpcplan's evaluator (plan_evaluate_chunks) as ONE final chunk of n intervals with x0 = X[0]
+    and s_target = the route's s_total: the cost, the largest Hermite-Simpson defect, the most violated row and the
+    quantities and verdicts of sanity_checks.reference_trajectory_check.  Returns a dict: the summary columns by name
+    (mpcplan.EV_SUMMARY_NAMES) plus the verdict bits by name (mpcplan.CHECK_NAMES, bools).  device = -1: on the CPU."""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 5)
+    n = X.shape[0] - 1
+    U = np.ascontiguousarray(U, np.float64).reshape(-1, 2)[:n]
+    if n < 1 or U.shape[0] != n:
+        raise ValueError("evaluate_plan needs X [n+1, 5] and U [n, 2] with n >= 1")
+    if S is not None:
+        S = np.ascontiguousarray(S, np.float64).ravel()[:n]
+    pl = mpcplan.Planner(route, params, device=device)
+    try:
+        q = pl.evaluate_chunks(X[0], route.s_total, 1, X[None], U[None], None if S is None else S[None], N=n,
+                               want=("summary",))["summary"]
+        v = pl.check_verdicts(q)
+    finally:
+        pl.close()
+    out = {name: float(q[0, i]) for i, name in enumerate(mpcplan.EV_SUMMARY_NAMES)}
+    out.update({name: bool(v[name][0]) for name in mpcplan.CHECK_NAMES})
+    return out
+
+
 def optimize_full_trajectory(route, max_chunk_size=20, max_chunks=10000, device=0, verbose=False, check=True,
                              solve_chunk=None):
     """The chunked receding-horizon planner of trajectory_planning.py:419-559 on a routes.Route (or the

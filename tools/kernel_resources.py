@@ -56,6 +56,11 @@ def evaluate_kernel_key(name):
     return tuple(int(x) for x in m.groups()) if m else None
 
 
+def plan_evaluate_kernel_key(name):
+    """True for the mangled name of libmpcplan.so's plan_evaluate_kernel (one instantiation), else None."""
+    return True if re.search(r"^_Z\d+plan_evaluate_kernel", name) else None
+
+
 if __name__ == "__main__":
     so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "safe-autonomous-driving-mpc_amd", "libmpcqp.so")
     print(json.dumps(kernel_resources(so), indent=1))
