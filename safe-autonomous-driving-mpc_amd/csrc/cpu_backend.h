@@ -1087,6 +1087,208 @@ inline void evaluate_one(const Ref& R, const mpc_params& p, const double (*X)[5]
         for (int a = 0; a < 5; ++a) terms[a] = t[a];
 }
 
+// ---------------------------------------------------------------------------------------------
+// shared pieces of the closed-loop members of Backend
+// ---------------------------------------------------------------------------------------------
+// a history array before the loop: steps that never run stay NaN / -1
+template <typename T>
+inline void hist_prefill(T* h, size_t n, T v) {
+    if (h) std::fill(h, h + n, v);
+}
+
+// MPC_CLQ_MIN_OBS_DIST, the gap of check_quantities (hist_obs_s[i] - hist_x[i, 0]) over every car seen so far
+// with numpy's NaN rule; bit 0 of qflags: a gap was recorded.  min_actor, when given, takes `actor`, who is
+// behind a new minimum (-1: a leader)
+inline void loop_min_gap(double* q, int& qflags, double g, double* min_actor = nullptr, double actor = 0.0) {
+    if (!(qflags & 1)) {
+        qflags |= 1;
+    } else if (!(g < q[MPC_CLQ_MIN_OBS_DIST] || g != g)) {
+        return;
+    }
+    q[MPC_CLQ_MIN_OBS_DIST] = g;
+    if (min_actor) *min_actor = actor;
+}
+
+// What every closed-loop member keeps per ego, the outputs they share and the plant step.  quant is
+// [B][MPC_CL_NQ]; history rows exist for the egos with slot[b] >= 0 (row slot[b] of the [n_hist][...] arrays);
+// the histories and step_ms are optional.  The extremes take a NaN operand and keep it, like numpy's max / min
+struct LoopEgos {
+    const int B;
+    const size_t ns;
+    const double s_stop;
+    const int* const slot;
+    double* const quant;
+    double *const hist_x, *const hist_u;
+    int* const hist_status;
+    double* const step_ms;
+    std::vector<double> x, ms;
+    std::vector<int> qflags, active, nrun;
+
+    LoopEgos(int B_, const double* x_init, int max_steps, double s_stop_, double* quant_, int n_hist, const int* slot_,
+             double* hist_x_, double* hist_u_, int* hist_status_, double* step_ms_)
+        : B(B_), ns((size_t)max_steps), s_stop(s_stop_), slot(slot_), quant(quant_), hist_x(hist_x_), hist_u(hist_u_),
+          hist_status(hist_status_), step_ms(step_ms_), x(x_init, x_init + (size_t)B_ * 5), qflags((size_t)B_, 0),
+          active((size_t)B_), nrun((size_t)B_, 0) {
+        const size_t nh = (size_t)n_hist;
+        hist_prefill(hist_x, nh * (ns + 1) * 5, (double)NAN);
+        hist_prefill(hist_u, nh * ns * 2, (double)NAN);
+        hist_prefill(hist_status, nh * ns, -1);
+        hist_prefill(step_ms, ns, (double)NAN);
+        for (int b = 0; b < B; ++b) {
+            active[b] = x[5 * (size_t)b] <= s_stop;
+            if (hist_x && slot[b] >= 0)
+                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
+            double* q = quant + (size_t)b * MPC_CL_NQ;
+            std::fill(q, q + MPC_CL_NQ, 0.0);
+            q[MPC_CLQ_EGO] = (double)b;
+            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
+            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
+            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
+        }
+    }
+
+    // The plant step x + dt f(x, ua, k_ref(s)) (:403-406) of ego b with the applied control ua, then perturb(x)
+    // on the new state; the kept history rows and the plant-side quantities (u: the commanded control)
+    template <typename Perturb>
+    void plant(const Ref& ref, double dt, int b, int step, const double* u, const double* ua, int status,
+               Perturb perturb) {
+        double* xb = x.data() + 5 * (size_t)b;
+        double* q = quant + (size_t)b * MPC_CL_NQ;
+        double st[5];
+        ref.state(xb[0], st);
+        const double u1 = u[0], u2 = u[1];
+        const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), ua[0], ua[1]};
+        for (int j = 0; j < 5; ++j) xb[j] = xb[j] + dt * xd[j];
+        perturb(xb);
+        if (slot[b] >= 0) {
+            const size_t h = (size_t)slot[b];
+            if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
+            if (hist_u) {
+                hist_u[(h * ns + step) * 2] = u1;
+                hist_u[(h * ns + step) * 2 + 1] = u2;
+            }
+            if (hist_status) hist_status[h * ns + step] = status;
+        }
+        nrun[b] = step + 1;
+        q[MPC_CLQ_N_STEPS] = (double)(step + 1);
+        q[MPC_CLQ_S_FINAL] = xb[0];
+        const double ad = std::fabs(xb[1]);
+        if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
+        if (step == 0) {                             // every ego that runs at all runs step 0
+            q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
+            q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
+        } else {
+            if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
+            if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
+            if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
+            if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
+        }
+        const int code = status & MPC_STATUS_MASK;
+        if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
+        if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
+        if (!(xb[0] <= s_stop)) active[b] = 0;
+    }
+
+    // after the loop: MPC_CLQ_MAX_STEP_MS and the optional n_steps
+    void finish(int* n_steps) {
+        sweep_max_step_ms(B, nrun.data(), ms, quant);
+        if (n_steps) std::memcpy(n_steps, nrun.data(), (size_t)B * sizeof(int));
+    }
+};
+
+// ObstaclesFSM.update (:335-372) of one ego on its state before the step.  fl: car active, car triggered, light
+// green, waiting.  Writes the slab entries to o (the car first) and returns their number; car_s is the car's
+// position while it is on the road, else NaN
+inline int fsm_step(const mpc_fsm& F, double dt, double s, double v, int* fl, double& car, double& timer, double* o,
+                    double& car_s) {
+    int n = 0;
+    car_s = NAN;
+    if (F.dynamic_obstacle) {                        // :335-349
+        if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
+        if (fl[0]) {
+            car = car + F.obs_v * dt;
+            if (car > F.obs_end_s) {
+                fl[0] = 0;
+            } else {
+                o[0] = car;
+                o[1] = F.obs_v;
+                n = 1;
+                car_s = car;
+            }
+        }
+    }
+    if (F.traffic_light && !fl[2]) {                 // :351-372
+        const double dist = F.tl_pos - s;
+        if (0.0 < dist && dist < F.tl_trigger_s) {
+            o[2 * n] = F.tl_pos;
+            o[2 * n + 1] = 0.0;
+            ++n;
+            if (v < 0.1 && dist < 10.0) fl[3] = 1;
+        }
+        if (fl[3]) {
+            timer += dt;
+            if (timer >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
+        }
+    }
+    return n;
+}
+
+// One ego's script of A actors for one step: each actor runs ObstaclesFSM's per-obstacle transitions on its own
+// state (fl, val: a car's position, a light's timer), visited in index order; o takes what they emit and their
+// number is returned.  Updates the gap and red-pass quantities (q, e: the ego's quant and extra rows), green (bit
+// a: actor a is a GREEN light) and car_s (the first car on the road, else NaN)
+enum { ACT_CAR_ACTIVE = 1, ACT_CAR_TRIGGERED = 2, ACT_TL_GREEN = 4, ACT_TL_WAITING = 8, ACT_PASS_DECIDED = 16 };
+inline int script_step(const mpc_actor* sc, int A, double dt, double s, double v, int* fls, double* vals, double* o,
+                       double* q, double* e, int& qflags, int& green, double& car_s) {
+    int n = 0, have_car = 0;
+    green = 0;
+    car_s = NAN;
+    for (int a = 0; a < A; ++a) {
+        const mpc_actor& M = sc[a];
+        if (M.kind == MPC_ACTOR_NONE) continue;
+        int& fl = fls[a];
+        double& val = vals[a];
+        if (M.kind == MPC_ACTOR_CAR) {               // ObstaclesFSM.update, :335-349, this car's state
+            if (!(fl & ACT_CAR_TRIGGERED) && s >= M.trigger_s) fl |= ACT_CAR_TRIGGERED | ACT_CAR_ACTIVE;
+            if (fl & ACT_CAR_ACTIVE) {
+                val = val + M.v * dt;
+                if (val > M.end_s) {
+                    fl &= ~ACT_CAR_ACTIVE;
+                } else {
+                    o[2 * n] = val;
+                    o[2 * n + 1] = M.v;
+                    ++n;
+                    if (!have_car) { have_car = 1; car_s = val; }
+                    if (val == val) loop_min_gap(q, qflags, val - s, e + MPC_TRX_MIN_GAP_ACTOR, (double)a);
+                }
+            }
+        } else {                                     // :351-372, this light's state
+            if (!(fl & ACT_TL_GREEN)) {
+                const double dist = M.pos_s - s;
+                if (0.0 < dist && dist < M.trigger_s) {
+                    o[2 * n] = M.pos_s;
+                    o[2 * n + 1] = 0.0;
+                    ++n;
+                    if (v < 0.1 && dist < 10.0) fl |= ACT_TL_WAITING;
+                }
+                if (fl & ACT_TL_WAITING) {
+                    val += dt;
+                    if (val >= M.stop_duration) fl = (fl | ACT_TL_GREEN) & ~ACT_TL_WAITING;
+                }
+            }
+            if (fl & ACT_TL_GREEN) green |= 1 << a;
+            if (!(fl & ACT_PASS_DECIDED) && s > M.pos_s) {   // the first state past this light
+                fl |= ACT_PASS_DECIDED;
+                if (!(fl & ACT_TL_GREEN)) {
+                    q[MPC_CLQ_RED_PASS] = 1.0;
+                    e[MPC_TRX_N_RED_PASS] += 1.0;
+                }
+            }
+        }
+    }
+    return n;
+}
+
 struct Backend {
     HostTable table;
     std::unique_ptr<Ref> ref;
@@ -1182,109 +1384,54 @@ struct Backend {
         for (int i = 0; i < n; ++i) ref->pose(s[i], d[i], out + 3 * (size_t)i);
     }
 
-    // run_simulation (trajectory_tracking.py:377-443) for B egos, step-synchronous like the device loop: per
-    // step the ObstaclesFSM of every ego in the loop, one batched solve over them, the Euler plant step
-    int closed_loop(const mpc_params& p0, int B, const double* x_init, const mpc_fsm& F, bool with_fsm,
-                    int max_steps, double s_stop, double* hist_x, double* hist_u, double* hist_obs_s,
-                    int* hist_tl, int* hist_status, int* n_steps, double* step_ms) const {
-        mpc_params p = p0;
-        p.max_obs = with_fsm ? 2 : 0;
-        const size_t nb = (size_t)B, ns = (size_t)max_steps;
-        if (hist_x) std::fill(hist_x, hist_x + nb * (ns + 1) * 5, NAN);
-        if (hist_u) std::fill(hist_u, hist_u + nb * ns * 2, NAN);
-        if (hist_obs_s) std::fill(hist_obs_s, hist_obs_s + nb * ns, NAN);
-        if (hist_tl) std::fill(hist_tl, hist_tl + nb * ns, -1);
-        if (hist_status) std::fill(hist_status, hist_status + nb * ns, -1);
-        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
-        std::vector<double> x(x_init, x_init + nb * 5), car(nb, F.obs_start_s), timer(nb, 0.0);
-        std::vector<int> flags(nb * 4, 0), active(nb), alist;
+    // The loop of every closed-loop member, step-synchronous like the device loop.  Per step: the list of the
+    // egos still in the loop; rank(alist) (the convoys' ordering; a no-op elsewhere); for the i-th listed ego b,
+    // sense(step, b, xs, obs) fills the state xs [5] and the slab obs [ow][2] the solver receives and returns
+    // n_obs; one batched solve over the list (with the slab when with_obs, p.max_obs == ow); then
+    // plant(step, b, u0, status) per listed ego.  The step times go to E.ms and the optional E.step_ms
+    template <typename Rank, typename Sense, typename Plant>
+    void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
+                  Plant plant) const {
+        std::vector<int> alist, nobsa, sta;
         std::vector<double> xa, obsa, u0a;
-        std::vector<int> nobsa, sta;
-        for (int b = 0; b < B; ++b) {
-            n_steps[b] = 0;
-            active[b] = x[5 * (size_t)b] <= s_stop;
-            if (hist_x) std::memcpy(hist_x + (size_t)b * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-        }
         for (int step = 0; step < max_steps; ++step) {
             const auto t0 = std::chrono::steady_clock::now();
             alist.clear();
-            for (int b = 0; b < B; ++b)
-                if (active[b]) alist.push_back(b);
+            for (int b = 0; b < E.B; ++b)
+                if (E.active[b]) alist.push_back(b);
             if (alist.empty()) break;
             const int nl = (int)alist.size();
+            rank(alist);
             xa.assign((size_t)nl * 5, 0.0);
-            obsa.assign((size_t)nl * 4, 0.0);
+            obsa.assign((size_t)nl * ow * 2, 0.0);
             nobsa.assign(nl, 0);
             u0a.assign((size_t)nl * 2, 0.0);
             sta.assign(nl, 0);
-            for (int i = 0; i < nl; ++i) {
-                const int b = alist[i];
-                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
-                int* fl = flags.data() + 4 * (size_t)b;      // car active, car triggered, light green, waiting
-                double* o = obsa.data() + 4 * (size_t)i;
-                int n = 0;
-                double car_s = NAN;
-                if (F.dynamic_obstacle) {                    // ObstaclesFSM.update, :335-349
-                    if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
-                    if (fl[0]) {
-                        car[b] = car[b] + F.obs_v * p.dt;
-                        if (car[b] > F.obs_end_s) {
-                            fl[0] = 0;
-                        } else {
-                            o[0] = car[b];
-                            o[1] = F.obs_v;
-                            n = 1;
-                            car_s = car[b];
-                        }
-                    }
-                }
-                if (F.traffic_light && !fl[2]) {             // :351-372
-                    const double dist = F.tl_pos - s;
-                    if (0.0 < dist && dist < F.tl_trigger_s) {
-                        o[2 * n] = F.tl_pos;
-                        o[2 * n + 1] = 0.0;
-                        ++n;
-                        if (v < 0.1 && dist < 10.0) fl[3] = 1;
-                    }
-                    if (fl[3]) {
-                        timer[b] += p.dt;
-                        if (timer[b] >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
-                    }
-                }
-                nobsa[i] = n;
-                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-                if (hist_obs_s) hist_obs_s[(size_t)b * ns + step] = car_s;
-                if (hist_tl) hist_tl[(size_t)b * ns + step] = fl[2];
-            }
-            solve_batch(p, nl, xa.data(), with_fsm ? obsa.data() : nullptr, with_fsm ? nobsa.data() : nullptr,
-                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
-            for (int i = 0; i < nl; ++i) {                   // plant step x + dt f(x, u0, k_ref(s)), :403-406
-                const int b = alist[i];
-                double* xb = x.data() + 5 * (size_t)b;
-                double st[5];
-                ref->state(xb[0], st);
-                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
-                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
-                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
-                if (hist_x) std::memcpy(hist_x + ((size_t)b * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-                if (hist_u) {
-                    hist_u[((size_t)b * ns + step) * 2] = u1;
-                    hist_u[((size_t)b * ns + step) * 2 + 1] = u2;
-                }
-                if (hist_status) hist_status[(size_t)b * ns + step] = sta[i];
-                n_steps[b] = step + 1;
-                if (!(xb[0] <= s_stop)) active[b] = 0;
-            }
-            if (step_ms)
-                step_ms[step] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            for (int i = 0; i < nl; ++i)
+                nobsa[i] = sense(step, alist[i], xa.data() + 5 * (size_t)i, obsa.data() + (size_t)i * ow * 2);
+            solve_batch(p, nl, xa.data(), with_obs ? obsa.data() : nullptr, with_obs ? nobsa.data() : nullptr, nullptr,
+                        u0a.data(), nullptr, nullptr, sta.data(), nullptr);
+            for (int i = 0; i < nl; ++i) plant(step, alist[i], u0a.data() + 2 * (size_t)i, sta[i]);
+            E.ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            if (E.step_ms) E.step_ms[step] = E.ms.back();
         }
-        return MPC_SUCCESS;
     }
 
-    // mpc_closed_loop_sweep on the host: closed_loop above with ego b's scenario fsm[n_fsm == 1 ? 0 : b], the
-    // check quantities (include/mpcqp.h, MPC_CLQ_*) accumulated while the loop runs, and history rows only for
-    // the egos with slot[b] >= 0 (row slot[b] of the [n_hist][...] arrays).  quant is [B][MPC_CL_NQ]; n_steps
-    // and step_ms are optional.  The extremes take a NaN operand and keep it, like numpy's max / min
+    // run_simulation (trajectory_tracking.py:377-443) for B egos: mpc_closed_loop on the host is the sweep below
+    // with one scenario, every ego's history kept ([B] rows) and the quantities dropped
+    int closed_loop(const mpc_params& p0, int B, const double* x_init, const mpc_fsm& F, bool with_fsm,
+                    int max_steps, double s_stop, double* hist_x, double* hist_u, double* hist_obs_s,
+                    int* hist_tl, int* hist_status, int* n_steps, double* step_ms) const {
+        std::vector<int> slot((size_t)B);
+        for (int b = 0; b < B; ++b) slot[b] = b;
+        std::vector<double> quant((size_t)B * MPC_CL_NQ);
+        return closed_loop_sweep(p0, B, x_init, &F, 1, with_fsm, max_steps, s_stop, quant.data(), B, slot.data(),
+                                 hist_x, hist_u, hist_obs_s, hist_tl, hist_status, n_steps, step_ms);
+    }
+
+    // mpc_closed_loop_sweep on the host: per step the ObstaclesFSM of every ego in the loop with ego b's scenario
+    // fsm[n_fsm == 1 ? 0 : b], one batched solve over them, the Euler plant step; the check quantities
+    // (include/mpcqp.h, MPC_CLQ_*) accumulate while the loop runs.  n_steps is optional
     int closed_loop_sweep(const mpc_params& p0, int B, const double* x_init, const mpc_fsm* fsm, int n_fsm,
                           bool with_fsm, int max_steps, double s_stop, double* quant, int n_hist, const int* slot,
                           double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl, int* hist_status,
@@ -1292,799 +1439,234 @@ struct Backend {
         mpc_params p = p0;
         p.max_obs = with_fsm ? 2 : 0;
         const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist;
-        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
-        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
-        if (hist_obs_s) std::fill(hist_obs_s, hist_obs_s + nh * ns, NAN);
-        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
-        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
-        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
-        std::vector<double> x(x_init, x_init + nb * 5), car(nb), timer(nb, 0.0), ms;
-        std::vector<int> flags(nb * 4, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
-        std::vector<double> xa, obsa, u0a;
-        std::vector<int> nobsa, sta;
-        for (int b = 0; b < B; ++b) {
-            car[b] = fsm[n_fsm == 1 ? 0 : b].obs_start_s;
-            active[b] = x[5 * (size_t)b] <= s_stop;
-            if (hist_x && slot[b] >= 0)
-                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-            double* q = quant + (size_t)b * MPC_CL_NQ;
-            std::fill(q, q + MPC_CL_NQ, 0.0);
-            q[MPC_CLQ_EGO] = (double)b;
-            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
-            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
-            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
-        }
-        for (int step = 0; step < max_steps; ++step) {
-            const auto t0 = std::chrono::steady_clock::now();
-            alist.clear();
-            for (int b = 0; b < B; ++b)
-                if (active[b]) alist.push_back(b);
-            if (alist.empty()) break;
-            const int nl = (int)alist.size();
-            xa.assign((size_t)nl * 5, 0.0);
-            obsa.assign((size_t)nl * 4, 0.0);
-            nobsa.assign(nl, 0);
-            u0a.assign((size_t)nl * 2, 0.0);
-            sta.assign(nl, 0);
-            for (int i = 0; i < nl; ++i) {
-                const int b = alist[i];
-                const mpc_fsm& F = fsm[n_fsm == 1 ? 0 : b];
-                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
-                int* fl = flags.data() + 4 * (size_t)b;      // car active, car triggered, light green, waiting
-                double* o = obsa.data() + 4 * (size_t)i;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                int n = 0;
-                double car_s = NAN;
-                if (F.dynamic_obstacle) {                    // ObstaclesFSM.update, :335-349
-                    if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
-                    if (fl[0]) {
-                        car[b] = car[b] + F.obs_v * p.dt;
-                        if (car[b] > F.obs_end_s) {
-                            fl[0] = 0;
-                        } else {
-                            o[0] = car[b];
-                            o[1] = F.obs_v;
-                            n = 1;
-                            car_s = car[b];
-                        }
-                    }
-                }
-                if (F.traffic_light && !fl[2]) {             // :351-372
-                    const double dist = F.tl_pos - s;
-                    if (0.0 < dist && dist < F.tl_trigger_s) {
-                        o[2 * n] = F.tl_pos;
-                        o[2 * n + 1] = 0.0;
-                        ++n;
-                        if (v < 0.1 && dist < 10.0) fl[3] = 1;
-                    }
-                    if (fl[3]) {
-                        timer[b] += p.dt;
-                        if (timer[b] >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
-                    }
-                }
-                nobsa[i] = n;
-                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-                if (car_s == car_s) {                        // the gap of check_quantities, hist_obs_s[i] - hist_x[i, 0]
-                    const double g = car_s - s;
-                    if (!(qflags[b] & 1)) {
-                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                        qflags[b] |= 1;
-                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
-                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                    }
-                }
-                if (F.traffic_light && !(qflags[b] & 2) && s > F.tl_pos) {   // the first state past the light
-                    qflags[b] |= 2;
-                    if (!fl[2]) q[MPC_CLQ_RED_PASS] = 1.0;
-                }
-                if (slot[b] >= 0) {
-                    if (hist_obs_s) hist_obs_s[(size_t)slot[b] * ns + step] = car_s;
-                    if (hist_tl) hist_tl[(size_t)slot[b] * ns + step] = fl[2];
-                }
-            }
-            solve_batch(p, nl, xa.data(), with_fsm ? obsa.data() : nullptr, with_fsm ? nobsa.data() : nullptr,
-                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
-            for (int i = 0; i < nl; ++i) {                   // plant step x + dt f(x, u0, k_ref(s)), :403-406
-                const int b = alist[i];
-                double* xb = x.data() + 5 * (size_t)b;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double st[5];
-                ref->state(xb[0], st);
-                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
-                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
-                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b];
-                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-                    if (hist_u) {
-                        hist_u[(h * ns + step) * 2] = u1;
-                        hist_u[(h * ns + step) * 2 + 1] = u2;
-                    }
-                    if (hist_status) hist_status[h * ns + step] = sta[i];
-                }
-                nrun[b] = step + 1;
-                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
-                q[MPC_CLQ_S_FINAL] = xb[0];
-                const double ad = std::fabs(xb[1]);
-                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
-                if (step == 0) {                             // every ego that runs at all runs step 0
-                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
-                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
-                } else {
-                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
-                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
-                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
-                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
-                }
-                const int code = sta[i] & MPC_STATUS_MASK;
-                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
-                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
-                if (!(xb[0] <= s_stop)) active[b] = 0;
-            }
-            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            if (step_ms) step_ms[step] = ms.back();
-        }
-        sweep_max_step_ms(B, nrun.data(), ms, quant);
-        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
+        hist_prefill(hist_obs_s, nh * ns, (double)NAN);
+        hist_prefill(hist_tl, nh * ns, -1);
+        LoopEgos E(B, x_init, max_steps, s_stop, quant, n_hist, slot, hist_x, hist_u, hist_status, step_ms);
+        std::vector<double> car(nb), timer(nb, 0.0);
+        std::vector<int> flags(nb * 4, 0);
+        for (int b = 0; b < B; ++b) car[b] = fsm[n_fsm == 1 ? 0 : b].obs_start_s;
+        run_loop(p, E, max_steps, with_fsm, 2, [](const std::vector<int>&) {},
+                 [&](int step, int b, double* xs, double* o) {
+                     const mpc_fsm& F = fsm[n_fsm == 1 ? 0 : b];
+                     const double s = E.x[5 * (size_t)b], v = E.x[5 * (size_t)b + 4];
+                     int* fl = flags.data() + 4 * (size_t)b;
+                     double* q = quant + (size_t)b * MPC_CL_NQ;
+                     double car_s;
+                     const int n = fsm_step(F, p.dt, s, v, fl, car[b], timer[b], o, car_s);
+                     std::memcpy(xs, E.x.data() + 5 * (size_t)b, 5 * sizeof(double));
+                     if (car_s == car_s) loop_min_gap(q, E.qflags[b], car_s - s);
+                     if (F.traffic_light && !(E.qflags[b] & 2) && s > F.tl_pos) {   // the first state past the light
+                         E.qflags[b] |= 2;
+                         if (!fl[2]) q[MPC_CLQ_RED_PASS] = 1.0;
+                     }
+                     if (slot[b] >= 0) {
+                         if (hist_obs_s) hist_obs_s[(size_t)slot[b] * ns + step] = car_s;
+                         if (hist_tl) hist_tl[(size_t)slot[b] * ns + step] = fl[2];
+                     }
+                     return n;
+                 },
+                 [&](int step, int b, const double* u, int status) {
+                     E.plant(*ref, p.dt, b, step, u, u, status, [](double*) {});
+                 });
+        E.finish(n_steps);
         return MPC_SUCCESS;
     }
 
-    // mpc_closed_loop_traffic on the host: closed_loop_sweep above with a script of A actors per ego
-    // (actors[(n_scripts == 1 ? 0 : b) * A + a]), each actor running ObstaclesFSM's per-obstacle transitions on
-    // its own state, visited in index order; the slab takes what they emit, n_obs entries of A.  with_slab: some
-    // actor of some script is not NONE (the solver then runs with max_obs = A).  extra [B][MPC_TR_NX], n_steps,
-    // step_ms and every history are optional; hist_slab is [n_hist][max_steps][A][2]
+    // The loop behind the three scripted members below.  Ego b runs the script actors[(n_scripts == 1 ? 0 : b) * A
+    // + a] (script_step); the slab takes what its actors emit, then (s, v) of its leaders, n_obs entries of A + K.
+    // with_slab: the solver runs with max_obs = A + K.
+    //   worlds (K > 0): per step every world's egos [w*W, (w+1)*W) still in the loop are sorted by the ahead-of
+    //     order (the larger s first, on equal s the lower index) on the states before the step; an ego's leaders
+    //     are its predecessors in that order, nearest first, at most K, cut at the first gap >= lead_range.
+    //   noise (noise != NULL, [n_noise], n_noise 1 or B; ego b draws as global ego ego_offset + b): the FSMs, the
+    //     leader ranking, the gap quantities, hist_slab and the exit test use the true states; the solver receives
+    //     x + meas_sigma * z and a perturbed copy of the slab; the plant integrates the clamped u + act_sigma * z
+    //     and adds (dt * proc_sigma) * z.
+    // extra is [B][nx] (MPC_TR_NX; MPC_CV_NX with worlds; MPC_NZ_NX with noise); extra, n_steps, step_ms and every
+    // history are optional; hist_slab is [n_hist][max_steps][A+K][2], hist_lead [n_hist][max_steps][K]
+    int closed_loop_scripted(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
+                             const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
+                             int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
+                             double* quant, double* extra, int nx, int n_hist, const int* slot, double* hist_x,
+                             double* hist_u, double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl,
+                             int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
+                             double* step_ms) const {
+        mpc_params p = p0;
+        const int AK = A + K;
+        p.max_obs = with_slab ? AK : 0;
+        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
+        const size_t nak = (size_t)AK, nxs = (size_t)nx;
+        hist_prefill(hist_ua, nh * ns * 2, (double)NAN);
+        hist_prefill(hist_xm, nh * ns * 5, (double)NAN);
+        hist_prefill(hist_car_s, nh * ns, (double)NAN);
+        hist_prefill(hist_tl, nh * ns, -1);
+        hist_prefill(hist_nobs, nh * ns, -1);
+        hist_prefill(hist_slab, nh * ns * nak * 2, (double)NAN);
+        hist_prefill(hist_lead, nh * ns * nk, -1);
+        LoopEgos E(B, x_init, max_steps, s_stop, quant, n_hist, slot, hist_x, hist_u, hist_status, step_ms);
+        const mpc_noise quiet = {};
+        std::vector<double> aval(nb * na, 0.0), ex(nb * nxs, 0.0);
+        std::vector<int> aflags(nb * na, 0);
+        std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
+        for (int b = 0; b < B; ++b) {
+            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+            for (int a = 0; a < A; ++a)
+                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
+            double* e = ex.data() + (size_t)b * nxs;
+            e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+            if (nx >= MPC_CV_NX) {
+                e[MPC_CVX_MIN_LEAD_GAP] = NAN;
+                e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
+            }
+        }
+        run_loop(p, E, max_steps, with_slab, nak,
+                 [&](const std::vector<int>& alist) {
+                     if (K == 0) return;
+                     // alist is increasing, so each world's egos in the loop are one run of it: sort the run, and
+                     // order[rank[b] - 1], order[rank[b] - 2], .. down to the run's start are ego b's leaders
+                     const int nl = (int)alist.size();
+                     order = alist;
+                     for (int i = 0, w = 0; w <= B / W; ++w) {
+                         while (i < nl && alist[i] < w * W) ++i;
+                         wbeg[w] = i;
+                     }
+                     for (int w = 0; w < B / W; ++w)
+                         std::sort(order.begin() + wbeg[w], order.begin() + wbeg[w + 1], [&](int a, int b) {
+                             const double sa = E.x[5 * (size_t)a], sb = E.x[5 * (size_t)b];
+                             return sa > sb || (sa == sb && a < b);
+                         });
+                     for (int i = 0; i < nl; ++i) rank[order[i]] = i;
+                 },
+                 [&](int step, int b, double* xm, double* oa) {
+                     const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
+                     const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
+                     const double s = E.x[5 * (size_t)b], v = E.x[5 * (size_t)b + 4];
+                     double o[2 * MPC_MAX_ACTORS];            // the true slab of this step
+                     double* q = quant + (size_t)b * MPC_CL_NQ;
+                     double* e = ex.data() + (size_t)b * nxs;
+                     int green;
+                     double car_s;
+                     int n = script_step(actors + (n_scripts == 1 ? 0 : (size_t)b * na), A, p.dt, s, v,
+                                         aflags.data() + (size_t)b * na, aval.data() + (size_t)b * na, o, q, e,
+                                         E.qflags[b], green, car_s);
+                     if (K > 0) {                             // the leaders, nearest first
+                         int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
+                         const int r = rank[b], r0 = wbeg[b / W];
+                         int nlead = 0;
+                         for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {
+                             const int j = order[r - 1 - nlead];
+                             const double sj = E.x[5 * (size_t)j], gap = sj - s;
+                             if (gap >= lead_range) break;
+                             o[2 * n] = sj;
+                             o[2 * n + 1] = E.x[5 * (size_t)j + 4];
+                             ++n;
+                             if (hlead) hlead[nlead] = j;
+                             loop_min_gap(q, E.qflags[b], gap, e + MPC_TRX_MIN_GAP_ACTOR, -1.0);   // a leader is a car
+                             if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || gap < e[MPC_CVX_MIN_LEAD_GAP] || gap != gap) {
+                                 e[MPC_CVX_MIN_LEAD_GAP] = gap;
+                                 e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
+                             }
+                         }
+                         if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
+                     }
+                     if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
+                     // what the solver receives: the measured state and the perceived slab
+                     for (int j = 0; j < 5; ++j) {
+                         xm[j] = E.x[5 * (size_t)b + j];
+                         if (Z.meas_sigma[j] != 0.0)
+                             xm[j] = xm[j] + Z.meas_sigma[j] * noise_z(seed, g, step, MPC_NZ_CH_MEAS + j);
+                     }
+                     for (int j = 0; j < n; ++j) {
+                         oa[2 * j] = o[2 * j];
+                         oa[2 * j + 1] = o[2 * j + 1];
+                         if (Z.perc_sigma[0] != 0.0)
+                             oa[2 * j] = oa[2 * j] + Z.perc_sigma[0] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j);
+                         if (Z.perc_sigma[1] != 0.0)
+                             oa[2 * j + 1] = oa[2 * j + 1] + Z.perc_sigma[1] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j + 1);
+                     }
+                     if (slot[b] >= 0) {
+                         const size_t h = (size_t)slot[b] * ns + step;
+                         if (hist_car_s) hist_car_s[h] = car_s;
+                         if (hist_tl) hist_tl[h] = green;
+                         if (hist_nobs) hist_nobs[h] = n;
+                         if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
+                         if (hist_xm) std::memcpy(hist_xm + h * 5, xm, 5 * sizeof(double));
+                     }
+                     return n;
+                 },
+                 [&](int step, int b, const double* u, int status) {
+                     const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
+                     const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
+                     double ua[2] = {u[0], u[1]};             // the applied control
+                     bool clamped = false;
+                     for (int k = 0; k < 2; ++k)
+                         if (Z.act_sigma[k] != 0.0) {
+                             const double t = ua[k] + Z.act_sigma[k] * noise_z(seed, g, step, MPC_NZ_CH_ACT + k);
+                             ua[k] = t < p.u_min[k] ? p.u_min[k] : (t > p.u_max[k] ? p.u_max[k] : t);
+                             clamped = clamped || t < p.u_min[k] || t > p.u_max[k];
+                         }
+                     E.plant(*ref, p.dt, b, step, u, ua, status, [&](double* xb) {
+                         for (int j = 0; j < 5; ++j)
+                             if (Z.proc_sigma[j] != 0.0)
+                                 xb[j] = xb[j] + (p.dt * Z.proc_sigma[j]) * noise_z(seed, g, step, MPC_NZ_CH_PROC + j);
+                     });
+                     if (nx < MPC_NZ_NX) return;
+                     double* e = ex.data() + (size_t)b * nxs;
+                     if (slot[b] >= 0 && hist_ua) {
+                         hist_ua[((size_t)slot[b] * ns + step) * 2] = ua[0];
+                         hist_ua[((size_t)slot[b] * ns + step) * 2 + 1] = ua[1];
+                     }
+                     if (step == 0) {
+                         e[MPC_NZX_U1A_MIN] = e[MPC_NZX_U1A_MAX] = ua[0];
+                         e[MPC_NZX_U2A_MIN] = e[MPC_NZX_U2A_MAX] = ua[1];
+                     } else {
+                         if (ua[0] < e[MPC_NZX_U1A_MIN] || ua[0] != ua[0]) e[MPC_NZX_U1A_MIN] = ua[0];
+                         if (ua[0] > e[MPC_NZX_U1A_MAX] || ua[0] != ua[0]) e[MPC_NZX_U1A_MAX] = ua[0];
+                         if (ua[1] < e[MPC_NZX_U2A_MIN] || ua[1] != ua[1]) e[MPC_NZX_U2A_MIN] = ua[1];
+                         if (ua[1] > e[MPC_NZX_U2A_MAX] || ua[1] != ua[1]) e[MPC_NZX_U2A_MAX] = ua[1];
+                     }
+                     if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
+                 });
+        E.finish(n_steps);
+        if (extra) std::memcpy(extra, ex.data(), nb * nxs * sizeof(double));
+        return MPC_SUCCESS;
+    }
+
+    // mpc_closed_loop_traffic on the host: the sweep with a script of A actors per ego, no worlds, no noise
     int closed_loop_traffic(const mpc_params& p0, int B, const double* x_init, const mpc_actor* actors, int A,
                             int n_scripts, bool with_slab, int max_steps, double s_stop, double* quant,
                             double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
                             double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs, double* hist_slab,
                             int* n_steps, double* step_ms) const {
-        mpc_params p = p0;
-        p.max_obs = with_slab ? A : 0;
-        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A;
-        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
-        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
-        if (hist_car_s) std::fill(hist_car_s, hist_car_s + nh * ns, NAN);
-        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
-        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
-        if (hist_nobs) std::fill(hist_nobs, hist_nobs + nh * ns, -1);
-        if (hist_slab) std::fill(hist_slab, hist_slab + nh * ns * na * 2, NAN);
-        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
-        enum { CAR_ACTIVE = 1, CAR_TRIGGERED = 2, TL_GREEN = 4, TL_WAITING = 8, PASS_DECIDED = 16 };
-        std::vector<double> x(x_init, x_init + nb * 5), aval(nb * na, 0.0), ex(nb * MPC_TR_NX, 0.0), ms;
-        std::vector<int> aflags(nb * na, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
-        std::vector<double> xa, obsa, u0a;
-        std::vector<int> nobsa, sta;
-        for (int b = 0; b < B; ++b) {
-            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-            for (int a = 0; a < A; ++a)
-                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
-            active[b] = x[5 * (size_t)b] <= s_stop;
-            if (hist_x && slot[b] >= 0)
-                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-            double* q = quant + (size_t)b * MPC_CL_NQ;
-            std::fill(q, q + MPC_CL_NQ, 0.0);
-            q[MPC_CLQ_EGO] = (double)b;
-            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
-            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
-            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
-            ex[(size_t)b * MPC_TR_NX + MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-        }
-        for (int step = 0; step < max_steps; ++step) {
-            const auto t0 = std::chrono::steady_clock::now();
-            alist.clear();
-            for (int b = 0; b < B; ++b)
-                if (active[b]) alist.push_back(b);
-            if (alist.empty()) break;
-            const int nl = (int)alist.size();
-            xa.assign((size_t)nl * 5, 0.0);
-            obsa.assign((size_t)nl * na * 2, 0.0);
-            nobsa.assign(nl, 0);
-            u0a.assign((size_t)nl * 2, 0.0);
-            sta.assign(nl, 0);
-            for (int i = 0; i < nl; ++i) {
-                const int b = alist[i];
-                const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
-                double* o = obsa.data() + (size_t)i * na * 2;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double* e = ex.data() + (size_t)b * MPC_TR_NX;
-                int n = 0, green = 0, have_car = 0;
-                double car_s = NAN;
-                for (int a = 0; a < A; ++a) {
-                    const mpc_actor& K = sc[a];
-                    if (K.kind == MPC_ACTOR_NONE) continue;
-                    int& fl = aflags[(size_t)b * na + a];
-                    double& val = aval[(size_t)b * na + a];
-                    if (K.kind == MPC_ACTOR_CAR) {               // ObstaclesFSM.update, :335-349, this car's state
-                        if (!(fl & CAR_TRIGGERED) && s >= K.trigger_s) fl |= CAR_TRIGGERED | CAR_ACTIVE;
-                        if (fl & CAR_ACTIVE) {
-                            val = val + K.v * p.dt;
-                            if (val > K.end_s) {
-                                fl &= ~CAR_ACTIVE;
-                            } else {
-                                o[2 * n] = val;
-                                o[2 * n + 1] = K.v;
-                                ++n;
-                                if (!have_car) { have_car = 1; car_s = val; }
-                                if (val == val) {                // the gap of check_quantities, over every car
-                                    const double g = val - s;
-                                    if (!(qflags[b] & 1)) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                        qflags[b] |= 1;
-                                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                    }
-                                }
-                            }
-                        }
-                    } else {                                     // :351-372, this light's state
-                        if (!(fl & TL_GREEN)) {
-                            const double dist = K.pos_s - s;
-                            if (0.0 < dist && dist < K.trigger_s) {
-                                o[2 * n] = K.pos_s;
-                                o[2 * n + 1] = 0.0;
-                                ++n;
-                                if (v < 0.1 && dist < 10.0) fl |= TL_WAITING;
-                            }
-                            if (fl & TL_WAITING) {
-                                val += p.dt;
-                                if (val >= K.stop_duration) fl = (fl | TL_GREEN) & ~TL_WAITING;
-                            }
-                        }
-                        if (fl & TL_GREEN) green |= 1 << a;
-                        if (!(fl & PASS_DECIDED) && s > K.pos_s) {   // the first state past this light
-                            fl |= PASS_DECIDED;
-                            if (!(fl & TL_GREEN)) {
-                                q[MPC_CLQ_RED_PASS] = 1.0;
-                                e[MPC_TRX_N_RED_PASS] += 1.0;
-                            }
-                        }
-                    }
-                }
-                nobsa[i] = n;
-                if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
-                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b] * ns + step;
-                    if (hist_car_s) hist_car_s[h] = car_s;
-                    if (hist_tl) hist_tl[h] = green;
-                    if (hist_nobs) hist_nobs[h] = n;
-                    if (hist_slab && n) std::memcpy(hist_slab + h * na * 2, o, (size_t)n * 2 * sizeof(double));
-                }
-            }
-            solve_batch(p, nl, xa.data(), with_slab ? obsa.data() : nullptr, with_slab ? nobsa.data() : nullptr,
-                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
-            for (int i = 0; i < nl; ++i) {                   // plant step and plant-side quantities: the sweep's
-                const int b = alist[i];
-                double* xb = x.data() + 5 * (size_t)b;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double st[5];
-                ref->state(xb[0], st);
-                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
-                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
-                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b];
-                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-                    if (hist_u) {
-                        hist_u[(h * ns + step) * 2] = u1;
-                        hist_u[(h * ns + step) * 2 + 1] = u2;
-                    }
-                    if (hist_status) hist_status[h * ns + step] = sta[i];
-                }
-                nrun[b] = step + 1;
-                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
-                q[MPC_CLQ_S_FINAL] = xb[0];
-                const double ad = std::fabs(xb[1]);
-                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
-                if (step == 0) {
-                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
-                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
-                } else {
-                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
-                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
-                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
-                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
-                }
-                const int code = sta[i] & MPC_STATUS_MASK;
-                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
-                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
-                if (!(xb[0] <= s_stop)) active[b] = 0;
-            }
-            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            if (step_ms) step_ms[step] = ms.back();
-        }
-        sweep_max_step_ms(B, nrun.data(), ms, quant);
-        if (extra) std::memcpy(extra, ex.data(), nb * MPC_TR_NX * sizeof(double));
-        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
-        return MPC_SUCCESS;
+        return closed_loop_scripted(p0, B, 1, 0, INFINITY, x_init, actors, A, n_scripts, with_slab, nullptr, 1, 0, 0,
+                                    max_steps, s_stop, quant, extra, MPC_TR_NX, n_hist, slot, hist_x, hist_u, nullptr,
+                                    nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps,
+                                    step_ms);
     }
 
-    // mpc_closed_loop_convoy on the host: closed_loop_traffic above with the egos [w*W, (w+1)*W) of a world as
-    // each other's obstacles.  Per step every world's egos still in the loop are sorted by the ahead-of order
-    // (the larger s first, on equal s the lower index) on the states before the step; an ego's leaders are its
-    // predecessors in that order, nearest first, at most K, cut at the first gap >= lead_range, appended as
-    // (s, v) after its script entries.  The slab is A + K wide (hist_slab [n_hist][max_steps][A+K][2]),
-    // hist_lead [n_hist][max_steps][K] holds the leaders' batch indices, extra is [B][MPC_CV_NX]
+    // mpc_closed_loop_convoy on the host: the egos [w*W, (w+1)*W) of a world as each other's obstacles
     int closed_loop_convoy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
                            const mpc_actor* actors, int A, int n_scripts, bool with_slab, int max_steps,
                            double s_stop, double* quant, double* extra, int n_hist, const int* slot, double* hist_x,
                            double* hist_u, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
                            double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
-        mpc_params p = p0;
-        const int AK = A + K;
-        p.max_obs = with_slab ? AK : 0;
-        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
-        const size_t nak = (size_t)AK;
-        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
-        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
-        if (hist_car_s) std::fill(hist_car_s, hist_car_s + nh * ns, NAN);
-        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
-        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
-        if (hist_nobs) std::fill(hist_nobs, hist_nobs + nh * ns, -1);
-        if (hist_slab) std::fill(hist_slab, hist_slab + nh * ns * nak * 2, NAN);
-        if (hist_lead) std::fill(hist_lead, hist_lead + nh * ns * nk, -1);
-        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
-        enum { CAR_ACTIVE = 1, CAR_TRIGGERED = 2, TL_GREEN = 4, TL_WAITING = 8, PASS_DECIDED = 16 };
-        std::vector<double> x(x_init, x_init + nb * 5), aval(nb * na, 0.0), ex(nb * MPC_CV_NX, 0.0), ms;
-        std::vector<int> aflags(nb * na, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
-        std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
-        std::vector<double> xa, obsa, u0a;
-        std::vector<int> nobsa, sta;
-        for (int b = 0; b < B; ++b) {
-            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-            for (int a = 0; a < A; ++a)
-                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
-            active[b] = x[5 * (size_t)b] <= s_stop;
-            if (hist_x && slot[b] >= 0)
-                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-            double* q = quant + (size_t)b * MPC_CL_NQ;
-            std::fill(q, q + MPC_CL_NQ, 0.0);
-            q[MPC_CLQ_EGO] = (double)b;
-            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
-            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
-            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
-            double* e = ex.data() + (size_t)b * MPC_CV_NX;
-            e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-            e[MPC_CVX_MIN_LEAD_GAP] = NAN;
-            e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
-        }
-        for (int step = 0; step < max_steps; ++step) {
-            const auto t0 = std::chrono::steady_clock::now();
-            alist.clear();
-            for (int b = 0; b < B; ++b)
-                if (active[b]) alist.push_back(b);
-            if (alist.empty()) break;
-            const int nl = (int)alist.size();
-            // alist is increasing, so each world's egos in the loop are one run of it: sort the run, and
-            // order[rank[b] - 1], order[rank[b] - 2], .. down to the run's start are ego b's leaders
-            order = alist;
-            for (int i = 0, w = 0; w <= B / W; ++w) {
-                while (i < nl && alist[i] < w * W) ++i;
-                wbeg[w] = i;
-            }
-            for (int w = 0; w < B / W; ++w)
-                std::sort(order.begin() + wbeg[w], order.begin() + wbeg[w + 1], [&](int a, int b) {
-                    const double sa = x[5 * (size_t)a], sb = x[5 * (size_t)b];
-                    return sa > sb || (sa == sb && a < b);
-                });
-            for (int i = 0; i < nl; ++i) rank[order[i]] = i;
-            xa.assign((size_t)nl * 5, 0.0);
-            obsa.assign((size_t)nl * nak * 2, 0.0);
-            nobsa.assign(nl, 0);
-            u0a.assign((size_t)nl * 2, 0.0);
-            sta.assign(nl, 0);
-            for (int i = 0; i < nl; ++i) {
-                const int b = alist[i];
-                const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
-                double* o = obsa.data() + (size_t)i * nak * 2;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double* e = ex.data() + (size_t)b * MPC_CV_NX;
-                int n = 0, green = 0, have_car = 0;
-                double car_s = NAN;
-                for (int a = 0; a < A; ++a) {
-                    const mpc_actor& M = sc[a];
-                    if (M.kind == MPC_ACTOR_NONE) continue;
-                    int& fl = aflags[(size_t)b * na + a];
-                    double& val = aval[(size_t)b * na + a];
-                    if (M.kind == MPC_ACTOR_CAR) {               // ObstaclesFSM.update, :335-349, this car's state
-                        if (!(fl & CAR_TRIGGERED) && s >= M.trigger_s) fl |= CAR_TRIGGERED | CAR_ACTIVE;
-                        if (fl & CAR_ACTIVE) {
-                            val = val + M.v * p.dt;
-                            if (val > M.end_s) {
-                                fl &= ~CAR_ACTIVE;
-                            } else {
-                                o[2 * n] = val;
-                                o[2 * n + 1] = M.v;
-                                ++n;
-                                if (!have_car) { have_car = 1; car_s = val; }
-                                if (val == val) {                // the gap of check_quantities, over every car
-                                    const double g = val - s;
-                                    if (!(qflags[b] & 1)) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                        qflags[b] |= 1;
-                                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                    }
-                                }
-                            }
-                        }
-                    } else {                                     // :351-372, this light's state
-                        if (!(fl & TL_GREEN)) {
-                            const double dist = M.pos_s - s;
-                            if (0.0 < dist && dist < M.trigger_s) {
-                                o[2 * n] = M.pos_s;
-                                o[2 * n + 1] = 0.0;
-                                ++n;
-                                if (v < 0.1 && dist < 10.0) fl |= TL_WAITING;
-                            }
-                            if (fl & TL_WAITING) {
-                                val += p.dt;
-                                if (val >= M.stop_duration) fl = (fl | TL_GREEN) & ~TL_WAITING;
-                            }
-                        }
-                        if (fl & TL_GREEN) green |= 1 << a;
-                        if (!(fl & PASS_DECIDED) && s > M.pos_s) {   // the first state past this light
-                            fl |= PASS_DECIDED;
-                            if (!(fl & TL_GREEN)) {
-                                q[MPC_CLQ_RED_PASS] = 1.0;
-                                e[MPC_TRX_N_RED_PASS] += 1.0;
-                            }
-                        }
-                    }
-                }
-                int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
-                const int r = rank[b], r0 = wbeg[b / W];
-                int nlead = 0;
-                for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {      // the leaders, nearest first
-                    const int j = order[r - 1 - nlead];
-                    const double sj = x[5 * (size_t)j], g = sj - s;
-                    if (g >= lead_range) break;
-                    o[2 * n] = sj;
-                    o[2 * n + 1] = x[5 * (size_t)j + 4];
-                    ++n;
-                    if (hlead) hlead[nlead] = j;
-                    if (!(qflags[b] & 1)) {                      // a leader is a car for the gap
-                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-                        qflags[b] |= 1;
-                    } else if (g < q[MPC_CLQ_MIN_OBS_DIST] || g != g) {
-                        q[MPC_CLQ_MIN_OBS_DIST] = g;
-                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-                    }
-                    if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || g < e[MPC_CVX_MIN_LEAD_GAP] || g != g) {
-                        e[MPC_CVX_MIN_LEAD_GAP] = g;
-                        e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
-                    }
-                }
-                nobsa[i] = n;
-                if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
-                if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
-                std::memcpy(xa.data() + 5 * (size_t)i, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b] * ns + step;
-                    if (hist_car_s) hist_car_s[h] = car_s;
-                    if (hist_tl) hist_tl[h] = green;
-                    if (hist_nobs) hist_nobs[h] = n;
-                    if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
-                }
-            }
-            solve_batch(p, nl, xa.data(), with_slab ? obsa.data() : nullptr, with_slab ? nobsa.data() : nullptr,
-                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
-            for (int i = 0; i < nl; ++i) {                   // plant step and plant-side quantities: the sweep's
-                const int b = alist[i];
-                double* xb = x.data() + 5 * (size_t)b;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double st[5];
-                ref->state(xb[0], st);
-                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
-                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), u1, u2};
-                for (int j = 0; j < 5; ++j) xb[j] = xb[j] + p.dt * xd[j];
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b];
-                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-                    if (hist_u) {
-                        hist_u[(h * ns + step) * 2] = u1;
-                        hist_u[(h * ns + step) * 2 + 1] = u2;
-                    }
-                    if (hist_status) hist_status[h * ns + step] = sta[i];
-                }
-                nrun[b] = step + 1;
-                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
-                q[MPC_CLQ_S_FINAL] = xb[0];
-                const double ad = std::fabs(xb[1]);
-                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
-                if (step == 0) {
-                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
-                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
-                } else {
-                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
-                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
-                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
-                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
-                }
-                const int code = sta[i] & MPC_STATUS_MASK;
-                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
-                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
-                if (!(xb[0] <= s_stop)) active[b] = 0;
-            }
-            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            if (step_ms) step_ms[step] = ms.back();
-        }
-        sweep_max_step_ms(B, nrun.data(), ms, quant);
-        if (extra) std::memcpy(extra, ex.data(), nb * MPC_CV_NX * sizeof(double));
-        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
-        return MPC_SUCCESS;
+        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, nullptr, 1, 0, 0,
+                                    max_steps, s_stop, quant, extra, MPC_CV_NX, n_hist, slot, hist_x, hist_u, nullptr,
+                                    nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps,
+                                    step_ms);
     }
 
-    // mpc_closed_loop_noisy on the host: closed_loop_convoy above with seeded noise between the world and the
-    // solver (include/mpcqp.h).  The FSMs, the leader ranking, the gap quantities, hist_slab and the exit test use
-    // the true states; the solver receives x + meas_sigma * z and a perturbed copy of the slab; the plant
-    // integrates the clamped u + act_sigma * z and adds (dt * proc_sigma) * z.  noise is [n_noise], n_noise 1
-    // (shared) or B; extra is [B][MPC_NZ_NX]; ego b draws as global ego ego_offset + b
+    // mpc_closed_loop_noisy on the host: the convoy with seeded noise between the world and the solver
     int closed_loop_noisy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
                           const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
                           int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
                           double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
                           double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
                           int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
-        mpc_params p = p0;
-        const int AK = A + K;
-        p.max_obs = with_slab ? AK : 0;
-        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
-        const size_t nak = (size_t)AK;
-        if (hist_x) std::fill(hist_x, hist_x + nh * (ns + 1) * 5, NAN);
-        if (hist_u) std::fill(hist_u, hist_u + nh * ns * 2, NAN);
-        if (hist_ua) std::fill(hist_ua, hist_ua + nh * ns * 2, NAN);
-        if (hist_xm) std::fill(hist_xm, hist_xm + nh * ns * 5, NAN);
-        if (hist_car_s) std::fill(hist_car_s, hist_car_s + nh * ns, NAN);
-        if (hist_tl) std::fill(hist_tl, hist_tl + nh * ns, -1);
-        if (hist_status) std::fill(hist_status, hist_status + nh * ns, -1);
-        if (hist_nobs) std::fill(hist_nobs, hist_nobs + nh * ns, -1);
-        if (hist_slab) std::fill(hist_slab, hist_slab + nh * ns * nak * 2, NAN);
-        if (hist_lead) std::fill(hist_lead, hist_lead + nh * ns * nk, -1);
-        if (step_ms) std::fill(step_ms, step_ms + ns, NAN);
-        enum { CAR_ACTIVE = 1, CAR_TRIGGERED = 2, TL_GREEN = 4, TL_WAITING = 8, PASS_DECIDED = 16 };
-        std::vector<double> x(x_init, x_init + nb * 5), aval(nb * na, 0.0), ex(nb * MPC_NZ_NX, 0.0), ms;
-        std::vector<int> aflags(nb * na, 0), qflags(nb, 0), active(nb), nrun(nb, 0), alist;
-        std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
-        std::vector<double> xa, obsa, u0a;
-        std::vector<int> nobsa, sta;
-        for (int b = 0; b < B; ++b) {
-            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-            for (int a = 0; a < A; ++a)
-                if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
-            active[b] = x[5 * (size_t)b] <= s_stop;
-            if (hist_x && slot[b] >= 0)
-                std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-            double* q = quant + (size_t)b * MPC_CL_NQ;
-            std::fill(q, q + MPC_CL_NQ, 0.0);
-            q[MPC_CLQ_EGO] = (double)b;
-            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
-            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
-            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
-            double* e = ex.data() + (size_t)b * MPC_NZ_NX;
-            e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-            e[MPC_CVX_MIN_LEAD_GAP] = NAN;
-            e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
-        }
-        for (int step = 0; step < max_steps; ++step) {
-            const auto t0 = std::chrono::steady_clock::now();
-            alist.clear();
-            for (int b = 0; b < B; ++b)
-                if (active[b]) alist.push_back(b);
-            if (alist.empty()) break;
-            const int nl = (int)alist.size();
-            order = alist;                                   // the ranking of closed_loop_convoy, on the true s
-            for (int i = 0, w = 0; w <= B / W; ++w) {
-                while (i < nl && alist[i] < w * W) ++i;
-                wbeg[w] = i;
-            }
-            for (int w = 0; w < B / W; ++w)
-                std::sort(order.begin() + wbeg[w], order.begin() + wbeg[w + 1], [&](int a, int b) {
-                    const double sa = x[5 * (size_t)a], sb = x[5 * (size_t)b];
-                    return sa > sb || (sa == sb && a < b);
-                });
-            for (int i = 0; i < nl; ++i) rank[order[i]] = i;
-            xa.assign((size_t)nl * 5, 0.0);
-            obsa.assign((size_t)nl * nak * 2, 0.0);
-            nobsa.assign(nl, 0);
-            u0a.assign((size_t)nl * 2, 0.0);
-            sta.assign(nl, 0);
-            for (int i = 0; i < nl; ++i) {
-                const int b = alist[i];
-                const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
-                const mpc_noise& Z = noise[n_noise == 1 ? 0 : b];
-                const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
-                const double s = x[5 * (size_t)b], v = x[5 * (size_t)b + 4];
-                double o[2 * MPC_MAX_ACTORS];                // the true slab of this step
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double* e = ex.data() + (size_t)b * MPC_NZ_NX;
-                int n = 0, green = 0, have_car = 0;
-                double car_s = NAN;
-                for (int a = 0; a < A; ++a) {
-                    const mpc_actor& M = sc[a];
-                    if (M.kind == MPC_ACTOR_NONE) continue;
-                    int& fl = aflags[(size_t)b * na + a];
-                    double& val = aval[(size_t)b * na + a];
-                    if (M.kind == MPC_ACTOR_CAR) {
-                        if (!(fl & CAR_TRIGGERED) && s >= M.trigger_s) fl |= CAR_TRIGGERED | CAR_ACTIVE;
-                        if (fl & CAR_ACTIVE) {
-                            val = val + M.v * p.dt;
-                            if (val > M.end_s) {
-                                fl &= ~CAR_ACTIVE;
-                            } else {
-                                o[2 * n] = val;
-                                o[2 * n + 1] = M.v;
-                                ++n;
-                                if (!have_car) { have_car = 1; car_s = val; }
-                                if (val == val) {
-                                    const double gap = val - s;
-                                    if (!(qflags[b] & 1)) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                        qflags[b] |= 1;
-                                    } else if (gap < q[MPC_CLQ_MIN_OBS_DIST] || gap != gap) {
-                                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
-                                        e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
-                                    }
-                                }
-                            }
-                        }
-                    } else {
-                        if (!(fl & TL_GREEN)) {
-                            const double dist = M.pos_s - s;
-                            if (0.0 < dist && dist < M.trigger_s) {
-                                o[2 * n] = M.pos_s;
-                                o[2 * n + 1] = 0.0;
-                                ++n;
-                                if (v < 0.1 && dist < 10.0) fl |= TL_WAITING;
-                            }
-                            if (fl & TL_WAITING) {
-                                val += p.dt;
-                                if (val >= M.stop_duration) fl = (fl | TL_GREEN) & ~TL_WAITING;
-                            }
-                        }
-                        if (fl & TL_GREEN) green |= 1 << a;
-                        if (!(fl & PASS_DECIDED) && s > M.pos_s) {
-                            fl |= PASS_DECIDED;
-                            if (!(fl & TL_GREEN)) {
-                                q[MPC_CLQ_RED_PASS] = 1.0;
-                                e[MPC_TRX_N_RED_PASS] += 1.0;
-                            }
-                        }
-                    }
-                }
-                int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
-                const int r = rank[b], r0 = wbeg[b / W];
-                int nlead = 0;
-                for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {
-                    const int j = order[r - 1 - nlead];
-                    const double sj = x[5 * (size_t)j], gap = sj - s;
-                    if (gap >= lead_range) break;
-                    o[2 * n] = sj;
-                    o[2 * n + 1] = x[5 * (size_t)j + 4];
-                    ++n;
-                    if (hlead) hlead[nlead] = j;
-                    if (!(qflags[b] & 1)) {
-                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
-                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-                        qflags[b] |= 1;
-                    } else if (gap < q[MPC_CLQ_MIN_OBS_DIST] || gap != gap) {
-                        q[MPC_CLQ_MIN_OBS_DIST] = gap;
-                        e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
-                    }
-                    if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || gap < e[MPC_CVX_MIN_LEAD_GAP] || gap != gap) {
-                        e[MPC_CVX_MIN_LEAD_GAP] = gap;
-                        e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
-                    }
-                }
-                nobsa[i] = n;
-                if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
-                if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
-                // what the solver receives: the measured state and the perceived slab
-                double* xm = xa.data() + 5 * (size_t)i;
-                for (int j = 0; j < 5; ++j) {
-                    xm[j] = x[5 * (size_t)b + j];
-                    if (Z.meas_sigma[j] != 0.0)
-                        xm[j] = xm[j] + Z.meas_sigma[j] * noise_z(seed, g, step, MPC_NZ_CH_MEAS + j);
-                }
-                double* oa = obsa.data() + (size_t)i * nak * 2;
-                for (int j = 0; j < n; ++j) {
-                    oa[2 * j] = o[2 * j];
-                    oa[2 * j + 1] = o[2 * j + 1];
-                    if (Z.perc_sigma[0] != 0.0)
-                        oa[2 * j] = oa[2 * j] + Z.perc_sigma[0] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j);
-                    if (Z.perc_sigma[1] != 0.0)
-                        oa[2 * j + 1] = oa[2 * j + 1] + Z.perc_sigma[1] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j + 1);
-                }
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b] * ns + step;
-                    if (hist_car_s) hist_car_s[h] = car_s;
-                    if (hist_tl) hist_tl[h] = green;
-                    if (hist_nobs) hist_nobs[h] = n;
-                    if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
-                    if (hist_xm) std::memcpy(hist_xm + h * 5, xm, 5 * sizeof(double));
-                }
-            }
-            solve_batch(p, nl, xa.data(), with_slab ? obsa.data() : nullptr, with_slab ? nobsa.data() : nullptr,
-                        nullptr, u0a.data(), nullptr, nullptr, sta.data(), nullptr);
-            for (int i = 0; i < nl; ++i) {                   // the convoy's plant step with the applied control
-                const int b = alist[i];
-                const mpc_noise& Z = noise[n_noise == 1 ? 0 : b];
-                const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
-                double* xb = x.data() + 5 * (size_t)b;
-                double* q = quant + (size_t)b * MPC_CL_NQ;
-                double* e = ex.data() + (size_t)b * MPC_NZ_NX;
-                double st[5];
-                ref->state(xb[0], st);
-                const double u1 = u0a[2 * (size_t)i], u2 = u0a[2 * (size_t)i + 1];
-                double ua[2] = {u1, u2};
-                bool clamped = false;
-                for (int k = 0; k < 2; ++k)
-                    if (Z.act_sigma[k] != 0.0) {
-                        const double t = ua[k] + Z.act_sigma[k] * noise_z(seed, g, step, MPC_NZ_CH_ACT + k);
-                        ua[k] = t < p.u_min[k] ? p.u_min[k] : (t > p.u_max[k] ? p.u_max[k] : t);
-                        clamped = clamped || t < p.u_min[k] || t > p.u_max[k];
-                    }
-                const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), ua[0], ua[1]};
-                for (int j = 0; j < 5; ++j) {
-                    xb[j] = xb[j] + p.dt * xd[j];
-                    if (Z.proc_sigma[j] != 0.0)
-                        xb[j] = xb[j] + (p.dt * Z.proc_sigma[j]) * noise_z(seed, g, step, MPC_NZ_CH_PROC + j);
-                }
-                if (slot[b] >= 0) {
-                    const size_t h = (size_t)slot[b];
-                    if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-                    if (hist_u) {
-                        hist_u[(h * ns + step) * 2] = u1;
-                        hist_u[(h * ns + step) * 2 + 1] = u2;
-                    }
-                    if (hist_ua) {
-                        hist_ua[(h * ns + step) * 2] = ua[0];
-                        hist_ua[(h * ns + step) * 2 + 1] = ua[1];
-                    }
-                    if (hist_status) hist_status[h * ns + step] = sta[i];
-                }
-                nrun[b] = step + 1;
-                q[MPC_CLQ_N_STEPS] = (double)(step + 1);
-                q[MPC_CLQ_S_FINAL] = xb[0];
-                const double ad = std::fabs(xb[1]);
-                if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
-                if (step == 0) {
-                    q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
-                    q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
-                    e[MPC_NZX_U1A_MIN] = e[MPC_NZX_U1A_MAX] = ua[0];
-                    e[MPC_NZX_U2A_MIN] = e[MPC_NZX_U2A_MAX] = ua[1];
-                } else {
-                    if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
-                    if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
-                    if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
-                    if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
-                    if (ua[0] < e[MPC_NZX_U1A_MIN] || ua[0] != ua[0]) e[MPC_NZX_U1A_MIN] = ua[0];
-                    if (ua[0] > e[MPC_NZX_U1A_MAX] || ua[0] != ua[0]) e[MPC_NZX_U1A_MAX] = ua[0];
-                    if (ua[1] < e[MPC_NZX_U2A_MIN] || ua[1] != ua[1]) e[MPC_NZX_U2A_MIN] = ua[1];
-                    if (ua[1] > e[MPC_NZX_U2A_MAX] || ua[1] != ua[1]) e[MPC_NZX_U2A_MAX] = ua[1];
-                }
-                if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
-                const int code = sta[i] & MPC_STATUS_MASK;
-                if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
-                if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
-                if (!(xb[0] <= s_stop)) active[b] = 0;
-            }
-            ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            if (step_ms) step_ms[step] = ms.back();
-        }
-        sweep_max_step_ms(B, nrun.data(), ms, quant);
-        if (extra) std::memcpy(extra, ex.data(), nb * MPC_NZ_NX * sizeof(double));
-        if (n_steps) std::memcpy(n_steps, nrun.data(), nb * sizeof(int));
-        return MPC_SUCCESS;
+        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
+                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
+                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
+                                    hist_lead, n_steps, step_ms);
     }
 };
 

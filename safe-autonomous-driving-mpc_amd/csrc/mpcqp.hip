@@ -27,7 +27,8 @@
 //   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
-// and lookup entry points) and, last, the comm layer (comm.h).
+// and lookup entry points; the driver the closed-loop entries share is closed_loop_host.h) and, last, the comm
+// layer (comm.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -652,6 +653,20 @@ extern "C" void mpc_default_fsm(mpc_fsm* f) {
     f->tl_stop_duration = 20.0;
 }
 
+// ------------------------------------------------------------------------------------------
+// the closed-loop entries: each checks its arguments, hands a device = -1 context to the host backend, and
+// otherwise configures the shared driver (closed_loop_host.h) with its buffers, outputs and kernels
+// ------------------------------------------------------------------------------------------
+#include "closed_loop_host.h"
+
+// a host-backend closed loop behind an entry: its return code, unless an exception was turned into one
+template <typename F>
+static int host_loop(F&& f) {
+    int hrc = MPC_SUCCESS;
+    const int erc = host_call([&] { hrc = f(); });
+    return erc != MPC_SUCCESS ? erc : hrc;
+}
+
 extern "C" int mpc_closed_loop(mpc_ctx* c, int B, const double* x_init, const mpc_fsm* fsm, int max_steps,
                                double s_stop, double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl,
                                int* hist_status, int* n_steps, double* step_ms) {
@@ -664,165 +679,46 @@ extern "C" int mpc_closed_loop(mpc_ctx* c, int B, const double* x_init, const mp
     mpc_fsm F;
     if (fsm) F = *fsm; else mpc_default_fsm(&F);     // NULL: both scenarios off
     const bool with_fsm = fsm && (F.dynamic_obstacle || F.traffic_light);
-    if (c->cpu) {
-        int hrc = MPC_SUCCESS;
-        const int erc = host_call([&] {
-            hrc = c->cpu->closed_loop(c->p, B, x_init, F, with_fsm, max_steps, s_stop, hist_x, hist_u, hist_obs_s,
-                                      hist_tl, hist_status, n_steps, step_ms);
+    if (c->cpu)
+        return host_loop([&] {
+            return c->cpu->closed_loop(c->p, B, x_init, F, with_fsm, max_steps, s_stop, hist_x, hist_u, hist_obs_s,
+                                       hist_tl, hist_status, n_steps, step_ms);
         });
-        return erc != MPC_SUCCESS ? erc : hrc;
-    }
     KParams kp = kparams(&c->p);
     kp.max_obs = with_fsm ? 2 : 0;          // the FSM yields at most the car and the light
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, ns = (size_t)max_steps;
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    ClState C;
-    C.x = (double*)dalloc(nb * 5 * 8);
-    C.obs = (double*)dalloc(nb * 4 * 8);
-    C.nobs = (int*)dalloc(nb * 4);
-    C.active = (int*)dalloc(nb * 4);
-    C.obs_s = (double*)dalloc(nb * 8);
-    C.tl_timer = (double*)dalloc(nb * 8);
-    C.fsm_flags = (int*)dalloc(nb * 4 * 4);
-    C.n_active = (int*)dalloc(4);
-    C.alist = (int*)dalloc(nb * 4);
-    C.n_list = (int*)dalloc(4);
-    C.xa = (double*)dalloc(nb * 5 * 8);
-    C.obsa = (double*)dalloc(nb * 4 * 8);
-    C.nobsa = (int*)dalloc(nb * 4);
-    C.u0a = (double*)dalloc(nb * 2 * 8);
-    C.sta = (int*)dalloc(nb * 4);
-    double* d_xinit = (double*)dalloc(nb * 5 * 8);
-    double* d_hx = hist_x ? (double*)dalloc(nb * (ns + 1) * 5 * 8) : nullptr;
-    double* d_hu = hist_u ? (double*)dalloc(nb * ns * 2 * 8) : nullptr;
-    double* d_ho = hist_obs_s ? (double*)dalloc(nb * ns * 8) : nullptr;
-    int* d_ht = hist_tl ? (int*)dalloc(nb * ns * 4) : nullptr;
-    int* d_hs = hist_status ? (int*)dalloc(nb * ns * 4) : nullptr;
-    int* d_ns = (int*)dalloc(nb * 4);
-    for (void* q : bufs)
-        if (!q) { release(); return fail(MPC_E_ALLOC, "hipMalloc closed-loop buffers"); }
-    if ((hist_x && !d_hx) || (hist_u && !d_hu) || (hist_obs_s && !d_ho) || (hist_tl && !d_ht) || (hist_status && !d_hs)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc closed-loop histories");
-    }
-    hipStream_t st = c->stream;
-    std::vector<hipEvent_t> ev;
-    auto cleanup = [&]() {
-        hipStreamSynchronize(st);
-        for (auto& e : ev)
-            if (e) hipEventDestroy(e);
-        release();
-    };
-    // steps that never run stay NaN / -1 (all-ones bytes)
-    bool ok0 = true;
-    if (d_hx) ok0 = ok0 && hipMemsetAsync(d_hx, 0xff, nb * (ns + 1) * 5 * 8, st) == hipSuccess;
-    if (d_hu) ok0 = ok0 && hipMemsetAsync(d_hu, 0xff, nb * ns * 2 * 8, st) == hipSuccess;
-    if (d_ho) ok0 = ok0 && hipMemsetAsync(d_ho, 0xff, nb * ns * 8, st) == hipSuccess;
-    if (d_ht) ok0 = ok0 && hipMemsetAsync(d_ht, 0xff, nb * ns * 4, st) == hipSuccess;
-    if (d_hs) ok0 = ok0 && hipMemsetAsync(d_hs, 0xff, nb * ns * 4, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok0) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "closed-loop buffer initialisation");
-    }
-    const dim3 tb(256), tg((B + 255) / 256);
-    hipLaunchKernelGGL(cl_init_kernel, tg, tb, 0, st, B, F, C, d_xinit, s_stop, d_hx, d_ns, max_steps);
-    if (step_ms) {
-        ev.assign(ns + 1, nullptr);
-        for (auto& e : ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
-                cleanup();
-                return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
-            }
-        if (hipEventRecord(ev[0], st) != hipSuccess) {
-            cleanup();
-            return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-        }
-    }
-    int steps_run = 0;
-    rc = MPC_SUCCESS;
-    // the solve runs on the egos still in the loop: the list is rebuilt at the host syncs below whenever
-    // egos have left, so retired egos stop costing solver work (results are per ego, unchanged)
-    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-    int nl = 0;
-    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "closed-loop initial ego list");
-    }
-    for (int step = 0; step < max_steps && nl > 0; ++step) {
-        // runs without scenarios too: records the RED light / no-car histories like the reference
-        hipLaunchKernelGGL(cl_fsm_kernel, tg, tb, 0, st, B, F, kp.dt, C, d_ho, d_ht, step, max_steps);
-        const dim3 lg((nl + 255) / 256);
-        hipLaunchKernelGGL(cl_gather_kernel, lg, tb, 0, st, nl, C);
-        rc = launch_solve(c, kp, nl, C.xa, with_fsm ? C.obsa : nullptr, with_fsm ? C.nobsa : nullptr, nullptr, C.u0a,
-                          nullptr, nullptr, C.sta, nullptr, st);
-        if (rc) break;
-        if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
-            rc = fail(MPC_E_DEVICE, "closed-loop active-count reset");
-            break;
-        }
-        hipLaunchKernelGGL(cl_plant_kernel, lg, tb, 0, st, c->tab, nl, kp.dt, C, s_stop, d_hx, d_hu, d_hs, d_ns, step,
-                           max_steps);
-        if (step_ms && hipEventRecord(ev[step + 1], st) != hipSuccess) {
-            rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-            break;
-        }
-        steps_run = step + 1;
-        if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
-            int na = 0;
-            if (hipMemcpyAsync(&na, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "closed-loop step sync");
-                break;
-            }
-            if (na == 0) break;
-            if (na < nl) {                                  // egos left: shrink the solver's list
-                hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-                if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    rc = fail(MPC_E_DEVICE, "closed-loop ego list");
-                    break;
-                }
-            }
-        }
-    }
-    if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "closed-loop kernel launch");
-    if (rc == MPC_SUCCESS) {
-        bool ok = hipMemcpyAsync(n_steps, d_ns, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (hist_x) ok = ok && hipMemcpyAsync(hist_x, d_hx, nb * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (hist_u) ok = ok && hipMemcpyAsync(hist_u, d_hu, nb * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (hist_obs_s) ok = ok && hipMemcpyAsync(hist_obs_s, d_ho, nb * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, d_ht, nb * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (hist_status) ok = ok && hipMemcpyAsync(hist_status, d_hs, nb * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-        ok = ok && hipStreamSynchronize(st) == hipSuccess;
-        if (!ok) rc = fail(MPC_E_DEVICE, "closed-loop copy-back");
-    }
-    if (step_ms) {
-        for (size_t i = 0; i < ns; ++i) {
-            float ms = NAN;
-            if ((int)i < steps_run && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) ms = NAN;
-            step_ms[i] = ms;
-        }
-    }
-    cleanup();
+    ClDriver D(c, "closed-loop", B, max_steps);
+    const size_t nb = D.nb, ns = D.ns;
+    const hipStream_t st = D.st;
+    D.cl_state(x_init, 2, true);
+    const ClState& C = D.C;
+    int* d_ns = D.out(n_steps, nb, false);  // histories of every ego: [B] rows
+    double* d_hx = D.out(hist_x, nb * (ns + 1) * 5);
+    double* d_hu = D.out(hist_u, nb * ns * 2);
+    double* d_ho = D.out(hist_obs_s, nb * ns);
+    int* d_ht = D.out(hist_tl, nb * ns);
+    int* d_hs = D.out(hist_status, nb * ns);
+    rc = D.begin();
+    if (rc) return rc;
+    hipLaunchKernelGGL(cl_init_kernel, D.tg, D.tb, 0, st, B, F, C, D.xinit, s_stop, d_hx, d_ns, max_steps);
+    rc = D.run(kp, with_fsm, step_ms != nullptr,
+               [&](int step, int nl, dim3 lg) {
+                   // runs without scenarios too: records the RED light / no-car histories like the reference
+                   hipLaunchKernelGGL(cl_fsm_kernel, D.tg, D.tb, 0, st, B, F, kp.dt, C, d_ho, d_ht, step, max_steps);
+                   hipLaunchKernelGGL(cl_gather_kernel, lg, D.tb, 0, st, nl, C);
+               },
+               [&](int step, int nl, dim3 lg) {
+                   hipLaunchKernelGGL(cl_plant_kernel, lg, D.tb, 0, st, c->tab, nl, kp.dt, C, s_stop, d_hx, d_hu, d_hs,
+                                      d_ns, step, max_steps);
+               });
+    if (rc == MPC_SUCCESS && !(D.fetch() && hipStreamSynchronize(st) == hipSuccess))
+        rc = fail(MPC_E_DEVICE, "closed-loop copy-back");
+    if (step_ms) D.fill_step_ms(step_ms);
     return rc;
 }
 
 // mpc_closed_loop with a scenario per ego, the check quantities accumulated on the device and histories for
-// the named egos only (include/mpcqp.h).  Device allocations: the closed loop's per-ego state (ClState), the
-// scenarios [B] when they differ, the quantities [MPC_CL_NQ][B], two int arrays [B] (flags, history slots),
-// n_steps [B] and the kept histories [n_hist][max_steps ..]: O(B) + O(n_hist * max_steps).  Step times come
-// from a ring of SW_EVENTS events read at the every-8-steps host sync
-#define SW_EVENTS 9
+// the named egos only (include/mpcqp.h)
 extern "C" int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, const mpc_fsm* fsm, int n_fsm,
                                      int max_steps, double s_stop, double* quant, int n_hist, const int* hist_egos,
                                      double* hist_x, double* hist_u, double* hist_obs_s, int* hist_tl,
@@ -831,26 +727,14 @@ extern "C" int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, co
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
     if (fsm ? !(n_fsm == 1 || n_fsm == B) : n_fsm != 0)
         return fail(MPC_E_ARG, "n_fsm must be B (a scenario per ego), 1 (shared) or 0 with fsm NULL");
-    if (!quant) return fail(MPC_E_ARG, "quant is required");
-    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
-    if (n_hist == 0 && (hist_x || hist_u || hist_obs_s || hist_tl || hist_status))
-        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
-    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
+    int rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_obs_s || hist_tl || hist_status);
+    if (rc) return rc;
     std::vector<int> slot;
-    try {
-        slot.assign((size_t)B, -1);
-    } catch (const std::bad_alloc&) {
-        return fail(MPC_E_ALLOC, "history slot map");
-    }
-    for (int k = 0; k < n_hist; ++k) {
-        const int e = hist_egos[k];
-        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
-        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
-        slot[e] = k;
-    }
+    rc = cl_slot_map(B, n_hist, hist_egos, slot);
+    if (rc) return rc;
     if (B == 0) return MPC_SUCCESS;
     if (!x_init) return fail(MPC_E_ARG, "x_init is required");
-    int rc = check_params(&c->p);
+    rc = check_params(&c->p);
     if (rc) return rc;
     mpc_fsm F;
     mpc_default_fsm(&F);                             // no scenario: both switches off
@@ -859,180 +743,35 @@ extern "C" int mpc_closed_loop_sweep(mpc_ctx* c, int B, const double* x_init, co
     bool with_fsm = F.dynamic_obstacle || F.traffic_light;
     if (per_ego)
         for (int b = 0; b < B && !with_fsm; ++b) with_fsm = fsm[b].dynamic_obstacle || fsm[b].traffic_light;
-    if (c->cpu) {
-        int hrc = MPC_SUCCESS;
-        const int erc = host_call([&] {
-            hrc = c->cpu->closed_loop_sweep(c->p, B, x_init, per_ego ? fsm : &F, per_ego ? B : 1, with_fsm, max_steps,
-                                            s_stop, quant, n_hist, slot.data(), hist_x, hist_u, hist_obs_s, hist_tl,
-                                            hist_status, n_steps, step_ms);
+    if (c->cpu)
+        return host_loop([&] {
+            return c->cpu->closed_loop_sweep(c->p, B, x_init, per_ego ? fsm : &F, per_ego ? B : 1, with_fsm, max_steps,
+                                             s_stop, quant, n_hist, slot.data(), hist_x, hist_u, hist_obs_s, hist_tl,
+                                             hist_status, n_steps, step_ms);
         });
-        return erc != MPC_SUCCESS ? erc : hrc;
-    }
     KParams kp = kparams(&c->p);
     kp.max_obs = with_fsm ? 2 : 0;          // the FSM yields at most the car and the light
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist;
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    ClState C;
-    C.x = (double*)dalloc(nb * 5 * 8);
-    C.obs = (double*)dalloc(nb * 4 * 8);
-    C.nobs = (int*)dalloc(nb * 4);
-    C.active = (int*)dalloc(nb * 4);
-    C.obs_s = (double*)dalloc(nb * 8);
-    C.tl_timer = (double*)dalloc(nb * 8);
-    C.fsm_flags = (int*)dalloc(nb * 4 * 4);
-    C.n_active = (int*)dalloc(4);
-    C.alist = (int*)dalloc(nb * 4);
-    C.n_list = (int*)dalloc(4);
-    C.xa = (double*)dalloc(nb * 5 * 8);
-    C.obsa = (double*)dalloc(nb * 4 * 8);
-    C.nobsa = (int*)dalloc(nb * 4);
-    C.u0a = (double*)dalloc(nb * 2 * 8);
-    C.sta = (int*)dalloc(nb * 4);
-    double* d_xinit = (double*)dalloc(nb * 5 * 8);
-    SwState S;
-    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
-    S.qflags = (int*)dalloc(nb * 4);
-    int* d_hslot = (int*)dalloc(nb * 4);
-    S.hslot = d_hslot;
-    S.n_steps = (int*)dalloc(nb * 4);
-    mpc_fsm* d_fsm = per_ego ? (mpc_fsm*)dalloc(nb * sizeof(mpc_fsm)) : nullptr;
-    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
-    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
-    S.hist_obs_s = hist_obs_s ? (double*)dalloc(nh * ns * 8) : nullptr;
-    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
-    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
-    for (void* q : bufs)
-        if (!q) { release(); return fail(MPC_E_ALLOC, "hipMalloc sweep buffers"); }
-    if ((per_ego && !d_fsm) || (hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_obs_s && !S.hist_obs_s) ||
-        (hist_tl && !S.hist_tl) || (hist_status && !S.hist_status)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc sweep scenarios / histories");
-    }
-    hipStream_t st = c->stream;
-    hipEvent_t ev[SW_EVENTS] = {};
-    auto cleanup = [&]() {
-        hipStreamSynchronize(st);
-        for (auto& e : ev)
-            if (e) hipEventDestroy(e);
-        release();
-    };
-    // steps that never run stay NaN / -1 (all-ones bytes)
-    bool ok0 = true;
-    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
-    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
-    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
-    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (per_ego) ok0 = ok0 && hipMemcpyAsync(d_fsm, fsm, nb * sizeof(mpc_fsm), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok0) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "sweep buffer initialisation");
-    }
-    const dim3 tb(256), tg((B + 255) / 256);
-    if (per_ego) hipLaunchKernelGGL(sw_init_kernel<true>, tg, tb, 0, st, B, F, d_fsm, C, S, d_xinit, s_stop, max_steps);
-    else hipLaunchKernelGGL(sw_init_kernel<false>, tg, tb, 0, st, B, F, d_fsm, C, S, d_xinit, s_stop, max_steps);
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            e = nullptr;
-            cleanup();
-            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
-        }
-    if (hipEventRecord(ev[0], st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-    }
-    // step i ran between events i and i + 1 of the ring; read at a host sync, at most 8 steps after the last
-    // read, so no event is re-recorded before its interval has been taken
-    std::vector<double> ms;
-    auto read_times = [&](int upto) {
-        for (int i = (int)ms.size(); i < upto; ++i) {
-            float t = NAN;
-            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
-            ms.push_back(t);
-        }
-    };
-    rc = MPC_SUCCESS;
-    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-    int nl = 0;
-    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "sweep initial ego list");
-    }
-    try {
-        for (int step = 0; step < max_steps && nl > 0; ++step) {
-            if (per_ego) hipLaunchKernelGGL(sw_fsm_kernel<true>, tg, tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
-            else hipLaunchKernelGGL(sw_fsm_kernel<false>, tg, tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
-            const dim3 lg((nl + 255) / 256);
-            hipLaunchKernelGGL(cl_gather_kernel, lg, tb, 0, st, nl, C);
-            rc = launch_solve(c, kp, nl, C.xa, with_fsm ? C.obsa : nullptr, with_fsm ? C.nobsa : nullptr, nullptr,
-                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
-            if (rc) break;
-            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "sweep active-count reset");
-                break;
-            }
-            hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, s_stop, step, max_steps);
-            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-                break;
-            }
-            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
-                int na = 0;
-                if (hipMemcpyAsync(&na, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    rc = fail(MPC_E_DEVICE, "sweep step sync");
-                    break;
-                }
-                read_times(step + 1);
-                if (na == 0) break;
-                if (na < nl) {                                  // egos left: shrink the solver's list
-                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess) {
-                        rc = fail(MPC_E_DEVICE, "sweep ego list");
-                        break;
-                    }
-                }
-            }
-        }
-        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "sweep kernel launch");
-        if (rc == MPC_SUCCESS) {
-            std::vector<double> hq(nb * MPC_CL_NQ);
-            std::vector<int> hn(nb);
-            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_obs_s) ok = ok && hipMemcpyAsync(hist_obs_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipStreamSynchronize(st) == hipSuccess;
-            if (!ok) {
-                rc = fail(MPC_E_DEVICE, "sweep copy-back");
-            } else {
-                for (size_t b = 0; b < nb; ++b)               // [MPC_CL_NQ][B] on the device -> [B][MPC_CL_NQ]
-                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
-                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
-                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
-                if (step_ms)
-                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
-            }
-        }
-    } catch (const std::bad_alloc&) {
-        rc = fail(MPC_E_ALLOC, "sweep host buffers");
-    }
-    cleanup();
-    return rc;
+    ClDriver D(c, "sweep", B, max_steps);
+    const hipStream_t st = D.st;
+    D.cl_state(x_init, 2, true);
+    const ClState& C = D.C;
+    const SwState S = D.sw_state(slot.data(), n_hist, hist_x, hist_u, hist_obs_s, hist_tl, hist_status);
+    const mpc_fsm* d_fsm = per_ego ? D.in(fsm, D.nb, D.nb) : nullptr;     // the scenarios [B] when they differ
+    rc = D.begin();
+    if (rc) return rc;
+    if (per_ego) hipLaunchKernelGGL(sw_init_kernel<true>, D.tg, D.tb, 0, st, B, F, d_fsm, C, S, D.xinit, s_stop, max_steps);
+    else hipLaunchKernelGGL(sw_init_kernel<false>, D.tg, D.tb, 0, st, B, F, d_fsm, C, S, D.xinit, s_stop, max_steps);
+    rc = D.run(kp, with_fsm, true,
+               [&](int step, int nl, dim3 lg) {
+                   if (per_ego) hipLaunchKernelGGL(sw_fsm_kernel<true>, D.tg, D.tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
+                   else hipLaunchKernelGGL(sw_fsm_kernel<false>, D.tg, D.tb, 0, st, B, F, d_fsm, kp.dt, C, S, step, max_steps);
+                   hipLaunchKernelGGL(cl_gather_kernel, lg, D.tb, 0, st, nl, C);
+               },
+               [&](int step, int nl, dim3 lg) {
+                   hipLaunchKernelGGL(sw_plant_kernel, lg, D.tb, 0, st, c->tab, B, nl, kp.dt, C, S, s_stop, step, max_steps);
+               });
+    return rc ? rc : D.finish(S, nullptr, 0, quant, nullptr, n_steps, step_ms);
 }
 
 extern "C" int mpc_cl_verdicts(const mpc_ctx* c, int B, const double* quant, double s_total, int* verdicts,
@@ -1060,11 +799,143 @@ extern "C" void mpc_actors_from_fsm(const mpc_fsm* f, mpc_actor out[2]) {
     }
 }
 
-// mpc_closed_loop_sweep with a script of A actors per ego (include/mpcqp.h): the same loop, plant kernel,
-// compaction and event ring around tr_fsm_kernel / tr_gather_kernel and an A-wide slab.  Device allocations: the
-// per-ego state and packed solver buffers [B], the per-actor state and the slab [A][B], the scripts [B][A] (or
-// [A] when shared), the quantities and extras, and the kept histories [n_hist][max_steps ..(A)]:
-// O(B * A) + O(n_hist * max_steps * A)
+extern "C" void mpc_default_noise(mpc_noise* n) { std::memset(n, 0, sizeof(*n)); }
+
+// What the three scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
+// worlds, K == 0), mpc_closed_loop_convoy, and mpc_closed_loop_noisy (noisy; noise is then never NULL)
+struct ScriptedLoop {
+    const char* label;
+    int B, W, K;
+    double lead_range;
+    const double* x_init;
+    const mpc_actor* actors;
+    int A, n_scripts;
+    bool with_slab, noisy;
+    const mpc_noise* noise;
+    int n_noise;
+    unsigned long long seed;
+    long long ego_offset;
+    int max_steps;
+    double s_stop;
+    double *quant, *extra;
+    int nx;                                 // the width of extra: MPC_TR_NX, MPC_CV_NX or MPC_NZ_NX
+    int n_hist;
+    const int* hist_egos;
+    double *hist_x, *hist_u, *hist_ua, *hist_xm, *hist_car_s;
+    int *hist_tl, *hist_status, *hist_nobs;
+    double* hist_slab;
+    int* hist_lead;
+    int* n_steps;
+    double* step_ms;
+};
+
+// The loop of the scripted entries around tr_fsm_kernel and an (A + K)-wide slab.  With worlds, cv_lead_kernel
+// ranks the leaders between the FSM and the gather and writes the slab histories (tr_fsm_kernel's rows are A
+// wide).  Noisy: nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel, on the field-major
+// sigma table [14][B] for per-ego noise; the other kernels are reused untouched and see the true states
+static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
+    const int B = a.B, A = a.A, K = a.K, AK = A + K, max_steps = a.max_steps;
+    std::vector<int> slot;
+    int rc = cl_slot_map(B, a.n_hist, a.hist_egos, slot);
+    if (rc) return rc;
+    if (B == 0) return MPC_SUCCESS;
+    if (!a.x_init) return fail(MPC_E_ARG, "x_init is required");
+    rc = check_params(&c->p);
+    if (rc) return rc;
+    const bool per_ego = a.n_scripts == B && B > 1;  // n_scripts == B == 1 is the shared case
+    const int nsc = per_ego ? B : (a.actors ? 1 : 0);
+    const bool nz_per_ego = a.noisy && a.n_noise == B && B > 1;
+    if (c->cpu)
+        return host_loop([&] {
+            const int hsc = nsc == 0 ? 1 : nsc;
+            if (a.noisy)
+                return c->cpu->closed_loop_noisy(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
+                                                 a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
+                                                 a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
+                                                 a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
+                                                 a.hist_slab, a.hist_lead, a.n_steps, a.step_ms);
+            if (a.W)
+                return c->cpu->closed_loop_convoy(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
+                                                  max_steps, a.s_stop, a.quant, a.extra, a.n_hist, slot.data(), a.hist_x,
+                                                  a.hist_u, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
+                                                  a.hist_slab, a.hist_lead, a.n_steps, a.step_ms);
+            return c->cpu->closed_loop_traffic(c->p, B, a.x_init, a.actors, A, hsc, a.with_slab, max_steps, a.s_stop,
+                                               a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_car_s,
+                                               a.hist_tl, a.hist_status, a.hist_nobs, a.hist_slab, a.n_steps, a.step_ms);
+        });
+    KParams kp = kparams(&c->p);
+    kp.max_obs = a.with_slab ? AK : 0;      // every actor and every leader adds at most one entry
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    std::vector<double> hsig;               // per-ego sigmas, field-major: the loads of a wave coalesce
+    if (nz_per_ego) {
+        try {
+            hsig.resize((size_t)B * NZ_NSIG);
+        } catch (const std::bad_alloc&) {
+            return fail(MPC_E_ALLOC, "noise table");
+        }
+        for (size_t b = 0; b < (size_t)B; ++b)   // mpc_noise is NZ_NSIG doubles, no padding
+            for (size_t f = 0; f < NZ_NSIG; ++f)
+                hsig[f * (size_t)B + b] = reinterpret_cast<const double*>(a.noise + b)[f];
+    }
+    ClDriver D(c, a.label, B, max_steps);
+    const hipStream_t st = D.st;
+    const size_t nhs = (size_t)a.n_hist * D.ns;
+    D.cl_state(a.x_init, (size_t)AK, false);
+    const ClState& C = D.C;
+    SwState S = D.sw_state(slot.data(), a.n_hist, a.hist_x, a.hist_u, a.hist_car_s, a.hist_tl, a.hist_status);
+    TrState T = D.tr_state(a.actors, A, nsc, per_ego, (size_t)AK, a.nx, a.n_hist, a.hist_nobs);
+    CvState V = {};
+    V.W = a.W;
+    V.K = K;
+    V.lead_range = a.lead_range;
+    if (a.W) {
+        V.hist_slab = D.out(a.hist_slab, nhs * (size_t)AK * 2);
+        V.hist_lead = D.out(a.hist_lead, nhs * (size_t)K);
+    } else {
+        T.hist_slab = D.out(a.hist_slab, nhs * (size_t)A * 2);
+    }
+    NzState Z = {};
+    if (a.noisy) {
+        mpc_noise zero;
+        mpc_default_noise(&zero);
+        Z.sig = nz_per_ego ? D.in(hsig.data(), hsig.size(), hsig.size()) : nullptr;
+        Z.shared = nz_per_ego ? zero : a.noise[0];
+        Z.k0 = (unsigned)(a.seed & 0xffffffffull);
+        Z.k1 = (unsigned)(a.seed >> 32);
+        Z.g0 = (unsigned long long)a.ego_offset;
+        Z.u_min0 = c->p.u_min[0];
+        Z.u_min1 = c->p.u_min[1];
+        Z.u_max0 = c->p.u_max[0];
+        Z.u_max1 = c->p.u_max[1];
+        Z.hist_ua = D.out(a.hist_ua, nhs * 2);
+        Z.hist_xm = D.out(a.hist_xm, nhs * 5);
+    }
+    rc = D.begin();
+    if (rc) return rc;
+    const dim3 tb = D.tb, tg = D.tg;
+    const dim3 wb(64 * ((a.W + 63) / 64)), wg(a.W ? B / a.W : 1);    // a workgroup per world
+    hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, D.xinit, a.s_stop, max_steps);
+    if (a.W) hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
+    if (a.noisy) hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
+    rc = D.run(kp, a.with_slab, true,
+               [&](int step, int nl, dim3 lg) {
+                   hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
+                   if (a.W) hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
+                   if (a.noisy) hipLaunchKernelGGL(nz_measure_kernel, lg, tb, 0, st, nl, B, AK, C, S, T, Z, step, max_steps);
+                   else hipLaunchKernelGGL(tr_gather_kernel, lg, tb, 0, st, nl, B, AK, C, T);
+               },
+               [&](int step, int nl, dim3 lg) {
+                   if (a.noisy)
+                       hipLaunchKernelGGL(nz_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, T, Z, a.s_stop, step,
+                                          max_steps);
+                   else
+                       hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, a.s_stop, step,
+                                          max_steps);
+               });
+    return rc ? rc : D.finish(S, T.ex, a.nx, a.quant, a.extra, a.n_steps, a.step_ms);
+}
+
+// mpc_closed_loop_sweep with a script of A actors per ego (include/mpcqp.h)
 extern "C" int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, const mpc_actor* actors, int A,
                                        int n_scripts, int max_steps, double s_stop, double* quant, double* extra,
                                        int n_hist, const int* hist_egos, double* hist_x, double* hist_u,
@@ -1072,237 +943,19 @@ extern "C" int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, 
                                        double* hist_slab, int* n_steps, double* step_ms) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
-    if (A < 0 || A > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A out of range [0, 16]");
-    if (actors ? !(n_scripts == 1 || n_scripts == B) : n_scripts != 0)
-        return fail(MPC_E_ARG, "n_scripts must be B (a script per ego), 1 (shared) or 0 with actors NULL");
-    if (!actors && A != 0) return fail(MPC_E_ARG, "actors is NULL but A > 0");
-    if (!quant) return fail(MPC_E_ARG, "quant is required");
-    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
-    if (n_hist == 0 && (hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs || hist_slab))
-        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
-    if (hist_slab && A == 0) return fail(MPC_E_ARG, "hist_slab is given but A == 0");
-    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
     bool with_slab = false;
-    for (size_t k = 0; k < (size_t)n_scripts * (size_t)A; ++k) {
-        if (actors[k].kind < MPC_ACTOR_NONE || actors[k].kind > MPC_ACTOR_LIGHT)
-            return fail(MPC_E_ARG, "actor kind outside MPC_ACTOR_NONE .. MPC_ACTOR_LIGHT");
-        with_slab = with_slab || actors[k].kind != MPC_ACTOR_NONE;
-    }
-    std::vector<int> slot;
-    try {
-        slot.assign((size_t)B, -1);
-    } catch (const std::bad_alloc&) {
-        return fail(MPC_E_ALLOC, "history slot map");
-    }
-    for (int k = 0; k < n_hist; ++k) {
-        const int e = hist_egos[k];
-        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
-        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
-        slot[e] = k;
-    }
-    if (B == 0) return MPC_SUCCESS;
-    if (!x_init) return fail(MPC_E_ARG, "x_init is required");
-    int rc = check_params(&c->p);
+    int rc = cl_check_script(actors, A, n_scripts, B, with_slab);
     if (rc) return rc;
-    const bool per_ego = n_scripts == B && B > 1;    // n_scripts == B == 1 is the shared case
-    const int nsc = per_ego ? B : (actors ? 1 : 0);
-    if (c->cpu) {
-        int hrc = MPC_SUCCESS;
-        const int erc = host_call([&] {
-            hrc = c->cpu->closed_loop_traffic(c->p, B, x_init, actors, A, nsc == 0 ? 1 : nsc, with_slab, max_steps,
-                                              s_stop, quant, extra, n_hist, slot.data(), hist_x, hist_u, hist_car_s,
-                                              hist_tl, hist_status, hist_nobs, hist_slab, n_steps, step_ms);
-        });
-        return erc != MPC_SUCCESS ? erc : hrc;
-    }
-    KParams kp = kparams(&c->p);
-    kp.max_obs = with_slab ? A : 0;          // every actor emits at most one entry
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A;
-    const size_t na1 = na ? na : 1;          // no zero-sized allocation
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    ClState C = {};                          // obs, obs_s, tl_timer, fsm_flags stay null: TrState holds them
-    C.x = (double*)dalloc(nb * 5 * 8);
-    C.nobs = (int*)dalloc(nb * 4);
-    C.active = (int*)dalloc(nb * 4);
-    C.n_active = (int*)dalloc(4);
-    C.alist = (int*)dalloc(nb * 4);
-    C.n_list = (int*)dalloc(4);
-    C.xa = (double*)dalloc(nb * 5 * 8);
-    C.obsa = (double*)dalloc(nb * na1 * 2 * 8);
-    C.nobsa = (int*)dalloc(nb * 4);
-    C.u0a = (double*)dalloc(nb * 2 * 8);
-    C.sta = (int*)dalloc(nb * 4);
-    double* d_xinit = (double*)dalloc(nb * 5 * 8);
-    SwState S = {};
-    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
-    S.qflags = (int*)dalloc(nb * 4);
-    int* d_hslot = (int*)dalloc(nb * 4);
-    S.hslot = d_hslot;
-    S.n_steps = (int*)dalloc(nb * 4);
-    TrState T = {};
-    mpc_actor* d_actors = (mpc_actor*)dalloc((per_ego ? nb : 1) * na1 * sizeof(mpc_actor));
-    T.actors = d_actors;
-    T.per_ego = per_ego ? 1 : 0;
-    T.aval = (double*)dalloc(nb * na1 * 8);
-    T.aflags = (int*)dalloc(nb * na1 * 4);
-    T.slab = (double*)dalloc(nb * na1 * 2 * 8);
-    T.ex = (double*)dalloc(nb * MPC_TR_NX * 8);
-    if (!C.x || !C.nobs || !C.active || !C.n_active || !C.alist || !C.n_list || !C.xa || !C.obsa || !C.nobsa ||
-        !C.u0a || !C.sta || !d_xinit || !S.q || !S.qflags || !d_hslot || !S.n_steps || !d_actors || !T.aval ||
-        !T.aflags || !T.slab || !T.ex) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc traffic buffers");
-    }
-    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
-    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
-    S.hist_obs_s = hist_car_s ? (double*)dalloc(nh * ns * 8) : nullptr;
-    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
-    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_nobs = hist_nobs ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_slab = hist_slab ? (double*)dalloc(nh * ns * na * 2 * 8) : nullptr;
-    if ((hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_car_s && !S.hist_obs_s) || (hist_tl && !S.hist_tl) ||
-        (hist_status && !S.hist_status) || (hist_nobs && !T.hist_nobs) || (hist_slab && !T.hist_slab)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc traffic histories");
-    }
-    hipStream_t st = c->stream;
-    hipEvent_t ev[SW_EVENTS] = {};
-    auto cleanup = [&]() {
-        hipStreamSynchronize(st);
-        for (auto& e : ev)
-            if (e) hipEventDestroy(e);
-        release();
-    };
-    // steps that never run stay NaN / -1 (all-ones bytes)
-    bool ok0 = true;
-    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
-    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
-    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
-    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (T.hist_nobs) ok0 = ok0 && hipMemsetAsync(T.hist_nobs, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (T.hist_slab) ok0 = ok0 && hipMemsetAsync(T.hist_slab, 0xff, nh * ns * na * 2 * 8, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (nsc > 0 && A > 0)
-        ok0 = ok0 && hipMemcpyAsync(d_actors, actors, (size_t)nsc * na * sizeof(mpc_actor), hipMemcpyHostToDevice,
-                                    st) == hipSuccess;
-    if (!ok0) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "traffic buffer initialisation");
-    }
-    const dim3 tb(256), tg((B + 255) / 256);
-    hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, d_xinit, s_stop, max_steps);
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            e = nullptr;
-            cleanup();
-            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
-        }
-    if (hipEventRecord(ev[0], st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-    }
-    // the sweep's ring: step i ran between events i and i + 1, read at a host sync at most 8 steps later
-    std::vector<double> ms;
-    auto read_times = [&](int upto) {
-        for (int i = (int)ms.size(); i < upto; ++i) {
-            float t = NAN;
-            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
-            ms.push_back(t);
-        }
-    };
-    rc = MPC_SUCCESS;
-    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-    int nl = 0;
-    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "traffic initial ego list");
-    }
-    try {
-        for (int step = 0; step < max_steps && nl > 0; ++step) {
-            hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
-            const dim3 lg((nl + 255) / 256);
-            hipLaunchKernelGGL(tr_gather_kernel, lg, tb, 0, st, nl, B, A, C, T);
-            rc = launch_solve(c, kp, nl, C.xa, with_slab ? C.obsa : nullptr, with_slab ? C.nobsa : nullptr, nullptr,
-                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
-            if (rc) break;
-            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "traffic active-count reset");
-                break;
-            }
-            hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, s_stop, step, max_steps);
-            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-                break;
-            }
-            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
-                int nact = 0;
-                if (hipMemcpyAsync(&nact, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    rc = fail(MPC_E_DEVICE, "traffic step sync");
-                    break;
-                }
-                read_times(step + 1);
-                if (nact == 0) break;
-                if (nact < nl) {                                // egos left: shrink the solver's list
-                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess) {
-                        rc = fail(MPC_E_DEVICE, "traffic ego list");
-                        break;
-                    }
-                }
-            }
-        }
-        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "traffic kernel launch");
-        if (rc == MPC_SUCCESS) {
-            std::vector<double> hq(nb * MPC_CL_NQ), hx(extra ? nb * MPC_TR_NX : 0);
-            std::vector<int> hn(nb);
-            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (extra) ok = ok && hipMemcpyAsync(hx.data(), T.ex, nb * MPC_TR_NX * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_car_s) ok = ok && hipMemcpyAsync(hist_car_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_nobs) ok = ok && hipMemcpyAsync(hist_nobs, T.hist_nobs, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_slab) ok = ok && hipMemcpyAsync(hist_slab, T.hist_slab, nh * ns * na * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipStreamSynchronize(st) == hipSuccess;
-            if (!ok) {
-                rc = fail(MPC_E_DEVICE, "traffic copy-back");
-            } else {
-                for (size_t b = 0; b < nb; ++b) {             // column-major on the device -> one row per ego
-                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
-                    if (extra)
-                        for (int k = 0; k < MPC_TR_NX; ++k) extra[b * MPC_TR_NX + k] = hx[(size_t)k * nb + b];
-                }
-                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
-                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
-                if (step_ms)
-                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
-            }
-        }
-    } catch (const std::bad_alloc&) {
-        rc = fail(MPC_E_ALLOC, "traffic host buffers");
-    }
-    cleanup();
-    return rc;
+    rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs || hist_slab);
+    if (rc) return rc;
+    if (hist_slab && A == 0) return fail(MPC_E_ARG, "hist_slab is given but A == 0");
+    const ScriptedLoop a = {"traffic", B, 0, 0, INFINITY, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
+                            max_steps, s_stop, quant, extra, MPC_TR_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
+                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps, step_ms};
+    return scripted_loop(c, a);
 }
 
-// mpc_closed_loop_traffic with the egos of a world as each other's obstacles (include/mpcqp.h): the same loop,
-// with cv_lead_kernel between tr_fsm_kernel and the gather and an (A + K)-wide slab.  Device allocations: the
-// traffic entry's with A + K for the slab width, and hist_lead [n_hist][max_steps][K]:
-// O(B * (A + K)) + O(n_hist * max_steps * (A + K))
+// mpc_closed_loop_traffic with the egos of a world as each other's obstacles (include/mpcqp.h)
 extern "C" int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
                                       const mpc_actor* actors, int A, int n_scripts, int max_steps, double s_stop,
                                       double* quant, double* extra, int n_hist, const int* hist_egos, double* hist_x,
@@ -1311,263 +964,24 @@ extern "C" int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double le
                                       double* step_ms) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
-    if (W < 1 || W > MPC_MAX_WORLD) return fail(MPC_E_ARG, "W out of range [1, 256]");
-    if (B % W != 0) return fail(MPC_E_ARG, "B is not a multiple of W");
-    if (A < 0 || A > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A out of range [0, 16]");
-    if (K < 0 || K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "K out of range [0, 16]");
-    if (A + K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A + K > 16");
-    if (!(lead_range > 0.0)) return fail(MPC_E_ARG, "lead_range must be > 0 (+inf allowed)");
-    if (actors ? !(n_scripts == 1 || n_scripts == B) : n_scripts != 0)
-        return fail(MPC_E_ARG, "n_scripts must be B (a script per ego), 1 (shared) or 0 with actors NULL");
-    if (!actors && A != 0) return fail(MPC_E_ARG, "actors is NULL but A > 0");
-    if (!quant) return fail(MPC_E_ARG, "quant is required");
-    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
-    if (n_hist == 0 &&
-        (hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs || hist_slab || hist_lead))
-        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
+    int rc = cl_check_world(B, W, K, A, lead_range);
+    if (rc) return rc;
+    bool with_slab = K > 0 && W > 1;
+    rc = cl_check_script(actors, A, n_scripts, B, with_slab);
+    if (rc) return rc;
+    rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs ||
+                                             hist_slab || hist_lead);
+    if (rc) return rc;
     if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
     if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
-    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
-    bool with_slab = K > 0 && W > 1;
-    for (size_t k = 0; k < (size_t)n_scripts * (size_t)A; ++k) {
-        if (actors[k].kind < MPC_ACTOR_NONE || actors[k].kind > MPC_ACTOR_LIGHT)
-            return fail(MPC_E_ARG, "actor kind outside MPC_ACTOR_NONE .. MPC_ACTOR_LIGHT");
-        with_slab = with_slab || actors[k].kind != MPC_ACTOR_NONE;
-    }
-    std::vector<int> slot;
-    try {
-        slot.assign((size_t)B, -1);
-    } catch (const std::bad_alloc&) {
-        return fail(MPC_E_ALLOC, "history slot map");
-    }
-    for (int k = 0; k < n_hist; ++k) {
-        const int e = hist_egos[k];
-        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
-        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
-        slot[e] = k;
-    }
-    if (B == 0) return MPC_SUCCESS;
-    if (!x_init) return fail(MPC_E_ARG, "x_init is required");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    const bool per_ego = n_scripts == B && B > 1;    // n_scripts == B == 1 is the shared case
-    const int nsc = per_ego ? B : (actors ? 1 : 0);
-    const int AK = A + K;
-    if (c->cpu) {
-        int hrc = MPC_SUCCESS;
-        const int erc = host_call([&] {
-            hrc = c->cpu->closed_loop_convoy(c->p, B, W, K, lead_range, x_init, actors, A, nsc == 0 ? 1 : nsc,
-                                             with_slab, max_steps, s_stop, quant, extra, n_hist, slot.data(), hist_x,
-                                             hist_u, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead,
-                                             n_steps, step_ms);
-        });
-        return erc != MPC_SUCCESS ? erc : hrc;
-    }
-    KParams kp = kparams(&c->p);
-    kp.max_obs = with_slab ? AK : 0;         // every actor and every leader adds at most one entry
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
-    const size_t nak = (size_t)AK;
-    const size_t na1 = na ? na : 1, nak1 = nak ? nak : 1;    // no zero-sized allocation
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    ClState C = {};                          // obs, obs_s, tl_timer, fsm_flags stay null: TrState holds them
-    C.x = (double*)dalloc(nb * 5 * 8);
-    C.nobs = (int*)dalloc(nb * 4);
-    C.active = (int*)dalloc(nb * 4);
-    C.n_active = (int*)dalloc(4);
-    C.alist = (int*)dalloc(nb * 4);
-    C.n_list = (int*)dalloc(4);
-    C.xa = (double*)dalloc(nb * 5 * 8);
-    C.obsa = (double*)dalloc(nb * nak1 * 2 * 8);
-    C.nobsa = (int*)dalloc(nb * 4);
-    C.u0a = (double*)dalloc(nb * 2 * 8);
-    C.sta = (int*)dalloc(nb * 4);
-    double* d_xinit = (double*)dalloc(nb * 5 * 8);
-    SwState S = {};
-    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
-    S.qflags = (int*)dalloc(nb * 4);
-    int* d_hslot = (int*)dalloc(nb * 4);
-    S.hslot = d_hslot;
-    S.n_steps = (int*)dalloc(nb * 4);
-    TrState T = {};
-    mpc_actor* d_actors = (mpc_actor*)dalloc((per_ego ? nb : 1) * na1 * sizeof(mpc_actor));
-    T.actors = d_actors;
-    T.per_ego = per_ego ? 1 : 0;
-    T.aval = (double*)dalloc(nb * na1 * 8);
-    T.aflags = (int*)dalloc(nb * na1 * 4);
-    T.slab = (double*)dalloc(nb * nak1 * 2 * 8);
-    T.ex = (double*)dalloc(nb * MPC_CV_NX * 8);
-    if (!C.x || !C.nobs || !C.active || !C.n_active || !C.alist || !C.n_list || !C.xa || !C.obsa || !C.nobsa ||
-        !C.u0a || !C.sta || !d_xinit || !S.q || !S.qflags || !d_hslot || !S.n_steps || !d_actors || !T.aval ||
-        !T.aflags || !T.slab || !T.ex) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc convoy buffers");
-    }
-    CvState V = {};
-    V.W = W;
-    V.K = K;
-    V.lead_range = lead_range;
-    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
-    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
-    S.hist_obs_s = hist_car_s ? (double*)dalloc(nh * ns * 8) : nullptr;
-    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
-    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_nobs = hist_nobs ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_slab = nullptr;                   // tr_fsm_kernel's rows are A wide: cv_lead_kernel writes the rows
-    V.hist_slab = hist_slab ? (double*)dalloc(nh * ns * nak * 2 * 8) : nullptr;
-    V.hist_lead = hist_lead ? (int*)dalloc(nh * ns * nk * 4) : nullptr;
-    if ((hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_car_s && !S.hist_obs_s) || (hist_tl && !S.hist_tl) ||
-        (hist_status && !S.hist_status) || (hist_nobs && !T.hist_nobs) || (hist_slab && !V.hist_slab) ||
-        (hist_lead && !V.hist_lead)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc convoy histories");
-    }
-    hipStream_t st = c->stream;
-    hipEvent_t ev[SW_EVENTS] = {};
-    auto cleanup = [&]() {
-        hipStreamSynchronize(st);
-        for (auto& e : ev)
-            if (e) hipEventDestroy(e);
-        release();
-    };
-    // steps that never run stay NaN / -1 (all-ones bytes)
-    bool ok0 = true;
-    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
-    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
-    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
-    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (T.hist_nobs) ok0 = ok0 && hipMemsetAsync(T.hist_nobs, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (V.hist_slab) ok0 = ok0 && hipMemsetAsync(V.hist_slab, 0xff, nh * ns * nak * 2 * 8, st) == hipSuccess;
-    if (V.hist_lead) ok0 = ok0 && hipMemsetAsync(V.hist_lead, 0xff, nh * ns * nk * 4, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (nsc > 0 && A > 0)
-        ok0 = ok0 && hipMemcpyAsync(d_actors, actors, (size_t)nsc * na * sizeof(mpc_actor), hipMemcpyHostToDevice,
-                                    st) == hipSuccess;
-    if (!ok0) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "convoy buffer initialisation");
-    }
-    const dim3 tb(256), tg((B + 255) / 256);
-    const dim3 wb(64 * ((W + 63) / 64)), wg(B / W);          // a workgroup per world
-    hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, d_xinit, s_stop, max_steps);
-    hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            e = nullptr;
-            cleanup();
-            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
-        }
-    if (hipEventRecord(ev[0], st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-    }
-    // the sweep's ring: step i ran between events i and i + 1, read at a host sync at most 8 steps later
-    std::vector<double> ms;
-    auto read_times = [&](int upto) {
-        for (int i = (int)ms.size(); i < upto; ++i) {
-            float t = NAN;
-            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
-            ms.push_back(t);
-        }
-    };
-    rc = MPC_SUCCESS;
-    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-    int nl = 0;
-    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "convoy initial ego list");
-    }
-    try {
-        for (int step = 0; step < max_steps && nl > 0; ++step) {
-            hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
-            hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
-            const dim3 lg((nl + 255) / 256);
-            hipLaunchKernelGGL(tr_gather_kernel, lg, tb, 0, st, nl, B, AK, C, T);
-            rc = launch_solve(c, kp, nl, C.xa, with_slab ? C.obsa : nullptr, with_slab ? C.nobsa : nullptr, nullptr,
-                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
-            if (rc) break;
-            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "convoy active-count reset");
-                break;
-            }
-            hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, s_stop, step, max_steps);
-            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-                break;
-            }
-            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
-                int nact = 0;
-                if (hipMemcpyAsync(&nact, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    rc = fail(MPC_E_DEVICE, "convoy step sync");
-                    break;
-                }
-                read_times(step + 1);
-                if (nact == 0) break;
-                if (nact < nl) {                                // egos left: shrink the solver's list
-                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess) {
-                        rc = fail(MPC_E_DEVICE, "convoy ego list");
-                        break;
-                    }
-                }
-            }
-        }
-        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "convoy kernel launch");
-        if (rc == MPC_SUCCESS) {
-            std::vector<double> hq(nb * MPC_CL_NQ), hx(extra ? nb * MPC_CV_NX : 0);
-            std::vector<int> hn(nb);
-            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (extra) ok = ok && hipMemcpyAsync(hx.data(), T.ex, nb * MPC_CV_NX * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_car_s) ok = ok && hipMemcpyAsync(hist_car_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_nobs) ok = ok && hipMemcpyAsync(hist_nobs, T.hist_nobs, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_slab) ok = ok && hipMemcpyAsync(hist_slab, V.hist_slab, nh * ns * nak * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_lead) ok = ok && hipMemcpyAsync(hist_lead, V.hist_lead, nh * ns * nk * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipStreamSynchronize(st) == hipSuccess;
-            if (!ok) {
-                rc = fail(MPC_E_DEVICE, "convoy copy-back");
-            } else {
-                for (size_t b = 0; b < nb; ++b) {             // column-major on the device -> one row per ego
-                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
-                    if (extra)
-                        for (int k = 0; k < MPC_CV_NX; ++k) extra[b * MPC_CV_NX + k] = hx[(size_t)k * nb + b];
-                }
-                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
-                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
-                if (step_ms)
-                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
-            }
-        }
-    } catch (const std::bad_alloc&) {
-        rc = fail(MPC_E_ALLOC, "convoy host buffers");
-    }
-    cleanup();
-    return rc;
+    const ScriptedLoop a = {"convoy", B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
+                            max_steps, s_stop, quant, extra, MPC_CV_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
+                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms};
+    return scripted_loop(c, a);
 }
 
-extern "C" void mpc_default_noise(mpc_noise* n) { std::memset(n, 0, sizeof(*n)); }
-
-// mpc_closed_loop_convoy with seeded noise between the world and the solver (include/mpcqp.h): the same loop with
-// nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel; tr_fsm_kernel, cv_lead_kernel,
-// cl_compact_kernel and launch_solve are reused untouched and see the true states.  noise == NULL runs the same
-// kernels on an all-zero shared struct.  Device allocations: the convoy entry's, extras MPC_NZ_NX wide, the
-// field-major sigma table [14][B] for per-ego noise, hist_ua and hist_xm:
-// O(B * (A + K)) + O(n_hist * max_steps * (A + K))
+// mpc_closed_loop_convoy with seeded noise between the world and the solver (include/mpcqp.h).  noise == NULL runs
+// the same kernels on an all-zero shared struct
 extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
                                      const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise,
                                      int n_noise, unsigned long long seed, long long ego_offset, int max_steps,
@@ -1577,294 +991,30 @@ extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lea
                                      double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
-    if (W < 1 || W > MPC_MAX_WORLD) return fail(MPC_E_ARG, "W out of range [1, 256]");
-    if (B % W != 0) return fail(MPC_E_ARG, "B is not a multiple of W");
-    if (A < 0 || A > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A out of range [0, 16]");
-    if (K < 0 || K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "K out of range [0, 16]");
-    if (A + K > MPC_MAX_ACTORS) return fail(MPC_E_ARG, "A + K > 16");
-    if (!(lead_range > 0.0)) return fail(MPC_E_ARG, "lead_range must be > 0 (+inf allowed)");
-    if (actors ? !(n_scripts == 1 || n_scripts == B) : n_scripts != 0)
-        return fail(MPC_E_ARG, "n_scripts must be B (a script per ego), 1 (shared) or 0 with actors NULL");
-    if (!actors && A != 0) return fail(MPC_E_ARG, "actors is NULL but A > 0");
+    int rc = cl_check_world(B, W, K, A, lead_range);
+    if (rc) return rc;
+    bool with_slab = K > 0 && W > 1;
+    rc = cl_check_script(actors, A, n_scripts, B, with_slab);
+    if (rc) return rc;
     if (noise ? !(n_noise == 1 || n_noise == B) : n_noise != 0)
         return fail(MPC_E_ARG, "n_noise must be B (a struct per ego), 1 (shared) or 0 with noise NULL");
     if (ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
-    if (!quant) return fail(MPC_E_ARG, "quant is required");
-    if (n_hist < 0) return fail(MPC_E_ARG, "n_hist < 0");
-    if (n_hist == 0 && (hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status || hist_nobs ||
-                        hist_slab || hist_lead))
-        return fail(MPC_E_ARG, "a history array is given but n_hist == 0");
+    rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status ||
+                                             hist_nobs || hist_slab || hist_lead);
+    if (rc) return rc;
     if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
     if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
-    if (n_hist > 0 && !hist_egos) return fail(MPC_E_ARG, "hist_egos is NULL but n_hist > 0");
-    bool with_slab = K > 0 && W > 1;
-    for (size_t k = 0; k < (size_t)n_scripts * (size_t)A; ++k) {
-        if (actors[k].kind < MPC_ACTOR_NONE || actors[k].kind > MPC_ACTOR_LIGHT)
-            return fail(MPC_E_ARG, "actor kind outside MPC_ACTOR_NONE .. MPC_ACTOR_LIGHT");
-        with_slab = with_slab || actors[k].kind != MPC_ACTOR_NONE;
-    }
     for (size_t k = 0; k < (size_t)n_noise * NZ_NSIG; ++k)       // mpc_noise is NZ_NSIG doubles, no padding
         if (!(reinterpret_cast<const double*>(noise)[k] >= 0.0))
             return fail(MPC_E_ARG, "a noise sigma is negative or NaN");
-    std::vector<int> slot;
-    try {
-        slot.assign((size_t)B, -1);
-    } catch (const std::bad_alloc&) {
-        return fail(MPC_E_ALLOC, "history slot map");
-    }
-    for (int k = 0; k < n_hist; ++k) {
-        const int e = hist_egos[k];
-        if (e < 0 || e >= B) return fail(MPC_E_ARG, "hist_egos: ego index out of range [0, B)");
-        if (slot[e] >= 0) return fail(MPC_E_ARG, "hist_egos: ego index repeated");
-        slot[e] = k;
-    }
-    if (B == 0) return MPC_SUCCESS;
-    if (!x_init) return fail(MPC_E_ARG, "x_init is required");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    const bool per_ego = n_scripts == B && B > 1;    // n_scripts == B == 1 is the shared case
-    const int nsc = per_ego ? B : (actors ? 1 : 0);
-    const bool nz_per_ego = n_noise == B && B > 1;
     mpc_noise zero;
     mpc_default_noise(&zero);
     if (!noise) noise = &zero;
-    const int AK = A + K;
-    if (c->cpu) {
-        int hrc = MPC_SUCCESS;
-        const int erc = host_call([&] {
-            hrc = c->cpu->closed_loop_noisy(c->p, B, W, K, lead_range, x_init, actors, A, nsc == 0 ? 1 : nsc, with_slab,
-                                            noise, nz_per_ego ? B : 1, seed, ego_offset, max_steps, s_stop, quant,
-                                            extra, n_hist, slot.data(), hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
-                                            hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms);
-        });
-        return erc != MPC_SUCCESS ? erc : hrc;
-    }
-    KParams kp = kparams(&c->p);
-    kp.max_obs = with_slab ? AK : 0;         // every actor and every leader adds at most one entry
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
-    const size_t nak = (size_t)AK;
-    const size_t na1 = na ? na : 1, nak1 = nak ? nak : 1;    // no zero-sized allocation
-    std::vector<double> hsig;                // per-ego sigmas, field-major: the loads of a wave coalesce
-    if (nz_per_ego) {
-        try {
-            hsig.resize(nb * NZ_NSIG);
-        } catch (const std::bad_alloc&) {
-            return fail(MPC_E_ALLOC, "noise table");
-        }
-        for (size_t b = 0; b < nb; ++b)
-            for (size_t f = 0; f < NZ_NSIG; ++f) hsig[f * nb + b] = reinterpret_cast<const double*>(noise + b)[f];
-    }
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    ClState C = {};                          // obs, obs_s, tl_timer, fsm_flags stay null: TrState holds them
-    C.x = (double*)dalloc(nb * 5 * 8);
-    C.nobs = (int*)dalloc(nb * 4);
-    C.active = (int*)dalloc(nb * 4);
-    C.n_active = (int*)dalloc(4);
-    C.alist = (int*)dalloc(nb * 4);
-    C.n_list = (int*)dalloc(4);
-    C.xa = (double*)dalloc(nb * 5 * 8);
-    C.obsa = (double*)dalloc(nb * nak1 * 2 * 8);
-    C.nobsa = (int*)dalloc(nb * 4);
-    C.u0a = (double*)dalloc(nb * 2 * 8);
-    C.sta = (int*)dalloc(nb * 4);
-    double* d_xinit = (double*)dalloc(nb * 5 * 8);
-    SwState S = {};
-    S.q = (double*)dalloc(nb * MPC_CL_NQ * 8);
-    S.qflags = (int*)dalloc(nb * 4);
-    int* d_hslot = (int*)dalloc(nb * 4);
-    S.hslot = d_hslot;
-    S.n_steps = (int*)dalloc(nb * 4);
-    TrState T = {};
-    mpc_actor* d_actors = (mpc_actor*)dalloc((per_ego ? nb : 1) * na1 * sizeof(mpc_actor));
-    T.actors = d_actors;
-    T.per_ego = per_ego ? 1 : 0;
-    T.aval = (double*)dalloc(nb * na1 * 8);
-    T.aflags = (int*)dalloc(nb * na1 * 4);
-    T.slab = (double*)dalloc(nb * nak1 * 2 * 8);
-    T.ex = (double*)dalloc(nb * MPC_NZ_NX * 8);
-    double* d_sig = nz_per_ego ? (double*)dalloc(nb * NZ_NSIG * 8) : nullptr;
-    if (!C.x || !C.nobs || !C.active || !C.n_active || !C.alist || !C.n_list || !C.xa || !C.obsa || !C.nobsa ||
-        !C.u0a || !C.sta || !d_xinit || !S.q || !S.qflags || !d_hslot || !S.n_steps || !d_actors || !T.aval ||
-        !T.aflags || !T.slab || !T.ex || (nz_per_ego && !d_sig)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc noisy-loop buffers");
-    }
-    CvState V = {};
-    V.W = W;
-    V.K = K;
-    V.lead_range = lead_range;
-    NzState Z = {};
-    Z.sig = d_sig;
-    Z.shared = nz_per_ego ? zero : noise[0];
-    Z.k0 = (unsigned)(seed & 0xffffffffull);
-    Z.k1 = (unsigned)(seed >> 32);
-    Z.g0 = (unsigned long long)ego_offset;
-    Z.u_min0 = c->p.u_min[0];
-    Z.u_min1 = c->p.u_min[1];
-    Z.u_max0 = c->p.u_max[0];
-    Z.u_max1 = c->p.u_max[1];
-    S.hist_x = hist_x ? (double*)dalloc(nh * (ns + 1) * 5 * 8) : nullptr;
-    S.hist_u = hist_u ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
-    Z.hist_ua = hist_ua ? (double*)dalloc(nh * ns * 2 * 8) : nullptr;
-    Z.hist_xm = hist_xm ? (double*)dalloc(nh * ns * 5 * 8) : nullptr;
-    S.hist_obs_s = hist_car_s ? (double*)dalloc(nh * ns * 8) : nullptr;
-    S.hist_tl = hist_tl ? (int*)dalloc(nh * ns * 4) : nullptr;
-    S.hist_status = hist_status ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_nobs = hist_nobs ? (int*)dalloc(nh * ns * 4) : nullptr;
-    T.hist_slab = nullptr;                   // tr_fsm_kernel's rows are A wide: cv_lead_kernel writes the rows
-    V.hist_slab = hist_slab ? (double*)dalloc(nh * ns * nak * 2 * 8) : nullptr;
-    V.hist_lead = hist_lead ? (int*)dalloc(nh * ns * nk * 4) : nullptr;
-    if ((hist_x && !S.hist_x) || (hist_u && !S.hist_u) || (hist_ua && !Z.hist_ua) || (hist_xm && !Z.hist_xm) ||
-        (hist_car_s && !S.hist_obs_s) || (hist_tl && !S.hist_tl) || (hist_status && !S.hist_status) ||
-        (hist_nobs && !T.hist_nobs) || (hist_slab && !V.hist_slab) || (hist_lead && !V.hist_lead)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc noisy-loop histories");
-    }
-    hipStream_t st = c->stream;
-    hipEvent_t ev[SW_EVENTS] = {};
-    auto cleanup = [&]() {
-        hipStreamSynchronize(st);
-        for (auto& e : ev)
-            if (e) hipEventDestroy(e);
-        release();
-    };
-    // steps that never run stay NaN / -1 (all-ones bytes)
-    bool ok0 = true;
-    if (S.hist_x) ok0 = ok0 && hipMemsetAsync(S.hist_x, 0xff, nh * (ns + 1) * 5 * 8, st) == hipSuccess;
-    if (S.hist_u) ok0 = ok0 && hipMemsetAsync(S.hist_u, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
-    if (Z.hist_ua) ok0 = ok0 && hipMemsetAsync(Z.hist_ua, 0xff, nh * ns * 2 * 8, st) == hipSuccess;
-    if (Z.hist_xm) ok0 = ok0 && hipMemsetAsync(Z.hist_xm, 0xff, nh * ns * 5 * 8, st) == hipSuccess;
-    if (S.hist_obs_s) ok0 = ok0 && hipMemsetAsync(S.hist_obs_s, 0xff, nh * ns * 8, st) == hipSuccess;
-    if (S.hist_tl) ok0 = ok0 && hipMemsetAsync(S.hist_tl, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (S.hist_status) ok0 = ok0 && hipMemsetAsync(S.hist_status, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (T.hist_nobs) ok0 = ok0 && hipMemsetAsync(T.hist_nobs, 0xff, nh * ns * 4, st) == hipSuccess;
-    if (V.hist_slab) ok0 = ok0 && hipMemsetAsync(V.hist_slab, 0xff, nh * ns * nak * 2 * 8, st) == hipSuccess;
-    if (V.hist_lead) ok0 = ok0 && hipMemsetAsync(V.hist_lead, 0xff, nh * ns * nk * 4, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_xinit, x_init, nb * 5 * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok0 = ok0 && hipMemcpyAsync(d_hslot, slot.data(), nb * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (nsc > 0 && A > 0)
-        ok0 = ok0 && hipMemcpyAsync(d_actors, actors, (size_t)nsc * na * sizeof(mpc_actor), hipMemcpyHostToDevice,
-                                    st) == hipSuccess;
-    if (nz_per_ego)
-        ok0 = ok0 && hipMemcpyAsync(d_sig, hsig.data(), nb * NZ_NSIG * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok0) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "noisy-loop buffer initialisation");
-    }
-    const dim3 tb(256), tg((B + 255) / 256);
-    const dim3 wb(64 * ((W + 63) / 64)), wg(B / W);          // a workgroup per world
-    hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, d_xinit, s_stop, max_steps);
-    hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
-    hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            e = nullptr;
-            cleanup();
-            return fail(MPC_E_DEVICE, "hipEventCreate (step timing)");
-        }
-    if (hipEventRecord(ev[0], st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-    }
-    // the sweep's ring: step i ran between events i and i + 1, read at a host sync at most 8 steps later
-    std::vector<double> ms;
-    auto read_times = [&](int upto) {
-        for (int i = (int)ms.size(); i < upto; ++i) {
-            float t = NAN;
-            if (hipEventElapsedTime(&t, ev[i % SW_EVENTS], ev[(i + 1) % SW_EVENTS]) != hipSuccess) t = NAN;
-            ms.push_back(t);
-        }
-    };
-    rc = MPC_SUCCESS;
-    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-    int nl = 0;
-    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
-        return fail(MPC_E_DEVICE, "noisy-loop initial ego list");
-    }
-    try {
-        for (int step = 0; step < max_steps && nl > 0; ++step) {
-            hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
-            hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
-            const dim3 lg((nl + 255) / 256);
-            hipLaunchKernelGGL(nz_measure_kernel, lg, tb, 0, st, nl, B, AK, C, S, T, Z, step, max_steps);
-            rc = launch_solve(c, kp, nl, C.xa, with_slab ? C.obsa : nullptr, with_slab ? C.nobsa : nullptr, nullptr,
-                              C.u0a, nullptr, nullptr, C.sta, nullptr, st);
-            if (rc) break;
-            if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "noisy-loop active-count reset");
-                break;
-            }
-            hipLaunchKernelGGL(nz_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, T, Z, s_stop, step,
-                               max_steps);
-            if (hipEventRecord(ev[(step + 1) % SW_EVENTS], st) != hipSuccess) {
-                rc = fail(MPC_E_DEVICE, "hipEventRecord (step timing)");
-                break;
-            }
-            if ((step & 7) == 7 || step == max_steps - 1) {     // every 8 steps: has every ego left the loop?
-                int nact = 0;
-                if (hipMemcpyAsync(&nact, C.n_active, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    rc = fail(MPC_E_DEVICE, "noisy-loop step sync");
-                    break;
-                }
-                read_times(step + 1);
-                if (nact == 0) break;
-                if (nact < nl) {                                // egos left: shrink the solver's list
-                    hipLaunchKernelGGL(cl_compact_kernel, dim3(1), dim3(1024), 0, st, B, C);
-                    if (hipMemcpyAsync(&nl, C.n_list, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess) {
-                        rc = fail(MPC_E_DEVICE, "noisy-loop ego list");
-                        break;
-                    }
-                }
-            }
-        }
-        if (rc == MPC_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "noisy-loop kernel launch");
-        if (rc == MPC_SUCCESS) {
-            std::vector<double> hq(nb * MPC_CL_NQ), hx(extra ? nb * MPC_NZ_NX : 0);
-            std::vector<int> hn(nb);
-            bool ok = hipMemcpyAsync(hn.data(), S.n_steps, nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipMemcpyAsync(hq.data(), S.q, nb * MPC_CL_NQ * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (extra) ok = ok && hipMemcpyAsync(hx.data(), T.ex, nb * MPC_NZ_NX * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_x) ok = ok && hipMemcpyAsync(hist_x, S.hist_x, nh * (ns + 1) * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_u) ok = ok && hipMemcpyAsync(hist_u, S.hist_u, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_ua) ok = ok && hipMemcpyAsync(hist_ua, Z.hist_ua, nh * ns * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_xm) ok = ok && hipMemcpyAsync(hist_xm, Z.hist_xm, nh * ns * 5 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_car_s) ok = ok && hipMemcpyAsync(hist_car_s, S.hist_obs_s, nh * ns * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_tl) ok = ok && hipMemcpyAsync(hist_tl, S.hist_tl, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_status) ok = ok && hipMemcpyAsync(hist_status, S.hist_status, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_nobs) ok = ok && hipMemcpyAsync(hist_nobs, T.hist_nobs, nh * ns * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_slab) ok = ok && hipMemcpyAsync(hist_slab, V.hist_slab, nh * ns * nak * 2 * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (hist_lead) ok = ok && hipMemcpyAsync(hist_lead, V.hist_lead, nh * ns * nk * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-            ok = ok && hipStreamSynchronize(st) == hipSuccess;
-            if (!ok) {
-                rc = fail(MPC_E_DEVICE, "noisy-loop copy-back");
-            } else {
-                for (size_t b = 0; b < nb; ++b) {             // column-major on the device -> one row per ego
-                    for (int k = 0; k < MPC_CL_NQ; ++k) quant[b * MPC_CL_NQ + k] = hq[(size_t)k * nb + b];
-                    if (extra)
-                        for (int k = 0; k < MPC_NZ_NX; ++k) extra[b * MPC_NZ_NX + k] = hx[(size_t)k * nb + b];
-                }
-                mpcqp_cpu::sweep_max_step_ms(B, hn.data(), ms, quant);
-                if (n_steps) std::memcpy(n_steps, hn.data(), nb * 4);
-                if (step_ms)
-                    for (size_t i = 0; i < ns; ++i) step_ms[i] = i < ms.size() ? ms[i] : (double)NAN;
-            }
-        }
-    } catch (const std::bad_alloc&) {
-        rc = fail(MPC_E_ALLOC, "noisy-loop host buffers");
-    }
-    cleanup();
-    return rc;
+    const ScriptedLoop a = {"noisy-loop", B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, true, noise, n_noise,
+                            seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, hist_egos, hist_x,
+                            hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead,
+                            n_steps, step_ms};
+    return scripted_loop(c, a);
 }
 
 // the draws of mpc_closed_loop_noisy on their own (include/mpcqp.h), on the context's backend
@@ -1883,23 +1033,13 @@ extern "C" int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const 
     }
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
     const size_t nn = (size_t)n;
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* ptr = nullptr;
-        if (hipMalloc(&ptr, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(ptr);
-        return ptr;
-    };
-    auto release = [&]() { for (void* q : bufs) hipFree(q); };
-    long long* d_ego = (long long*)dalloc(nn * 8);
-    int* d_step = (int*)dalloc(nn * 4);
-    int* d_ch = (int*)dalloc(nn * 4);
-    unsigned* d_w = words ? (unsigned*)dalloc(nn * 16) : nullptr;
-    double* d_z = z ? (double*)dalloc(nn * 8) : nullptr;
-    if (!d_ego || !d_step || !d_ch || (words && !d_w) || (z && !d_z)) {
-        release();
-        return fail(MPC_E_ALLOC, "hipMalloc noise-draw buffers");
-    }
+    DevBufs mem;
+    long long* d_ego = mem.alloc<long long>(nn);
+    int* d_step = mem.alloc<int>(nn);
+    int* d_ch = mem.alloc<int>(nn);
+    unsigned* d_w = words ? mem.alloc<unsigned>(nn * 4) : nullptr;
+    double* d_z = z ? mem.alloc<double>(nn) : nullptr;
+    if (!mem.ok()) return fail(MPC_E_ALLOC, "hipMalloc noise-draw buffers");
     hipStream_t st = c->stream;
     bool ok = hipMemcpyAsync(d_ego, ego, nn * 8, hipMemcpyHostToDevice, st) == hipSuccess;
     ok = ok && hipMemcpyAsync(d_step, step, nn * 4, hipMemcpyHostToDevice, st) == hipSuccess;
@@ -1912,7 +1052,6 @@ extern "C" int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const 
     if (words) ok = ok && hipMemcpyAsync(words, d_w, nn * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
     if (z) ok = ok && hipMemcpyAsync(z, d_z, nn * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
-    release();
     return ok ? MPC_SUCCESS : fail(MPC_E_DEVICE, "noise draw");
 }
 
