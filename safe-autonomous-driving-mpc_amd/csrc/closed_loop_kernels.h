@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/mpcqp.h"
 #include "device_common.h"
+#include "loop_steps.h"
 
 // ------------------------------------------------------------------------------------------
 // batched closed loop: run_simulation, trajectory_tracking.py:377-443, per ego,
@@ -69,7 +70,7 @@ __global__ void cl_gather_kernel(int nl, ClState C) {
     C.nobsa[i] = C.nobs[e];
 }
 
-// ObstaclesFSM.update(dt, s, v) (trajectory_tracking.py:330-374) for every active ego
+// ObstaclesFSM.update(dt, s, v) (trajectory_tracking.py:330-374, loop_steps.h's fsm_step) for every active ego
 __global__ void cl_fsm_kernel(int B, mpc_fsm F, double dt, ClState C, double* hist_obs_s, int* hist_tl, int step,
                               int max_steps) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -77,37 +78,8 @@ __global__ void cl_fsm_kernel(int B, mpc_fsm F, double dt, ClState C, double* hi
     if (!C.active[b]) { C.nobs[b] = 0; return; }
     const double s = C.x[5 * (size_t)b], v = C.x[5 * (size_t)b + 4];
     int* fl = C.fsm_flags + 4 * (size_t)b;
-    double* o = C.obs + 4 * (size_t)b;
-    int n = 0;
-    double car_s = NAN;
-    if (F.dynamic_obstacle) {
-        if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
-        if (fl[0]) {
-            const double os = C.obs_s[b] + F.obs_v * dt;
-            C.obs_s[b] = os;
-            if (os > F.obs_end_s) {
-                fl[0] = 0;
-            } else {
-                o[0] = os;
-                o[1] = F.obs_v;
-                n = 1;
-                car_s = os;
-            }
-        }
-    }
-    if (F.traffic_light && !fl[2]) {
-        const double dist = F.tl_pos - s;
-        if (0.0 < dist && dist < F.tl_trigger_s) {
-            o[2 * n] = F.tl_pos;
-            o[2 * n + 1] = 0.0;
-            ++n;
-            if (v < 0.1 && dist < 10.0) fl[3] = 1;
-        }
-        if (fl[3]) {
-            C.tl_timer[b] += dt;
-            if (C.tl_timer[b] >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
-        }
-    }
+    double car_s;
+    const int n = fsm_step(F, dt, s, v, fl, C.obs_s[b], C.tl_timer[b], C.obs + 4 * (size_t)b, car_s);
     C.nobs[b] = n;
     if (hist_obs_s) hist_obs_s[(size_t)b * max_steps + step] = car_s;
     if (hist_tl) hist_tl[(size_t)b * max_steps + step] = fl[2];
@@ -126,10 +98,9 @@ __global__ void cl_plant_kernel(DevTable tab, int nl, double dt, ClState C, doub
     for (int j = 0; j < 5; ++j) x[j] = C.x[5 * (size_t)b + j];
     const double u1 = C.u0a[2 * (size_t)i], u2 = C.u0a[2 * (size_t)i + 1];
     get_state(tab, x[0], st, nullptr);
-    const double xd[5] = {x[4], x[4] * x[2], x[4] * (x[3] - st[3]), u1, u2};
+    plant_step(x, dt, u1, u2, st[3]);
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        x[j] = x[j] + dt * xd[j];
         C.x[5 * (size_t)b + j] = x[j];
         if (hist_x) hist_x[((size_t)b * (max_steps + 1) + step + 1) * 5 + j] = x[j];
     }

@@ -88,11 +88,12 @@ __global__ void __launch_bounds__(MPC_MAX_WORLD) cv_lead_kernel(int B, int A, Cl
             hslab[2 * j] = T.slab[(size_t)(2 * j) * B + b];
             hslab[2 * j + 1] = T.slab[(size_t)(2 * j + 1) * B + b];
         }
+    const EgoCols q{S.q, (size_t)B, (size_t)b}, ex{T.ex, (size_t)B, (size_t)b};
     int qf = S.qflags[b];
     const int qf0 = qf;
-    double gmin = SW_Q(S, MPC_CLQ_MIN_OBS_DIST, B, b);
-    double lmin = TR_X(T, MPC_CVX_MIN_LEAD_GAP, B, b);
-    bool have = TR_X(T, MPC_CVX_MIN_LEAD_EGO, B, b) >= 0.0;
+    double gmin = q[MPC_CLQ_MIN_OBS_DIST];
+    double lmin = ex[MPC_CVX_MIN_LEAD_GAP];
+    int lf = ex[MPC_CVX_MIN_LEAD_EGO] >= 0.0;        // bit 0: a leader gap was recorded
     int gset = 0, lego = -1, nl = 0;
     for (; nl < K && nl < r; ++nl) {
         const int j = ki[r - 1 - nl];
@@ -104,34 +105,24 @@ __global__ void __launch_bounds__(MPC_MAX_WORLD) cv_lead_kernel(int B, int A, Cl
         T.slab[(size_t)(2 * n + 1) * B + b] = vj;
         if (hslab) { hslab[2 * n] = sj; hslab[2 * n + 1] = vj; }
         if (hlead) hlead[nl] = base + j;
-        if (!(qf & 1)) {                             // the sweep's gap rule, a leader being a car
-            gmin = g; gset = 1;
-            qf |= 1;
-        } else if (g < gmin || g != g) {
-            gmin = g; gset = 1;
-        }
-        if (!have) {
-            lmin = g; lego = base + j;
-            have = true;
-        } else if (g < lmin || g != g) {
-            lmin = g; lego = base + j;
-        }
+        if (min_gap(gmin, qf, g)) gset = 1;          // the sweep's gap rule, a leader being a car
+        if (min_gap(lmin, lf, g)) lego = base + j;
     }
     const int n = n0 + nl;
     if (nl) {
         C.nobs[b] = n;
-        if ((double)n > TR_X(T, MPC_TRX_MAX_NOBS, B, b)) TR_X(T, MPC_TRX_MAX_NOBS, B, b) = (double)n;
-        if ((double)nl > TR_X(T, MPC_CVX_MAX_LEADERS, B, b)) TR_X(T, MPC_CVX_MAX_LEADERS, B, b) = (double)nl;
+        if ((double)n > ex[MPC_TRX_MAX_NOBS]) ex[MPC_TRX_MAX_NOBS] = (double)n;
+        if ((double)nl > ex[MPC_CVX_MAX_LEADERS]) ex[MPC_CVX_MAX_LEADERS] = (double)nl;
         if (h >= 0 && T.hist_nobs) T.hist_nobs[hrow] = n;
     }
     if (gset) {
-        SW_Q(S, MPC_CLQ_MIN_OBS_DIST, B, b) = gmin;
-        TR_X(T, MPC_TRX_MIN_GAP_ACTOR, B, b) = -1.0;
+        q[MPC_CLQ_MIN_OBS_DIST] = gmin;
+        ex[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
     }
     if (qf != qf0) S.qflags[b] = qf;
     if (lego >= 0) {
-        TR_X(T, MPC_CVX_MIN_LEAD_GAP, B, b) = lmin;
-        TR_X(T, MPC_CVX_MIN_LEAD_EGO, B, b) = (double)lego;
+        ex[MPC_CVX_MIN_LEAD_GAP] = lmin;
+        ex[MPC_CVX_MIN_LEAD_EGO] = (double)lego;
     }
 }
 
@@ -139,7 +130,8 @@ __global__ void __launch_bounds__(MPC_MAX_WORLD) cv_lead_kernel(int B, int A, Cl
 __global__ void __launch_bounds__(256) cv_init_kernel(int B, TrState T) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    TR_X(T, MPC_CVX_MIN_LEAD_GAP, B, b) = NAN;
-    TR_X(T, MPC_CVX_MIN_LEAD_EGO, B, b) = -1.0;
-    TR_X(T, MPC_CVX_MAX_LEADERS, B, b) = 0.0;
+    const EgoCols ex{T.ex, (size_t)B, (size_t)b};
+    ex[MPC_CVX_MIN_LEAD_GAP] = NAN;
+    ex[MPC_CVX_MIN_LEAD_EGO] = -1.0;
+    ex[MPC_CVX_MAX_LEADERS] = 0.0;
 }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "host_table.h"
+#include "loop_steps.h"
 
 namespace mpcqp_cpu {
 
@@ -218,8 +219,7 @@ public:
         for (int k = 0; k < p_.N; ++k) {
             double st[5];
             R_.state(x[0], st);
-            const double xd[5] = {x[4], x[4] * x[2], x[4] * (x[3] - st[3]), U[2 * k], U[2 * k + 1]};
-            for (int j = 0; j < 5; ++j) x[j] = x[j] + dt * xd[j];
+            plant_step(x, dt, U[2 * k], U[2 * k + 1], st[3]);
             std::memcpy(X[k + 1], x, sizeof(x));
         }
     }
@@ -934,35 +934,7 @@ private:
 // ---------------------------------------------------------------------------------------------
 inline void sweep_max_step_ms(int B, const int* n_steps, const std::vector<double>& ms, double* quant);
 
-// The noise source of mpc_closed_loop_noisy (include/mpcqp.h): Philox4x32-10 and the four-word variate, the
-// arithmetic of noise_kernels.h's nz_philox / nz_variate (the high halves from 64-bit products)
-inline void noise_words(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (unsigned)p1;
-        c2 = n2;
-        c3 = (unsigned)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-inline double noise_variate(const unsigned w[4]) {
-    const unsigned long long s = (unsigned long long)w[0] + w[1] + w[2] + w[3];
-    return ((double)s - 8589934590.0) * (1.7320508075688772 * 0x1p-32);
-}
-
-inline double noise_z(unsigned long long seed, unsigned long long g, int step, int channel) {
-    unsigned w[4];
-    noise_words((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)channel, (unsigned)seed,
-                (unsigned)(seed >> 32), w);
-    return noise_variate(w);
-}
-
-// mpc_noise_draw on the host; words and z may be null
+// mpc_noise_draw on the host (the noise source is loop_steps.h's); words and z may be null
 inline void noise_draw(unsigned long long seed, int n, const long long* ego, const int* step, const int* channel,
                        unsigned* words, double* z) {
     for (int i = 0; i < n; ++i) {
@@ -1096,22 +1068,9 @@ inline void hist_prefill(T* h, size_t n, T v) {
     if (h) std::fill(h, h + n, v);
 }
 
-// MPC_CLQ_MIN_OBS_DIST, the gap of check_quantities (hist_obs_s[i] - hist_x[i, 0]) over every car seen so far
-// with numpy's NaN rule; bit 0 of qflags: a gap was recorded.  min_actor, when given, takes `actor`, who is
-// behind a new minimum (-1: a leader)
-inline void loop_min_gap(double* q, int& qflags, double g, double* min_actor = nullptr, double actor = 0.0) {
-    if (!(qflags & 1)) {
-        qflags |= 1;
-    } else if (!(g < q[MPC_CLQ_MIN_OBS_DIST] || g != g)) {
-        return;
-    }
-    q[MPC_CLQ_MIN_OBS_DIST] = g;
-    if (min_actor) *min_actor = actor;
-}
-
 // What every closed-loop member keeps per ego, the outputs they share and the plant step.  quant is
 // [B][MPC_CL_NQ]; history rows exist for the egos with slot[b] >= 0 (row slot[b] of the [n_hist][...] arrays);
-// the histories and step_ms are optional.  The extremes take a NaN operand and keep it, like numpy's max / min
+// the histories and step_ms are optional.  The steps and the quantity rules are loop_steps.h's
 struct LoopEgos {
     const int B;
     const size_t ns;
@@ -1138,12 +1097,7 @@ struct LoopEgos {
             active[b] = x[5 * (size_t)b] <= s_stop;
             if (hist_x && slot[b] >= 0)
                 std::memcpy(hist_x + (size_t)slot[b] * (ns + 1) * 5, x.data() + 5 * (size_t)b, 5 * sizeof(double));
-            double* q = quant + (size_t)b * MPC_CL_NQ;
-            std::fill(q, q + MPC_CL_NQ, 0.0);
-            q[MPC_CLQ_EGO] = (double)b;
-            q[MPC_CLQ_S_FINAL] = x[5 * (size_t)b];
-            q[MPC_CLQ_MAX_DEV] = std::fabs(x[5 * (size_t)b + 1]);
-            q[MPC_CLQ_MIN_OBS_DIST] = NAN;
+            quant_init(quant + (size_t)b * MPC_CL_NQ, b, x[5 * (size_t)b], x[5 * (size_t)b + 1]);
         }
     }
 
@@ -1153,39 +1107,18 @@ struct LoopEgos {
     void plant(const Ref& ref, double dt, int b, int step, const double* u, const double* ua, int status,
                Perturb perturb) {
         double* xb = x.data() + 5 * (size_t)b;
-        double* q = quant + (size_t)b * MPC_CL_NQ;
         double st[5];
         ref.state(xb[0], st);
-        const double u1 = u[0], u2 = u[1];
-        const double xd[5] = {xb[4], xb[4] * xb[2], xb[4] * (xb[3] - st[3]), ua[0], ua[1]};
-        for (int j = 0; j < 5; ++j) xb[j] = xb[j] + dt * xd[j];
+        plant_step(xb, dt, ua[0], ua[1], st[3]);
         perturb(xb);
         if (slot[b] >= 0) {
             const size_t h = (size_t)slot[b];
             if (hist_x) std::memcpy(hist_x + (h * (ns + 1) + step + 1) * 5, xb, 5 * sizeof(double));
-            if (hist_u) {
-                hist_u[(h * ns + step) * 2] = u1;
-                hist_u[(h * ns + step) * 2 + 1] = u2;
-            }
+            if (hist_u) std::memcpy(hist_u + (h * ns + step) * 2, u, 2 * sizeof(double));
             if (hist_status) hist_status[h * ns + step] = status;
         }
         nrun[b] = step + 1;
-        q[MPC_CLQ_N_STEPS] = (double)(step + 1);
-        q[MPC_CLQ_S_FINAL] = xb[0];
-        const double ad = std::fabs(xb[1]);
-        if (ad > q[MPC_CLQ_MAX_DEV] || ad != ad) q[MPC_CLQ_MAX_DEV] = ad;
-        if (step == 0) {                             // every ego that runs at all runs step 0
-            q[MPC_CLQ_U1_MIN] = q[MPC_CLQ_U1_MAX] = u1;
-            q[MPC_CLQ_U2_MIN] = q[MPC_CLQ_U2_MAX] = u2;
-        } else {
-            if (u1 < q[MPC_CLQ_U1_MIN] || u1 != u1) q[MPC_CLQ_U1_MIN] = u1;
-            if (u1 > q[MPC_CLQ_U1_MAX] || u1 != u1) q[MPC_CLQ_U1_MAX] = u1;
-            if (u2 < q[MPC_CLQ_U2_MIN] || u2 != u2) q[MPC_CLQ_U2_MIN] = u2;
-            if (u2 > q[MPC_CLQ_U2_MAX] || u2 != u2) q[MPC_CLQ_U2_MAX] = u2;
-        }
-        const int code = status & MPC_STATUS_MASK;
-        if (code == MPC_INFEASIBLE) q[MPC_CLQ_N_INFEASIBLE] += 1.0;
-        if (code != MPC_OK) q[MPC_CLQ_N_NOT_OK] += 1.0;
+        plant_quant(quant + (size_t)b * MPC_CL_NQ, step, xb, u[0], u[1], status);
         if (!(xb[0] <= s_stop)) active[b] = 0;
     }
 
@@ -1196,95 +1129,31 @@ struct LoopEgos {
     }
 };
 
-// ObstaclesFSM.update (:335-372) of one ego on its state before the step.  fl: car active, car triggered, light
-// green, waiting.  Writes the slab entries to o (the car first) and returns their number; car_s is the car's
-// position while it is on the road, else NaN
-inline int fsm_step(const mpc_fsm& F, double dt, double s, double v, int* fl, double& car, double& timer, double* o,
-                    double& car_s) {
-    int n = 0;
-    car_s = NAN;
-    if (F.dynamic_obstacle) {                        // :335-349
-        if (!fl[1] && s >= F.obs_trigger_s) { fl[1] = 1; fl[0] = 1; }
-        if (fl[0]) {
-            car = car + F.obs_v * dt;
-            if (car > F.obs_end_s) {
-                fl[0] = 0;
-            } else {
-                o[0] = car;
-                o[1] = F.obs_v;
-                n = 1;
-                car_s = car;
-            }
-        }
-    }
-    if (F.traffic_light && !fl[2]) {                 // :351-372
-        const double dist = F.tl_pos - s;
-        if (0.0 < dist && dist < F.tl_trigger_s) {
-            o[2 * n] = F.tl_pos;
-            o[2 * n + 1] = 0.0;
-            ++n;
-            if (v < 0.1 && dist < 10.0) fl[3] = 1;
-        }
-        if (fl[3]) {
-            timer += dt;
-            if (timer >= F.tl_stop_duration) { fl[2] = 1; fl[3] = 0; }
-        }
-    }
-    return n;
-}
-
-// One ego's script of A actors for one step: each actor runs ObstaclesFSM's per-obstacle transitions on its own
-// state (fl, val: a car's position, a light's timer), visited in index order; o takes what they emit and their
-// number is returned.  Updates the gap and red-pass quantities (q, e: the ego's quant and extra rows), green (bit
-// a: actor a is a GREEN light) and car_s (the first car on the road, else NaN)
-enum { ACT_CAR_ACTIVE = 1, ACT_CAR_TRIGGERED = 2, ACT_TL_GREEN = 4, ACT_TL_WAITING = 8, ACT_PASS_DECIDED = 16 };
+// One ego's script of A actors for one step: actor_step per actor on its own state (fl, val), visited in index
+// order; o takes what they emit and their number is returned.  Updates the gap and red-pass quantities (q, e: the
+// ego's quant and extra rows), green (bit a: actor a is a GREEN light) and car_s (the first car on the road, else
+// NaN)
 inline int script_step(const mpc_actor* sc, int A, double dt, double s, double v, int* fls, double* vals, double* o,
                        double* q, double* e, int& qflags, int& green, double& car_s) {
     int n = 0, have_car = 0;
     green = 0;
     car_s = NAN;
     for (int a = 0; a < A; ++a) {
-        const mpc_actor& M = sc[a];
-        if (M.kind == MPC_ACTOR_NONE) continue;
-        int& fl = fls[a];
-        double& val = vals[a];
-        if (M.kind == MPC_ACTOR_CAR) {               // ObstaclesFSM.update, :335-349, this car's state
-            if (!(fl & ACT_CAR_TRIGGERED) && s >= M.trigger_s) fl |= ACT_CAR_TRIGGERED | ACT_CAR_ACTIVE;
-            if (fl & ACT_CAR_ACTIVE) {
-                val = val + M.v * dt;
-                if (val > M.end_s) {
-                    fl &= ~ACT_CAR_ACTIVE;
-                } else {
-                    o[2 * n] = val;
-                    o[2 * n + 1] = M.v;
-                    ++n;
-                    if (!have_car) { have_car = 1; car_s = val; }
-                    if (val == val) loop_min_gap(q, qflags, val - s, e + MPC_TRX_MIN_GAP_ACTOR, (double)a);
-                }
-            }
-        } else {                                     // :351-372, this light's state
-            if (!(fl & ACT_TL_GREEN)) {
-                const double dist = M.pos_s - s;
-                if (0.0 < dist && dist < M.trigger_s) {
-                    o[2 * n] = M.pos_s;
-                    o[2 * n + 1] = 0.0;
-                    ++n;
-                    if (v < 0.1 && dist < 10.0) fl |= ACT_TL_WAITING;
-                }
-                if (fl & ACT_TL_WAITING) {
-                    val += dt;
-                    if (val >= M.stop_duration) fl = (fl | ACT_TL_GREEN) & ~ACT_TL_WAITING;
-                }
-            }
-            if (fl & ACT_TL_GREEN) green |= 1 << a;
-            if (!(fl & ACT_PASS_DECIDED) && s > M.pos_s) {   // the first state past this light
-                fl |= ACT_PASS_DECIDED;
-                if (!(fl & ACT_TL_GREEN)) {
-                    q[MPC_CLQ_RED_PASS] = 1.0;
-                    e[MPC_TRX_N_RED_PASS] += 1.0;
-                }
-            }
+        if (sc[a].kind == MPC_ACTOR_NONE) continue;
+        double os, ov;
+        const int r = actor_step(sc[a], dt, s, v, fls[a], vals[a], os, ov);
+        if (r & ACTOR_GREEN) green |= 1 << a;
+        if (r & ACTOR_RAN_RED) {
+            q[MPC_CLQ_RED_PASS] = 1.0;
+            e[MPC_TRX_N_RED_PASS] += 1.0;
         }
+        if (!(r & ACTOR_EMITS)) continue;
+        o[2 * n] = os;
+        o[2 * n + 1] = ov;
+        ++n;
+        if (sc[a].kind != MPC_ACTOR_CAR) continue;
+        if (!have_car) { have_car = 1; car_s = os; }
+        if (os == os && min_gap(q[MPC_CLQ_MIN_OBS_DIST], qflags, os - s)) e[MPC_TRX_MIN_GAP_ACTOR] = (double)a;
     }
     return n;
 }
@@ -1454,11 +1323,8 @@ struct Backend {
                      double car_s;
                      const int n = fsm_step(F, p.dt, s, v, fl, car[b], timer[b], o, car_s);
                      std::memcpy(xs, E.x.data() + 5 * (size_t)b, 5 * sizeof(double));
-                     if (car_s == car_s) loop_min_gap(q, E.qflags[b], car_s - s);
-                     if (F.traffic_light && !(E.qflags[b] & 2) && s > F.tl_pos) {   // the first state past the light
-                         E.qflags[b] |= 2;
-                         if (!fl[2]) q[MPC_CLQ_RED_PASS] = 1.0;
-                     }
+                     if (car_s == car_s) min_gap(q[MPC_CLQ_MIN_OBS_DIST], E.qflags[b], car_s - s);
+                     red_pass_step(F, s, fl[2], q, E.qflags[b]);
                      if (slot[b] >= 0) {
                          if (hist_obs_s) hist_obs_s[(size_t)slot[b] * ns + step] = car_s;
                          if (hist_tl) hist_tl[(size_t)slot[b] * ns + step] = fl[2];
@@ -1539,7 +1405,8 @@ struct Backend {
                  },
                  [&](int step, int b, double* xm, double* oa) {
                      const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
-                     const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
+                     const NoiseAt at = {(unsigned)seed, (unsigned)(seed >> 32),
+                                         (unsigned long long)ego_offset + (unsigned long long)b, step};
                      const double s = E.x[5 * (size_t)b], v = E.x[5 * (size_t)b + 4];
                      double o[2 * MPC_MAX_ACTORS];            // the true slab of this step
                      double* q = quant + (size_t)b * MPC_CL_NQ;
@@ -1561,29 +1428,19 @@ struct Backend {
                              o[2 * n + 1] = E.x[5 * (size_t)j + 4];
                              ++n;
                              if (hlead) hlead[nlead] = j;
-                             loop_min_gap(q, E.qflags[b], gap, e + MPC_TRX_MIN_GAP_ACTOR, -1.0);   // a leader is a car
-                             if (e[MPC_CVX_MIN_LEAD_EGO] < 0.0 || gap < e[MPC_CVX_MIN_LEAD_GAP] || gap != gap) {
-                                 e[MPC_CVX_MIN_LEAD_GAP] = gap;
-                                 e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
-                             }
+                             if (min_gap(q[MPC_CLQ_MIN_OBS_DIST], E.qflags[b], gap))   // a leader is a car
+                                 e[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
+                             int lf = e[MPC_CVX_MIN_LEAD_EGO] >= 0.0;     // bit 0: a leader gap was recorded
+                             if (min_gap(e[MPC_CVX_MIN_LEAD_GAP], lf, gap)) e[MPC_CVX_MIN_LEAD_EGO] = (double)j;
                          }
                          if ((double)nlead > e[MPC_CVX_MAX_LEADERS]) e[MPC_CVX_MAX_LEADERS] = (double)nlead;
                      }
                      if ((double)n > e[MPC_TRX_MAX_NOBS]) e[MPC_TRX_MAX_NOBS] = (double)n;
                      // what the solver receives: the measured state and the perceived slab
-                     for (int j = 0; j < 5; ++j) {
-                         xm[j] = E.x[5 * (size_t)b + j];
-                         if (Z.meas_sigma[j] != 0.0)
-                             xm[j] = xm[j] + Z.meas_sigma[j] * noise_z(seed, g, step, MPC_NZ_CH_MEAS + j);
-                     }
-                     for (int j = 0; j < n; ++j) {
-                         oa[2 * j] = o[2 * j];
-                         oa[2 * j + 1] = o[2 * j + 1];
-                         if (Z.perc_sigma[0] != 0.0)
-                             oa[2 * j] = oa[2 * j] + Z.perc_sigma[0] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j);
-                         if (Z.perc_sigma[1] != 0.0)
-                             oa[2 * j + 1] = oa[2 * j + 1] + Z.perc_sigma[1] * noise_z(seed, g, step, MPC_NZ_CH_PERC + 2 * j + 1);
-                     }
+                     for (int j = 0; j < 5; ++j)
+                         xm[j] = noise_add(E.x[5 * (size_t)b + j], Z.meas_sigma[j], at, MPC_NZ_CH_MEAS + j);
+                     for (int j = 0; j < 2 * n; ++j)          // entry j / 2: s on the even channel, v on the odd
+                         oa[j] = noise_add(o[j], Z.perc_sigma[j & 1], at, MPC_NZ_CH_PERC + j);
                      if (slot[b] >= 0) {
                          const size_t h = (size_t)slot[b] * ns + step;
                          if (hist_car_s) hist_car_s[h] = car_s;
@@ -1596,35 +1453,22 @@ struct Backend {
                  },
                  [&](int step, int b, const double* u, int status) {
                      const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
-                     const unsigned long long g = (unsigned long long)ego_offset + (unsigned long long)b;
-                     double ua[2] = {u[0], u[1]};             // the applied control
+                     const NoiseAt at = {(unsigned)seed, (unsigned)(seed >> 32),
+                                         (unsigned long long)ego_offset + (unsigned long long)b, step};
+                     double ua[2];                            // the applied control
                      bool clamped = false;
                      for (int k = 0; k < 2; ++k)
-                         if (Z.act_sigma[k] != 0.0) {
-                             const double t = ua[k] + Z.act_sigma[k] * noise_z(seed, g, step, MPC_NZ_CH_ACT + k);
-                             ua[k] = t < p.u_min[k] ? p.u_min[k] : (t > p.u_max[k] ? p.u_max[k] : t);
-                             clamped = clamped || t < p.u_min[k] || t > p.u_max[k];
-                         }
+                         ua[k] = apply_actuation(u[k], Z.act_sigma[k], at, MPC_NZ_CH_ACT + k, p.u_min[k], p.u_max[k],
+                                                 clamped);
                      E.plant(*ref, p.dt, b, step, u, ua, status, [&](double* xb) {
                          for (int j = 0; j < 5; ++j)
-                             if (Z.proc_sigma[j] != 0.0)
-                                 xb[j] = xb[j] + (p.dt * Z.proc_sigma[j]) * noise_z(seed, g, step, MPC_NZ_CH_PROC + j);
+                             xb[j] = noise_add(xb[j], Z.proc_sigma[j], at, MPC_NZ_CH_PROC + j, p.dt);
                      });
                      if (nx < MPC_NZ_NX) return;
                      double* e = ex.data() + (size_t)b * nxs;
-                     if (slot[b] >= 0 && hist_ua) {
-                         hist_ua[((size_t)slot[b] * ns + step) * 2] = ua[0];
-                         hist_ua[((size_t)slot[b] * ns + step) * 2 + 1] = ua[1];
-                     }
-                     if (step == 0) {
-                         e[MPC_NZX_U1A_MIN] = e[MPC_NZX_U1A_MAX] = ua[0];
-                         e[MPC_NZX_U2A_MIN] = e[MPC_NZX_U2A_MAX] = ua[1];
-                     } else {
-                         if (ua[0] < e[MPC_NZX_U1A_MIN] || ua[0] != ua[0]) e[MPC_NZX_U1A_MIN] = ua[0];
-                         if (ua[0] > e[MPC_NZX_U1A_MAX] || ua[0] != ua[0]) e[MPC_NZX_U1A_MAX] = ua[0];
-                         if (ua[1] < e[MPC_NZX_U2A_MIN] || ua[1] != ua[1]) e[MPC_NZX_U2A_MIN] = ua[1];
-                         if (ua[1] > e[MPC_NZX_U2A_MAX] || ua[1] != ua[1]) e[MPC_NZX_U2A_MAX] = ua[1];
-                     }
+                     if (slot[b] >= 0 && hist_ua)
+                         std::memcpy(hist_ua + ((size_t)slot[b] * ns + step) * 2, ua, sizeof(ua));
+                     extremes4(e, MPC_NZX_U1A_MIN, step, ua[0], ua[1]);
                      if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
                  });
         E.finish(n_steps);

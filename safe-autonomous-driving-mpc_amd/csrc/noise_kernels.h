@@ -7,42 +7,8 @@
 #pragma once
 #include "convoy_kernels.h"
 
-// The noise source (include/mpcqp.h): stateless Philox4x32-10, one block per variate.  Integer arithmetic and
-// single rounded FP64 operations only (the build has -ffp-contract=off), so a draw is the same bits on the device,
-// on the host backend and in numpy.
-#define NZ_M0 0xD2511F53u
-#define NZ_M1 0xCD9E8D57u
-#define NZ_W0 0x9E3779B9u
-#define NZ_W1 0xBB67AE85u
-#define NZ_C (1.7320508075688772 * 0x1p-32)    // the double nearest sqrt(3), scaled exactly
-
-__device__ __forceinline__ void nz_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                          unsigned k1, unsigned w[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(NZ_M0, c0), lo0 = NZ_M0 * c0;
-        const unsigned hi1 = __umulhi(NZ_M1, c2), lo1 = NZ_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += NZ_W0;
-        k1 += NZ_W1;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-// the variate of four words: the sum is an exact integer below 2^34, the subtraction is exact, one rounding
-__device__ __forceinline__ double nz_variate(const unsigned w[4]) {
-    const unsigned long long s = (unsigned long long)w[0] + w[1] + w[2] + w[3];
-    return ((double)s - 8589934590.0) * NZ_C;
-}
-
-__device__ __forceinline__ double nz_z(unsigned k0, unsigned k1, unsigned long long g, int step, int channel) {
-    unsigned w[4];
-    nz_philox((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)channel, k0, k1, w);
-    return nz_variate(w);
-}
+// The noise source (Philox4x32-10, the variate, the sigma application and the actuation clamp) is loop_steps.h's,
+// so a draw is the same bits on the device, on the host backend and in numpy.
 
 // rows of the per-ego sigma table: mpc_noise's fields in its order
 #define NZ_MEAS 0
@@ -75,8 +41,9 @@ __device__ __forceinline__ double nz_sigma(const NzState& Z, int f, int B, int b
 __global__ void __launch_bounds__(256) nz_init_kernel(int B, TrState T) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const EgoCols ex{T.ex, (size_t)B, (size_t)b};
 #pragma unroll
-    for (int k = MPC_NZX_U1A_MIN; k < MPC_NZ_NX; ++k) TR_X(T, k, B, b) = 0.0;
+    for (int k = MPC_NZX_U1A_MIN; k < MPC_NZ_NX; ++k) ex[k] = 0.0;
 }
 
 // tr_gather_kernel with the measurement and perception draws: slot i <- ego alist[i], its state plus
@@ -90,14 +57,13 @@ __global__ void __launch_bounds__(256) nz_measure_kernel(int nl, int B, int A, C
     if (i >= nl) return;
     const int e = C.alist[i];
     const bool act = C.active[e] != 0;
-    const unsigned long long g = Z.g0 + (unsigned long long)e;
+    const NoiseAt at = {Z.k0, Z.k1, Z.g0 + (unsigned long long)e, step};
     const int h = S.hslot[e];
     double* hxm = act && h >= 0 && Z.hist_xm ? Z.hist_xm + ((size_t)h * max_steps + step) * 5 : nullptr;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         double xv = C.x[5 * (size_t)e + j];
-        const double sg = nz_sigma(Z, NZ_MEAS + j, B, e);
-        if (act && sg != 0.0) xv = xv + sg * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_MEAS + j);
+        if (act) xv = noise_add(xv, nz_sigma(Z, NZ_MEAS + j, B, e), at, MPC_NZ_CH_MEAS + j);
         C.xa[5 * (size_t)i + j] = xv;
         if (hxm) hxm[j] = xv;
     }
@@ -109,8 +75,10 @@ __global__ void __launch_bounds__(256) nz_measure_kernel(int nl, int B, int A, C
         if (j < n) {
             os = T.slab[(size_t)(2 * j) * B + e];
             ov = T.slab[(size_t)(2 * j + 1) * B + e];
-            if (act && sp != 0.0) os = os + sp * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_PERC + 2 * j);
-            if (act && sv != 0.0) ov = ov + sv * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_PERC + 2 * j + 1);
+            if (act) {
+                os = noise_add(os, sp, at, MPC_NZ_CH_PERC + 2 * j);
+                ov = noise_add(ov, sv, at, MPC_NZ_CH_PERC + 2 * j + 1);
+            }
         }
         o[2 * j] = os;
         o[2 * j + 1] = ov;
@@ -118,9 +86,9 @@ __global__ void __launch_bounds__(256) nz_measure_kernel(int nl, int B, int A, C
     C.nobsa[i] = n;
 }
 
-// sw_plant_kernel with the actuation draw and clamp and the process draw.  The arithmetic and the quantity
-// updates are that kernel's, restated: with every sigma 0 the two are the same bit for bit.  MPC_CLQ_U* and
-// hist_u keep the commanded (u1, u2); the applied (ua1, ua2) go to the MPC_NZX_* extras and hist_ua
+// sw_plant_kernel with the actuation draw and clamp and the process draw: the same plant_step, plant_quant and
+// sw_plant_store, so with every sigma 0 the two are the same bit for bit.  MPC_CLQ_U* and hist_u keep the
+// commanded (u1, u2); the applied (ua1, ua2) go to the MPC_NZX_* extras and hist_ua
 __global__ void __launch_bounds__(256) nz_plant_kernel(DevTable tab, int B, int nl, double dt, ClState C, SwState S,
                                                        TrState T, NzState Z, double s_stop, int step,
                                                        int max_steps) {
@@ -129,80 +97,29 @@ __global__ void __launch_bounds__(256) nz_plant_kernel(DevTable tab, int B, int 
     const int b = C.alist[i];
     if (!C.active[b]) return;
     const int h = S.hslot[b];
-    const unsigned long long g = Z.g0 + (unsigned long long)b;
+    const NoiseAt at = {Z.k0, Z.k1, Z.g0 + (unsigned long long)b, step};
     double x[5], st[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) x[j] = C.x[5 * (size_t)b + j];
     const double u1 = C.u0a[2 * (size_t)i], u2 = C.u0a[2 * (size_t)i + 1];
-    double ua1 = u1, ua2 = u2;
     bool clamped = false;
-    const double sa1 = nz_sigma(Z, NZ_ACT, B, b), sa2 = nz_sigma(Z, NZ_ACT + 1, B, b);
-    if (sa1 != 0.0) {
-        const double t = u1 + sa1 * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_ACT);
-        ua1 = t < Z.u_min0 ? Z.u_min0 : (t > Z.u_max0 ? Z.u_max0 : t);
-        clamped = clamped || t < Z.u_min0 || t > Z.u_max0;
-    }
-    if (sa2 != 0.0) {
-        const double t = u2 + sa2 * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_ACT + 1);
-        ua2 = t < Z.u_min1 ? Z.u_min1 : (t > Z.u_max1 ? Z.u_max1 : t);
-        clamped = clamped || t < Z.u_min1 || t > Z.u_max1;
-    }
+    const double ua1 = apply_actuation(u1, nz_sigma(Z, NZ_ACT, B, b), at, MPC_NZ_CH_ACT, Z.u_min0, Z.u_max0, clamped);
+    const double ua2 = apply_actuation(u2, nz_sigma(Z, NZ_ACT + 1, B, b), at, MPC_NZ_CH_ACT + 1, Z.u_min1, Z.u_max1,
+                                       clamped);
     get_state(tab, x[0], st, nullptr);
-    const double xd[5] = {x[4], x[4] * x[2], x[4] * (x[3] - st[3]), ua1, ua2};
+    plant_step(x, dt, ua1, ua2, st[3]);
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        x[j] = x[j] + dt * xd[j];
-        const double sp = nz_sigma(Z, NZ_PROC + j, B, b);
-        if (sp != 0.0) x[j] = x[j] + (dt * sp) * nz_z(Z.k0, Z.k1, g, step, MPC_NZ_CH_PROC + j);
-        C.x[5 * (size_t)b + j] = x[j];
-        if (h >= 0 && S.hist_x) S.hist_x[((size_t)h * (max_steps + 1) + step + 1) * 5 + j] = x[j];
-    }
+    for (int j = 0; j < 5; ++j) x[j] = noise_add(x[j], nz_sigma(Z, NZ_PROC + j, B, b), at, MPC_NZ_CH_PROC + j, dt);
     const int status = C.sta[i];
-    if (h >= 0) {
-        if (S.hist_u) {
-            S.hist_u[((size_t)h * max_steps + step) * 2] = u1;
-            S.hist_u[((size_t)h * max_steps + step) * 2 + 1] = u2;
-        }
-        if (Z.hist_ua) {
-            Z.hist_ua[((size_t)h * max_steps + step) * 2] = ua1;
-            Z.hist_ua[((size_t)h * max_steps + step) * 2 + 1] = ua2;
-        }
-        if (S.hist_status) S.hist_status[(size_t)h * max_steps + step] = status;
+    const EgoCols ex{T.ex, (size_t)B, (size_t)b};
+    plant_quant(EgoCols{S.q, (size_t)B, (size_t)b}, step, x, u1, u2, status);
+    extremes4(ex, MPC_NZX_U1A_MIN, step, ua1, ua2);
+    if (clamped) ex[MPC_NZX_N_CLAMPED] += 1.0;
+    if (h >= 0 && Z.hist_ua) {
+        Z.hist_ua[((size_t)h * max_steps + step) * 2] = ua1;
+        Z.hist_ua[((size_t)h * max_steps + step) * 2 + 1] = ua2;
     }
-    S.n_steps[b] = step + 1;
-    SW_Q(S, MPC_CLQ_N_STEPS, B, b) = (double)(step + 1);
-    SW_Q(S, MPC_CLQ_S_FINAL, B, b) = x[0];
-    const double ad = fabs(x[1]), md = SW_Q(S, MPC_CLQ_MAX_DEV, B, b);
-    if (ad > md || ad != ad) SW_Q(S, MPC_CLQ_MAX_DEV, B, b) = ad;
-    if (step == 0) {
-        SW_Q(S, MPC_CLQ_U1_MIN, B, b) = u1;
-        SW_Q(S, MPC_CLQ_U1_MAX, B, b) = u1;
-        SW_Q(S, MPC_CLQ_U2_MIN, B, b) = u2;
-        SW_Q(S, MPC_CLQ_U2_MAX, B, b) = u2;
-        TR_X(T, MPC_NZX_U1A_MIN, B, b) = ua1;
-        TR_X(T, MPC_NZX_U1A_MAX, B, b) = ua1;
-        TR_X(T, MPC_NZX_U2A_MIN, B, b) = ua2;
-        TR_X(T, MPC_NZX_U2A_MAX, B, b) = ua2;
-    } else {
-        const double a0 = SW_Q(S, MPC_CLQ_U1_MIN, B, b), a1 = SW_Q(S, MPC_CLQ_U1_MAX, B, b);
-        const double b0 = SW_Q(S, MPC_CLQ_U2_MIN, B, b), b1 = SW_Q(S, MPC_CLQ_U2_MAX, B, b);
-        if (u1 < a0 || u1 != u1) SW_Q(S, MPC_CLQ_U1_MIN, B, b) = u1;
-        if (u1 > a1 || u1 != u1) SW_Q(S, MPC_CLQ_U1_MAX, B, b) = u1;
-        if (u2 < b0 || u2 != u2) SW_Q(S, MPC_CLQ_U2_MIN, B, b) = u2;
-        if (u2 > b1 || u2 != u2) SW_Q(S, MPC_CLQ_U2_MAX, B, b) = u2;
-        const double c0 = TR_X(T, MPC_NZX_U1A_MIN, B, b), c1 = TR_X(T, MPC_NZX_U1A_MAX, B, b);
-        const double d0 = TR_X(T, MPC_NZX_U2A_MIN, B, b), d1 = TR_X(T, MPC_NZX_U2A_MAX, B, b);
-        if (ua1 < c0 || ua1 != ua1) TR_X(T, MPC_NZX_U1A_MIN, B, b) = ua1;
-        if (ua1 > c1 || ua1 != ua1) TR_X(T, MPC_NZX_U1A_MAX, B, b) = ua1;
-        if (ua2 < d0 || ua2 != ua2) TR_X(T, MPC_NZX_U2A_MIN, B, b) = ua2;
-        if (ua2 > d1 || ua2 != ua2) TR_X(T, MPC_NZX_U2A_MAX, B, b) = ua2;
-    }
-    if (clamped) TR_X(T, MPC_NZX_N_CLAMPED, B, b) += 1.0;
-    const int code = status & MPC_STATUS_MASK;
-    if (code == MPC_INFEASIBLE) SW_Q(S, MPC_CLQ_N_INFEASIBLE, B, b) += 1.0;
-    if (code != MPC_OK) SW_Q(S, MPC_CLQ_N_NOT_OK, B, b) += 1.0;
-    if (!(x[0] <= s_stop)) C.active[b] = 0;
-    else atomicAdd(C.n_active, 1);
+    sw_plant_store(C, S, b, h, x, u1, u2, status, s_stop, step, max_steps);
 }
 
 // mpc_noise_draw: draw i of (ego[i], step[i], channel[i]); words [n][4] and z [n], either may be null
@@ -214,10 +131,10 @@ __global__ void __launch_bounds__(256) nz_draw_kernel(int n, unsigned k0, unsign
     if (i >= n) return;
     const unsigned long long g = (unsigned long long)ego[i];
     unsigned w[4];
-    nz_philox((unsigned)g, (unsigned)(g >> 32), (unsigned)step[i], (unsigned)channel[i], k0, k1, w);
+    noise_words((unsigned)g, (unsigned)(g >> 32), (unsigned)step[i], (unsigned)channel[i], k0, k1, w);
     if (words) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) words[4 * (size_t)i + k] = w[k];
     }
-    if (z) z[i] = nz_variate(w);
+    if (z) z[i] = noise_variate(w);
 }

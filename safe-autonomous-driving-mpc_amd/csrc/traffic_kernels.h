@@ -1,18 +1,11 @@
 // traffic_kernels.h -- the kernels around the solve in the closed-loop traffic scripts (mpc_closed_loop_traffic):
 // sweep_kernels.h's initialisation and FSM step with a script of A actors per ego instead of one car and one
 // light, and a gather that packs the A-wide obstacle slab.  Each actor runs the per-obstacle state machine of
-// sw_fsm_kernel (ObstaclesFSM.update) on its own state.  The compaction kernel, the plant kernel (with the
+// ObstaclesFSM.update on its own state (loop_steps.h, actor_step).  The compaction kernel, the plant kernel (with the
 // plant-side quantities and the kept hist_x / hist_u / hist_status) and the solver launch are the sweep's,
 // unchanged.
 #pragma once
 #include "sweep_kernels.h"
-
-// per-actor flag bits
-#define TR_CAR_ACTIVE 1      // car: on the road (obs_active)
-#define TR_CAR_TRIGGERED 2   // car: has been spawned once (obs_has_triggered)
-#define TR_TL_GREEN 4        // light: GREEN
-#define TR_TL_WAITING 8      // light: the ego stands in front of it (tl_waiting)
-#define TR_PASS_DECIDED 16   // light: the red-pass question is decided
 
 // One thread per ego; the per-actor state is actor-major ([A][B]) so that the threads of a wave touch
 // neighbouring addresses for every actor, and so are the slab the FSM step writes and the extras.
@@ -20,15 +13,13 @@ struct TrState {
     const mpc_actor* actors;   // [B][A] (per_ego) or [A] (one shared script)
     int per_ego;
     double* aval;              // [A][B] car: position; light: timer
-    int* aflags;               // [A][B] TR_* bits
+    int* aflags;               // [A][B] ACT_* bits (loop_steps.h)
     double* slab;              // [A][2][B] this step's slab of every ego (entry j: rows 2j, 2j + 1)
-    double* ex;                // [MPC_TR_NX][B] extras
+    double* ex;                // [MPC_TR_NX][B] extras (an EgoCols like SwState::q)
     // histories of the selected egos beyond SwState's; either may be null
     int* hist_nobs;            // [n_hist][max_steps]
     double* hist_slab;         // [n_hist][max_steps][A][2]
 };
-
-#define TR_X(T, col, B, b) (T).ex[(size_t)(col) * (size_t)(B) + (size_t)(b)]
 
 // sw_init_kernel with ego b's script: a car starts at its pos_s, a light at timer 0, every flag clear
 __global__ void __launch_bounds__(256) tr_init_kernel(int B, int A, ClState C, SwState S, TrState T,
@@ -50,18 +41,15 @@ __global__ void __launch_bounds__(256) tr_init_kernel(int B, int A, ClState C, S
     C.nobs[b] = 0;
     S.n_steps[b] = 0;
     S.qflags[b] = 0;
-    for (int k = 0; k < MPC_CL_NQ; ++k) SW_Q(S, k, B, b) = 0.0;
-    SW_Q(S, MPC_CLQ_EGO, B, b) = (double)b;
-    SW_Q(S, MPC_CLQ_S_FINAL, B, b) = x_init[5 * (size_t)b];
-    SW_Q(S, MPC_CLQ_MAX_DEV, B, b) = fabs(x_init[5 * (size_t)b + 1]);
-    SW_Q(S, MPC_CLQ_MIN_OBS_DIST, B, b) = NAN;
-    TR_X(T, MPC_TRX_MAX_NOBS, B, b) = 0.0;
-    TR_X(T, MPC_TRX_N_RED_PASS, B, b) = 0.0;
-    TR_X(T, MPC_TRX_MIN_GAP_ACTOR, B, b) = -1.0;
+    quant_init(EgoCols{S.q, (size_t)B, (size_t)b}, b, x_init[5 * (size_t)b], x_init[5 * (size_t)b + 1]);
+    const EgoCols ex{T.ex, (size_t)B, (size_t)b};
+    ex[MPC_TRX_MAX_NOBS] = 0.0;
+    ex[MPC_TRX_N_RED_PASS] = 0.0;
+    ex[MPC_TRX_MIN_GAP_ACTOR] = -1.0;
 }
 
-// sw_fsm_kernel's transitions per actor, in index order, on the state before the step; the slab takes what the
-// actors emit in that order.  The gap and red-pass quantities are the sweep's, over every car / every light
+// actor_step per actor, in index order, on the state before the step; the slab takes what the actors emit in that
+// order.  The gap and red-pass quantities are the sweep's, over every car / every light
 __global__ void __launch_bounds__(256) tr_fsm_kernel(int B, int A, double dt, ClState C, SwState S, TrState T,
                                                      int step, int max_steps) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -71,11 +59,12 @@ __global__ void __launch_bounds__(256) tr_fsm_kernel(int B, int A, double dt, Cl
     const mpc_actor* sc = T.actors + (T.per_ego ? (size_t)b * A : 0);
     const int h = S.hslot[b];
     double* hslab = h >= 0 && T.hist_slab ? T.hist_slab + ((size_t)h * max_steps + step) * A * 2 : nullptr;
+    const EgoCols q{S.q, (size_t)B, (size_t)b}, ex{T.ex, (size_t)B, (size_t)b};
     int n = 0, green = 0, n_red = 0, have_car = 0;
     double car_s = NAN;
     int qf = S.qflags[b];
     const int qf0 = qf;
-    double gmin = SW_Q(S, MPC_CLQ_MIN_OBS_DIST, B, b);
+    double gmin = q[MPC_CLQ_MIN_OBS_DIST];
     int gact = -1;                                   // the actor that replaced the minimum at this step
     for (int a = 0; a < A; ++a) {
         const int kind = sc[a].kind;
@@ -83,70 +72,31 @@ __global__ void __launch_bounds__(256) tr_fsm_kernel(int B, int A, double dt, Cl
         const size_t ia = (size_t)a * B + b;
         int fl = T.aflags[ia];
         const int fl0 = fl;
-        double os = 0.0, ov = 0.0;
-        bool emit = false;
-        if (kind == MPC_ACTOR_CAR) {
-            if (!(fl & TR_CAR_TRIGGERED) && s >= sc[a].trigger_s) fl |= TR_CAR_TRIGGERED | TR_CAR_ACTIVE;
-            if (fl & TR_CAR_ACTIVE) {
-                ov = sc[a].v;
-                os = T.aval[ia] + ov * dt;
-                T.aval[ia] = os;
-                if (os > sc[a].end_s) {
-                    fl &= ~TR_CAR_ACTIVE;
-                } else {
-                    emit = true;
-                    if (!have_car) { have_car = 1; car_s = os; }
-                    if (os == os) {                  // a recorded car position
-                        const double g = os - s;
-                        if (!(qf & 1)) {
-                            gmin = g; gact = a;
-                            qf |= 1;
-                        } else if (g < gmin || g != g) {
-                            gmin = g; gact = a;
-                        }
-                    }
-                }
-            }
-        } else {
-            const double tl_pos = sc[a].pos_s;
-            if (!(fl & TR_TL_GREEN)) {
-                const double dist = tl_pos - s;
-                if (0.0 < dist && dist < sc[a].trigger_s) {
-                    emit = true;
-                    os = tl_pos;
-                    if (v < 0.1 && dist < 10.0) fl |= TR_TL_WAITING;
-                }
-                if (fl & TR_TL_WAITING) {
-                    const double t = T.aval[ia] + dt;
-                    T.aval[ia] = t;
-                    if (t >= sc[a].stop_duration) fl = (fl | TR_TL_GREEN) & ~TR_TL_WAITING;
-                }
-            }
-            if (fl & TR_TL_GREEN) green |= 1 << a;
-            if (!(fl & TR_PASS_DECIDED) && s > tl_pos) {
-                fl |= TR_PASS_DECIDED;
-                if (!(fl & TR_TL_GREEN)) ++n_red;
-            }
-        }
-        if (emit) {                                  // n < A: every actor emits at most once
-            T.slab[(size_t)(2 * n) * B + b] = os;
-            T.slab[(size_t)(2 * n + 1) * B + b] = ov;
-            if (hslab) { hslab[2 * n] = os; hslab[2 * n + 1] = ov; }
-            ++n;
-        }
+        double os, ov;
+        const int r = actor_step(sc[a], dt, s, v, fl, T.aval[ia], os, ov);
         if (fl != fl0) T.aflags[ia] = fl;
+        if (r & ACTOR_GREEN) green |= 1 << a;
+        if (r & ACTOR_RAN_RED) ++n_red;
+        if (!(r & ACTOR_EMITS)) continue;
+        T.slab[(size_t)(2 * n) * B + b] = os;        // n < A: every actor emits at most once
+        T.slab[(size_t)(2 * n + 1) * B + b] = ov;
+        if (hslab) { hslab[2 * n] = os; hslab[2 * n + 1] = ov; }
+        ++n;
+        if (kind != MPC_ACTOR_CAR) continue;
+        if (!have_car) { have_car = 1; car_s = os; }
+        if (os == os && min_gap(gmin, qf, os - s)) gact = a;   // a recorded car position
     }
     C.nobs[b] = n;
     if (gact >= 0) {
-        SW_Q(S, MPC_CLQ_MIN_OBS_DIST, B, b) = gmin;
-        TR_X(T, MPC_TRX_MIN_GAP_ACTOR, B, b) = (double)gact;
+        q[MPC_CLQ_MIN_OBS_DIST] = gmin;
+        ex[MPC_TRX_MIN_GAP_ACTOR] = (double)gact;
     }
     if (qf != qf0) S.qflags[b] = qf;
     if (n_red) {
-        SW_Q(S, MPC_CLQ_RED_PASS, B, b) = 1.0;
-        TR_X(T, MPC_TRX_N_RED_PASS, B, b) += (double)n_red;
+        q[MPC_CLQ_RED_PASS] = 1.0;
+        ex[MPC_TRX_N_RED_PASS] += (double)n_red;
     }
-    if ((double)n > TR_X(T, MPC_TRX_MAX_NOBS, B, b)) TR_X(T, MPC_TRX_MAX_NOBS, B, b) = (double)n;
+    if ((double)n > ex[MPC_TRX_MAX_NOBS]) ex[MPC_TRX_MAX_NOBS] = (double)n;
     if (h >= 0) {
         if (S.hist_obs_s) S.hist_obs_s[(size_t)h * max_steps + step] = car_s;
         if (S.hist_tl) S.hist_tl[(size_t)h * max_steps + step] = green;
