@@ -35,7 +35,8 @@ extern "C" {
  * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed.
  * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
  *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
- *    So were mpc_closed_loop_noisy / mpc_noise_draw and mpc_evaluate_batch / mpc_evaluate_batch_device. */
+ *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device and
+ *    mpc_closed_loop_traced. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -469,6 +470,48 @@ int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, co
  * n < 0, a NULL index array with n > 0, ego[i] < 0, or a channel outside 0 .. MPC_NZ_CHANNELS - 1: MPC_E_ARG. */
 int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const long long* ego, const int* step,
                    const int* channel, unsigned* words, double* z);
+
+/* Closed-loop plan traces: mpc_closed_loop_noisy that also keeps the plan behind each applied control, the sixth
+ * return value of the reference's run_simulation (hist_preds, trajectory_tracking.py:389, :416), and accumulates
+ * on the device how far every ego ended up from what it planned.  The arguments are mpc_closed_loop_noisy's, in
+ * its order, followed by the trace outputs.
+ *   hist_pred    [n_hist][max_steps][N+1][5]: for named ego hist_egos[k] at step t exactly what the solver
+ *                returned as Xpred for the inputs it was handed at that step (the measured state hist_xm[k][t]
+ *                and the perceived slab), so stage 0 is the measured state.  NaN past n_steps.
+ *   hist_plan    [n_hist][max_steps][N][2]: the solver's U of that step; hist_plan[k][t][0] is hist_u[k][t].
+ *                NaN past n_steps.
+ *   lookahead, n_look   0 <= n_look <= MPC_MAX_LOOK; each 1 <= lookahead[i] <= N, distinct.
+ *   gapq         [B][n_look][MPC_TG_NQ], required iff n_look > 0: plan-vs-outcome gaps of every ego.  With x_r the
+ *                true state row r of the ego (row 0 is x_init, row r the state after step r - 1: hist_x's rows)
+ *                and P_t[j] stage j of the prediction made at step t, lookahead j = lookahead[i] compares the
+ *                pairs (P_t[j], x_{t+j}) for t = 0 .. n_steps - 1 with t + j <= n_steps: the final state is
+ *                compared, predictions that reach past the ego's exit are not.  The truth is compared, not the
+ *                measurement: like every MPC_CLQ_* quantity of the noisy entry the gap judges the world.
+ * With n_look == 0 and hist_pred == hist_plan == NULL the call launches exactly the noisy entry's kernels and every
+ * output equals mpc_closed_loop_noisy's bit for bit.  With any trace output requested the solver is also asked for
+ * its U and Xpred, two more kernels run per step, and every output the noisy entry has still equals the noisy
+ * entry's bit for bit.
+ * Misuse: the noisy entry's cases, n_look out of range, a lookahead outside 1 .. N or repeated, lookahead NULL with
+ * n_look > 0, gapq NULL with n_look > 0 or given with n_look == 0, hist_pred or hist_plan with n_hist == 0:
+ * MPC_E_ARG.
+ * Device memory is the noisy entry's, O(B * (A + K)) + O(n_hist * max_steps * (A + K)), plus, only when a trace
+ * output is requested, O(B * N) for the solver's U and Xpred of the listed egos, O(B * sum(lookahead) * 3) for the
+ * prediction rings, O(B * n_look) for the gaps and O(n_hist * max_steps * N) for the two histories. */
+#define MPC_MAX_LOOK 4
+#define MPC_TG_N_CMP 0            /* number of pairs, max(0, n_steps - j + 1)                                  */
+#define MPC_TG_MAX_DS 1           /* max over the pairs of |P_t[j].c - x_{t+j}.c| for c = s, d, v: the sweep's   */
+#define MPC_TG_MAX_DD 2           /* NaN rule (a NaN difference enters and stays); NaN when there is no pair     */
+#define MPC_TG_MAX_DV 3
+#define MPC_TG_STEP_DD 4          /* the t of the pair that holds MAX_DD: the earliest on ties, the first NaN
+                                     pair if there is one; -1.0 when there is no pair                          */
+#define MPC_TG_NQ 5
+int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                           const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
+                           unsigned long long seed, long long ego_offset, int max_steps, double s_stop, double* quant,
+                           double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u,
+                           double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                           int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
+                           const int* lookahead, int n_look, double* gapq, double* hist_pred, double* hist_plan);
 
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no

@@ -1,5 +1,5 @@
-// closed_loop_host.h -- the host-side driver behind the five closed-loop entries of the C ABI (mpc_closed_loop,
-// _sweep, _traffic, _convoy, _noisy).  Included by mpcqp.hip below launch_solve: it uses that file's fail(), mpc_ctx
+// closed_loop_host.h -- the host-side driver behind the six closed-loop entries of the C ABI (mpc_closed_loop,
+// _sweep, _traffic, _convoy, _noisy, _traced).  Included by mpcqp.hip below launch_solve: it uses that file's fail(), mpc_ctx
 // and launch_solve, and the state structs of the closed-loop kernel headers.
 //
 // An entry checks its arguments, declares its buffers and outputs on a ClDriver, launches its own init kernels and
@@ -120,7 +120,7 @@ struct ClDriver {
         const void* host;
         size_t bytes;
     };
-    enum { MAX_OUTS = 12, MAX_INS = 4 };
+    enum { MAX_OUTS = 16, MAX_INS = 4 };
     Out outs[MAX_OUTS];
     In ins[MAX_INS];
     int n_outs = 0, n_ins = 0;
@@ -257,9 +257,12 @@ struct ClDriver {
     // (FSM, leaders, gather or measurement; lg: the grid of one thread per listed ego), launch_solve runs on the
     // nl listed egos (with the slab when with_obs), plant(step, nl, lg) launches the plant kernel.  The solve
     // runs on the egos still in the loop: the list is rebuilt at the every-8-steps host sync whenever egos have
-    // left, so retired egos stop costing solver work (results are per ego, unchanged).  timed: record the ring
+    // left, so retired egos stop costing solver work (results are per ego, unchanged).  timed: record the ring.
+    // Ua [B][N][2], Xpa [B][N+1][5] (device, optional): the solver's U and Xpred of the listed egos, by list
+    // position, for the plant callable to use; u0 and the status do not depend on whether they are asked for
     template <typename Pre, typename Plant>
-    int run(const KParams& kp, bool with_obs, bool timed, Pre pre, Plant plant) {
+    int run(const KParams& kp, bool with_obs, bool timed, Pre pre, Plant plant, double* Ua = nullptr,
+            double* Xpa = nullptr) {
         if (timed) {
             for (auto& e : ev)
                 if (hipEventCreate(&e) != hipSuccess) {
@@ -276,7 +279,7 @@ struct ClDriver {
                 const dim3 lg((nl + 255) / 256);
                 pre(step, nl, lg);
                 rc = launch_solve(c, kp, nl, C.xa, with_obs ? C.obsa : nullptr, with_obs ? C.nobsa : nullptr, nullptr,
-                                  C.u0a, nullptr, nullptr, C.sta, nullptr, st);
+                                  C.u0a, Ua, Xpa, C.sta, nullptr, st);
                 if (rc) break;
                 if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {
                     rc = fail(MPC_E_DEVICE, msg("active-count reset"));

@@ -1257,12 +1257,20 @@ struct Backend {
     // egos still in the loop; rank(alist) (the convoys' ordering; a no-op elsewhere); for the i-th listed ego b,
     // sense(step, b, xs, obs) fills the state xs [5] and the slab obs [ow][2] the solver receives and returns
     // n_obs; one batched solve over the list (with the slab when with_obs, p.max_obs == ow); then
-    // plant(step, b, u0, status) per listed ego.  The step times go to E.ms and the optional E.step_ms
+    // plant(step, b, u0, status) per listed ego.  The step times go to E.ms and the optional E.step_ms.
+    // planned: the solver is also asked for its U and Xpred, and after the plant steps trace(step, b, U, Xpred)
+    // runs per listed ego
     template <typename Rank, typename Sense, typename Plant>
     void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
                   Plant plant) const {
+        run_loop(p, E, max_steps, with_obs, ow, rank, sense, plant, false, [](int, int, const double*, const double*) {});
+    }
+    template <typename Rank, typename Sense, typename Plant, typename Trace>
+    void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
+                  Plant plant, bool planned, Trace trace) const {
         std::vector<int> alist, nobsa, sta;
-        std::vector<double> xa, obsa, u0a;
+        std::vector<double> xa, obsa, u0a, Ua, Xpa;
+        const size_t nu = 2 * (size_t)p.N, nxp = 5 * ((size_t)p.N + 1);
         for (int step = 0; step < max_steps; ++step) {
             const auto t0 = std::chrono::steady_clock::now();
             alist.clear();
@@ -1278,9 +1286,15 @@ struct Backend {
             sta.assign(nl, 0);
             for (int i = 0; i < nl; ++i)
                 nobsa[i] = sense(step, alist[i], xa.data() + 5 * (size_t)i, obsa.data() + (size_t)i * ow * 2);
+            if (planned) {
+                Ua.assign((size_t)nl * nu, 0.0);
+                Xpa.assign((size_t)nl * nxp, 0.0);
+            }
             solve_batch(p, nl, xa.data(), with_obs ? obsa.data() : nullptr, with_obs ? nobsa.data() : nullptr, nullptr,
-                        u0a.data(), nullptr, nullptr, sta.data(), nullptr);
+                        u0a.data(), planned ? Ua.data() : nullptr, planned ? Xpa.data() : nullptr, sta.data(), nullptr);
             for (int i = 0; i < nl; ++i) plant(step, alist[i], u0a.data() + 2 * (size_t)i, sta[i]);
+            if (planned)
+                for (int i = 0; i < nl; ++i) trace(step, alist[i], Ua.data() + (size_t)i * nu, Xpa.data() + (size_t)i * nxp);
             E.ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             if (E.step_ms) E.step_ms[step] = E.ms.back();
         }
@@ -1348,6 +1362,10 @@ struct Backend {
     //     leader ranking, the gap quantities, hist_slab and the exit test use the true states; the solver receives
     //     x + meas_sigma * z and a perturbed copy of the slab; the plant integrates the clamped u + act_sigma * z
     //     and adds (dt * proc_sigma) * z.
+    //   traces (n_look > 0, hist_pred or hist_plan): the solver's U and Xpred of every step are kept; after the
+    //     plant step every ego stores stage j of its prediction in its ring for lookahead j and compares its new true
+    //     state with the prediction made j - 1 steps before (loop_steps.h, trace_gap); gapq is
+    //     [B][n_look][MPC_TG_NQ], hist_pred [n_hist][max_steps][N+1][5], hist_plan [n_hist][max_steps][N][2].
     // extra is [B][nx] (MPC_TR_NX; MPC_CV_NX with worlds; MPC_NZ_NX with noise); extra, n_steps, step_ms and every
     // history are optional; hist_slab is [n_hist][max_steps][A+K][2], hist_lead [n_hist][max_steps][K]
     int closed_loop_scripted(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
@@ -1356,7 +1374,8 @@ struct Backend {
                              double* quant, double* extra, int nx, int n_hist, const int* slot, double* hist_x,
                              double* hist_u, double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl,
                              int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
-                             double* step_ms) const {
+                             double* step_ms, const int* lookahead = nullptr, int n_look = 0, double* gapq = nullptr,
+                             double* hist_pred = nullptr, double* hist_plan = nullptr) const {
         mpc_params p = p0;
         const int AK = A + K;
         p.max_obs = with_slab ? AK : 0;
@@ -1369,6 +1388,17 @@ struct Backend {
         hist_prefill(hist_nobs, nh * ns, -1);
         hist_prefill(hist_slab, nh * ns * nak * 2, (double)NAN);
         hist_prefill(hist_lead, nh * ns * nk, -1);
+        const size_t nu = 2 * (size_t)p.N, nxp = 5 * ((size_t)p.N + 1);
+        hist_prefill(hist_pred, nh * ns * nxp, (double)NAN);
+        hist_prefill(hist_plan, nh * ns * nu, (double)NAN);
+        size_t slots = 0;                                 // ring slots of one ego, lookahead i's from ring0[i] on
+        size_t ring0[MPC_MAX_LOOK] = {};
+        for (int i = 0; i < n_look; ++i) {
+            ring0[i] = slots;
+            slots += (size_t)lookahead[i];
+        }
+        std::vector<double> ring(nb * slots * 3, 0.0);
+        for (size_t k = 0; k < nb * (size_t)n_look; ++k) trace_init(gapq + k * MPC_TG_NQ);
         LoopEgos E(B, x_init, max_steps, s_stop, quant, n_hist, slot, hist_x, hist_u, hist_status, step_ms);
         const mpc_noise quiet = {};
         std::vector<double> aval(nb * na, 0.0), ex(nb * nxs, 0.0);
@@ -1470,6 +1500,26 @@ struct Backend {
                          std::memcpy(hist_ua + ((size_t)slot[b] * ns + step) * 2, ua, sizeof(ua));
                      extremes4(e, MPC_NZX_U1A_MIN, step, ua[0], ua[1]);
                      if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
+                 },
+                 n_look > 0 || hist_pred || hist_plan,
+                 [&](int step, int b, const double* U, const double* Xp) {
+                     const double* x = E.x.data() + 5 * (size_t)b;       // the true state after the step
+                     for (int i = 0; i < n_look; ++i) {
+                         const int j = lookahead[i];
+                         double* rg = ring.data() + ((size_t)b * slots + ring0[i]) * 3;
+                         double* w = rg + 3 * (size_t)trace_slot(step, j);
+                         w[0] = Xp[5 * j];
+                         w[1] = Xp[5 * j + 1];
+                         w[2] = Xp[5 * j + 4];
+                         if (!trace_pair(step, j)) continue;
+                         const int t0 = step + 1 - j;                    // j == 1: the slot just written
+                         const double* r = rg + 3 * (size_t)trace_slot(t0, j);
+                         trace_gap(gapq + ((size_t)b * n_look + i) * MPC_TG_NQ, t0, r[0], r[1], r[2], x[0], x[1], x[4]);
+                     }
+                     if (slot[b] < 0) return;
+                     const size_t h = (size_t)slot[b] * ns + step;
+                     if (hist_pred) std::memcpy(hist_pred + h * nxp, Xp, nxp * sizeof(double));
+                     if (hist_plan) std::memcpy(hist_plan + h * nu, U, nu * sizeof(double));
                  });
         E.finish(n_steps);
         if (extra) std::memcpy(extra, ex.data(), nb * nxs * sizeof(double));
@@ -1511,6 +1561,21 @@ struct Backend {
                                     seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
                                     hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
                                     hist_lead, n_steps, step_ms);
+    }
+
+    // mpc_closed_loop_traced on the host: the noisy loop with the plans kept and the plan-vs-outcome gaps
+    int closed_loop_traced(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
+                           const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
+                           int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
+                           double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
+                           double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                           int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
+                           const int* lookahead, int n_look, double* gapq, double* hist_pred,
+                           double* hist_plan) const {
+        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
+                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
+                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
+                                    hist_lead, n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan);
     }
 };
 

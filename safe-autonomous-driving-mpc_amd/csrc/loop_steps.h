@@ -203,6 +203,51 @@ LOOP_STEP inline void plant_quant(Q q, int step, const double* x, double u1, dou
 }
 
 // ------------------------------------------------------------------------------------------
+// the plan-vs-outcome gaps of mpc_closed_loop_traced (include/mpcqp.h, MPC_TG_*)
+// ------------------------------------------------------------------------------------------
+// Lookahead j keeps the (s, d, v) of stage j of the last j predictions in a ring of j slots: the prediction made
+// at step t takes slot t mod j
+LOOP_STEP inline int trace_slot(int t, int j) { return t % j; }
+
+// the state after step t is row t + 1 of the ego: it pairs with the prediction made at step t + 1 - j, if any
+LOOP_STEP inline bool trace_pair(int t, int j) { return t + 1 >= j; }
+
+// the row of an ego and a lookahead before the first pair, which one without pairs keeps
+template <typename Q>
+LOOP_STEP inline void trace_init(Q g) {
+    g[MPC_TG_N_CMP] = 0.0;
+    g[MPC_TG_MAX_DS] = NAN;
+    g[MPC_TG_MAX_DD] = NAN;
+    g[MPC_TG_MAX_DV] = NAN;
+    g[MPC_TG_STEP_DD] = -1.0;
+}
+
+// One pair: (ps, pd, pv) predicted at step t0 against the true (xs, xd, xv).  The first pair seeds the maxima, the
+// later ones enter by keep_max; MAX_DD's step moves only when the maximum grows or turns NaN, so ties and later
+// NaNs leave it at the earliest (numpy's argmax)
+template <typename Q>
+LOOP_STEP inline void trace_gap(Q g, int t0, double ps, double pd, double pv, double xs, double xd, double xv) {
+    const double ds = fabs(ps - xs), dd = fabs(pd - xd), dv = fabs(pv - xv);
+    const double n = g[MPC_TG_N_CMP];
+    g[MPC_TG_N_CMP] = n + 1.0;
+    if (n == 0.0) {
+        g[MPC_TG_MAX_DS] = ds;
+        g[MPC_TG_MAX_DD] = dd;
+        g[MPC_TG_MAX_DV] = dv;
+        g[MPC_TG_STEP_DD] = (double)t0;
+        return;
+    }
+    double ms = g[MPC_TG_MAX_DS], mv = g[MPC_TG_MAX_DV];
+    const double md = g[MPC_TG_MAX_DD];
+    if (keep_max(ms, ds)) g[MPC_TG_MAX_DS] = ds;
+    if (keep_max(mv, dv)) g[MPC_TG_MAX_DV] = dv;
+    if (dd > md || (dd != dd && md == md)) {
+        g[MPC_TG_MAX_DD] = dd;
+        g[MPC_TG_STEP_DD] = (double)t0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // the noise source of mpc_closed_loop_noisy (include/mpcqp.h): stateless Philox4x32-10, one block per variate
 // ------------------------------------------------------------------------------------------
 #define NZ_M0 0xD2511F53u

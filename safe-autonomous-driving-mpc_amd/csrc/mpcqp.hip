@@ -25,6 +25,7 @@
 //   traffic_kernels.h      the traffic scripts' FSM / gather kernels (up to 16 actors per ego)
 //   convoy_kernels.h       the convoys' leader-ranking kernel (a workgroup per world)
 //   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
+//   trace_kernels.h        the plan traces' gap and history kernels (the solver's U / Xpred of every step)
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points; the driver the closed-loop entries share is closed_loop_host.h) and, last, the comm
@@ -50,6 +51,7 @@
 #include "traffic_kernels.h"
 #include "convoy_kernels.h"
 #include "noise_kernels.h"
+#include "trace_kernels.h"
 #include "evaluate_kernel.h"
 
 // ------------------------------------------------------------------------------------------
@@ -801,8 +803,9 @@ extern "C" void mpc_actors_from_fsm(const mpc_fsm* f, mpc_actor out[2]) {
 
 extern "C" void mpc_default_noise(mpc_noise* n) { std::memset(n, 0, sizeof(*n)); }
 
-// What the three scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
-// worlds, K == 0), mpc_closed_loop_convoy, and mpc_closed_loop_noisy (noisy; noise is then never NULL)
+// What the four scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
+// worlds, K == 0), mpc_closed_loop_convoy, mpc_closed_loop_noisy (noisy; noise is then never NULL) and
+// mpc_closed_loop_traced (noisy, with the trace outputs at the end; the other three leave them empty)
 struct ScriptedLoop {
     const char* label;
     int B, W, K;
@@ -827,12 +830,17 @@ struct ScriptedLoop {
     int* hist_lead;
     int* n_steps;
     double* step_ms;
+    const int* lookahead;
+    int n_look;
+    double *gapq, *hist_pred, *hist_plan;
 };
 
 // The loop of the scripted entries around tr_fsm_kernel and an (A + K)-wide slab.  With worlds, cv_lead_kernel
 // ranks the leaders between the FSM and the gather and writes the slab histories (tr_fsm_kernel's rows are A
 // wide).  Noisy: nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel, on the field-major
-// sigma table [14][B] for per-ego noise; the other kernels are reused untouched and see the true states
+// sigma table [14][B] for per-ego noise; the other kernels are reused untouched and see the true states.  Traced
+// (any trace output asked for): the solver also writes its U and Xpred of the listed egos, and tg_gap_kernel and
+// tg_hist_kernel follow the plant kernel
 static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     const int B = a.B, A = a.A, K = a.K, AK = A + K, max_steps = a.max_steps;
     std::vector<int> slot;
@@ -845,9 +853,17 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     const bool per_ego = a.n_scripts == B && B > 1;  // n_scripts == B == 1 is the shared case
     const int nsc = per_ego ? B : (a.actors ? 1 : 0);
     const bool nz_per_ego = a.noisy && a.n_noise == B && B > 1;
+    const bool traced = a.n_look > 0 || a.hist_pred || a.hist_plan;
     if (c->cpu)
         return host_loop([&] {
             const int hsc = nsc == 0 ? 1 : nsc;
+            if (traced)
+                return c->cpu->closed_loop_traced(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
+                                                  a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
+                                                  a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
+                                                  a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
+                                                  a.hist_slab, a.hist_lead, a.n_steps, a.step_ms, a.lookahead, a.n_look,
+                                                  a.gapq, a.hist_pred, a.hist_plan);
             if (a.noisy)
                 return c->cpu->closed_loop_noisy(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
                                                  a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
@@ -910,6 +926,31 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
         Z.hist_ua = D.out(a.hist_ua, nhs * 2);
         Z.hist_xm = D.out(a.hist_xm, nhs * 5);
     }
+    TgState G = {};
+    std::vector<double> hgap;               // the gaps as the device keeps them, [n_look][MPC_TG_NQ][B]
+    double *d_U = nullptr, *d_Xp = nullptr;
+    if (traced) {
+        const size_t nN = (size_t)c->p.N;
+        try {
+            hgap.resize((size_t)a.n_look * MPC_TG_NQ * D.nb);
+        } catch (const std::bad_alloc&) {
+            return fail(MPC_E_ALLOC, "gap table");
+        }
+        size_t slots = 0;
+        for (int i = 0; i < a.n_look; ++i) {
+            G.look[i] = a.lookahead[i];
+            G.ring0[i] = (int)slots;
+            slots += (size_t)a.lookahead[i];
+        }
+        G.N = c->p.N;
+        G.n_look = a.n_look;
+        G.Ua = d_U = D.mem.alloc<double>(D.nb * nN * 2);
+        G.Xpa = d_Xp = D.mem.alloc<double>(D.nb * (nN + 1) * 5);
+        G.ring = D.mem.alloc<double>(slots * 3 * D.nb);
+        G.gq = D.out(hgap.data(), hgap.size(), false);
+        G.hist_pred = D.out(a.hist_pred, nhs * (nN + 1) * 5);
+        G.hist_plan = D.out(a.hist_plan, nhs * nN * 2);
+    }
     rc = D.begin();
     if (rc) return rc;
     const dim3 tb = D.tb, tg = D.tg;
@@ -917,6 +958,7 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, D.xinit, a.s_stop, max_steps);
     if (a.W) hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
     if (a.noisy) hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
+    if (G.n_look) hipLaunchKernelGGL(tg_init_kernel, tg, tb, 0, st, B, G);
     rc = D.run(kp, a.with_slab, true,
                [&](int step, int nl, dim3 lg) {
                    hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
@@ -931,8 +973,19 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
                    else
                        hipLaunchKernelGGL(sw_plant_kernel, lg, tb, 0, st, c->tab, B, nl, kp.dt, C, S, a.s_stop, step,
                                           max_steps);
-               });
-    return rc ? rc : D.finish(S, T.ex, a.nx, a.quant, a.extra, a.n_steps, a.step_ms);
+                   if (G.n_look) hipLaunchKernelGGL(tg_gap_kernel, lg, tb, 0, st, nl, B, C, S, G, step);
+                   if (G.hist_pred || G.hist_plan) {
+                       const size_t ne = (size_t)nl * (size_t)(7 * G.N + 5);    // 5 (N + 1) + 2 N elements per ego
+                       hipLaunchKernelGGL(tg_hist_kernel, dim3((unsigned)((ne + 255) / 256)), tb, 0, st, nl, C, S, G, step,
+                                          max_steps);
+                   }
+               },
+               d_U, d_Xp);
+    if (rc == MPC_SUCCESS) rc = D.finish(S, T.ex, a.nx, a.quant, a.extra, a.n_steps, a.step_ms);
+    if (rc == MPC_SUCCESS)                  // field-major on the device, one row per ego and lookahead outside
+        for (size_t b = 0; b < D.nb; ++b)
+            for (size_t k = 0; k < (size_t)a.n_look * MPC_TG_NQ; ++k) a.gapq[b * a.n_look * MPC_TG_NQ + k] = hgap[k * D.nb + b];
+    return rc;
 }
 
 // mpc_closed_loop_sweep with a script of A actors per ego (include/mpcqp.h)
@@ -951,7 +1004,8 @@ extern "C" int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, 
     if (hist_slab && A == 0) return fail(MPC_E_ARG, "hist_slab is given but A == 0");
     const ScriptedLoop a = {"traffic", B, 0, 0, INFINITY, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
                             max_steps, s_stop, quant, extra, MPC_TR_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
-                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps, step_ms};
+                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps, step_ms,
+                            nullptr, 0, nullptr, nullptr, nullptr};
     return scripted_loop(c, a);
 }
 
@@ -976,19 +1030,20 @@ extern "C" int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double le
     if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
     const ScriptedLoop a = {"convoy", B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
                             max_steps, s_stop, quant, extra, MPC_CV_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
-                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms};
+                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms,
+                            nullptr, 0, nullptr, nullptr, nullptr};
     return scripted_loop(c, a);
 }
 
-// mpc_closed_loop_convoy with seeded noise between the world and the solver (include/mpcqp.h).  noise == NULL runs
-// the same kernels on an all-zero shared struct
-extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
-                                     const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise,
-                                     int n_noise, unsigned long long seed, long long ego_offset, int max_steps,
-                                     double s_stop, double* quant, double* extra, int n_hist, const int* hist_egos,
-                                     double* hist_x, double* hist_u, double* hist_ua, double* hist_xm,
-                                     double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
-                                     double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) {
+// mpc_closed_loop_noisy and mpc_closed_loop_traced (include/mpcqp.h) behind one argument check: the noisy entry is
+// the traced one with no trace output.  noise == NULL runs the same kernels on an all-zero shared struct
+static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                       const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
+                       unsigned long long seed, long long ego_offset, int max_steps, double s_stop, double* quant,
+                       double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u, double* hist_ua,
+                       double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                       double* hist_slab, int* hist_lead, int* n_steps, double* step_ms, const int* lookahead,
+                       int n_look, double* gapq, double* hist_pred, double* hist_plan) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
     int rc = cl_check_world(B, W, K, A, lead_range);
@@ -1000,8 +1055,17 @@ extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lea
         return fail(MPC_E_ARG, "n_noise must be B (a struct per ego), 1 (shared) or 0 with noise NULL");
     if (ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
     rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status ||
-                                             hist_nobs || hist_slab || hist_lead);
+                                             hist_nobs || hist_slab || hist_lead || hist_pred || hist_plan);
     if (rc) return rc;
+    if (n_look < 0 || n_look > MPC_MAX_LOOK) return fail(MPC_E_ARG, "n_look out of range [0, 4]");
+    if (n_look > 0 && !lookahead) return fail(MPC_E_ARG, "lookahead is NULL but n_look > 0");
+    if (n_look > 0 ? !gapq : gapq != nullptr)
+        return fail(MPC_E_ARG, "gapq is required with n_look > 0 and must be NULL with n_look == 0");
+    for (int i = 0; i < n_look; ++i) {
+        if (lookahead[i] < 1 || lookahead[i] > c->p.N) return fail(MPC_E_ARG, "a lookahead is outside [1, N]");
+        for (int k = 0; k < i; ++k)
+            if (lookahead[k] == lookahead[i]) return fail(MPC_E_ARG, "a lookahead is repeated");
+    }
     if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
     if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
     for (size_t k = 0; k < (size_t)n_noise * NZ_NSIG; ++k)       // mpc_noise is NZ_NSIG doubles, no padding
@@ -1010,11 +1074,39 @@ extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lea
     mpc_noise zero;
     mpc_default_noise(&zero);
     if (!noise) noise = &zero;
-    const ScriptedLoop a = {"noisy-loop", B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, true, noise, n_noise,
+    const ScriptedLoop a = {label, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, true, noise, n_noise,
                             seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, hist_egos, hist_x,
                             hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead,
-                            n_steps, step_ms};
+                            n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan};
     return scripted_loop(c, a);
+}
+
+extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                                     const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise,
+                                     int n_noise, unsigned long long seed, long long ego_offset, int max_steps,
+                                     double s_stop, double* quant, double* extra, int n_hist, const int* hist_egos,
+                                     double* hist_x, double* hist_u, double* hist_ua, double* hist_xm,
+                                     double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                                     double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) {
+    return noisy_entry("noisy-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed, ego_offset,
+                       max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
+                       hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, nullptr, 0, nullptr,
+                       nullptr, nullptr);
+}
+
+extern "C" int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                                      const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise,
+                                      int n_noise, unsigned long long seed, long long ego_offset, int max_steps,
+                                      double s_stop, double* quant, double* extra, int n_hist, const int* hist_egos,
+                                      double* hist_x, double* hist_u, double* hist_ua, double* hist_xm,
+                                      double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
+                                      double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
+                                      const int* lookahead, int n_look, double* gapq, double* hist_pred,
+                                      double* hist_plan) {
+    return noisy_entry("traced-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed,
+                       ego_offset, max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm,
+                       hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, lookahead,
+                       n_look, gapq, hist_pred, hist_plan);
 }
 
 // the draws of mpc_closed_loop_noisy on their own (include/mpcqp.h), on the context's backend

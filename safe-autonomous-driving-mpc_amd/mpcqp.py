@@ -67,7 +67,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traced", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -93,6 +93,11 @@ NZ_CH_MEAS, NZ_CH_ACT, NZ_CH_PROC, NZ_CH_PERC, NZ_CHANNELS = 0, 5, 7, 16, 48
 NZX_U1A_MIN, NZX_U1A_MAX, NZX_U2A_MIN, NZX_U2A_MAX, NZX_N_CLAMPED = 6, 7, 8, 9, 10
 NZ_NX = 11
 NZX_FIELDS = CVX_FIELDS + ("u1a_min", "u1a_max", "u2a_min", "u2a_max", "n_clamped")
+# mpc_closed_loop_traced: the lookahead limit and the columns of a gapq row (MPC_TG_*)
+MAX_LOOK = 4
+TG_N_CMP, TG_MAX_DS, TG_MAX_DD, TG_MAX_DV, TG_STEP_DD = 0, 1, 2, 3, 4
+TG_NQ = 5
+TG_FIELDS = ("n_cmp", "max_ds", "max_dd", "max_dv", "step_dd")
 # mpc_evaluate_batch: the columns of its per-instance summary (MPC_EVQ_*)
 EVQ_COST, EVQ_MIN_ROW, EVQ_ARGMIN_STAGE, EVQ_ARGMIN_KIND, EVQ_L1, EVQ_N_NEG = 0, 1, 2, 3, 4, 5
 EVQ_MIN_LANE, EVQ_MIN_OBS, EVQ_MIN_V, EVQ_BOX = 6, 7, 8, 9
@@ -163,6 +168,8 @@ def lib():
                                         C.c_int, C.c_int, C.POINTER(MpcNoise), C.c_int, C.c_ulonglong, C.c_longlong,
                                         C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _ip,
                                         _ip, _ip, _dp, _ip, _ip, _dp]
+    L.mpc_closed_loop_traced.restype = C.c_int
+    L.mpc_closed_loop_traced.argtypes = L.mpc_closed_loop_noisy.argtypes + [_ip, C.c_int, _dp, _dp, _dp]
     L.mpc_noise_draw.restype = C.c_int
     L.mpc_noise_draw.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.POINTER(C.c_longlong), _ip, _ip,
                                  C.POINTER(C.c_uint), _dp]
@@ -519,6 +526,24 @@ class Solver:
         Returns closed_loop_convoy's dict with extra [B,11] (columns NZX_FIELDS), hist_ua [n_hist,max_steps,2] (the
         applied controls; hist_u stays the commanded ones) and hist_xm [n_hist,max_steps,5] (the state the solver
         was given)."""
+        return self._closed_loop_noisy(x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise,
+                                       seed, lo, None)
+
+    def closed_loop_traced(self, x_init, W=1, K=0, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
+                           s_max=None, hist_egos=(), noise=None, seed=0, lo=0, lookahead=(), preds=False, plans=False):
+        """mpc_closed_loop_traced: closed_loop_noisy that keeps the plan behind each applied control.  lookahead: up
+        to MAX_LOOK distinct stages j in 1 .. N; preds / plans: keep the solver's Xpred / U of every step for the
+        egos of hist_egos.
+        Returns closed_loop_noisy's dict, plus gapq [B,len(lookahead),5] (columns TG_FIELDS: the plan-vs-outcome gaps
+        of every ego, stage j of the prediction made at step t against the true state j steps later) when lookahead
+        is not empty, hist_pred [n_hist,max_steps,N+1,5] with preds and hist_plan [n_hist,max_steps,N,2] with plans
+        (NaN past n_steps)."""
+        return self._closed_loop_noisy(x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise,
+                                       seed, lo, (lookahead, preds, plans))
+
+    def _closed_loop_noisy(self, x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise, seed,
+                           lo, trace):
+        """closed_loop_noisy (trace None) or closed_loop_traced (trace = (lookahead, preds, plans))."""
         x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
         B = x_init.shape[0]
         if s_stop is None:
@@ -551,16 +576,31 @@ class Solver:
         hd = np.empty((nh, max_steps, max(K, 0)), np.int32)
         g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
         gi = (lambda a: _pi(a) if nh else None)
-        _check(lib().mpc_closed_loop_noisy(self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A),
-                                           int(n_scripts), nz, int(n_noise), int(seed), int(lo), int(max_steps),
-                                           float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(ha),
-                                           g(hm), g(hc), gi(ht), gi(hs), gi(hn), g(hl) if A + K > 0 else None,
-                                           gi(hd) if K > 0 else None, _pi(ns), _p(sm)), "mpc_closed_loop_noisy")
+        args = (self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A), int(n_scripts), nz, int(n_noise),
+                int(seed), int(lo), int(max_steps), float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(ha),
+                g(hm), g(hc), gi(ht), gi(hs), gi(hn), g(hl) if A + K > 0 else None, gi(hd) if K > 0 else None, _pi(ns),
+                _p(sm))
+        more = {}
+        if trace is None:
+            _check(lib().mpc_closed_loop_noisy(*args), "mpc_closed_loop_noisy")
+        else:
+            lookahead, preds, plans = trace
+            N = self.params.N
+            look = np.ascontiguousarray(lookahead, np.int32).ravel()
+            if look.size:
+                more["gapq"] = np.empty((B, look.size, TG_NQ))
+            if preds:
+                more["hist_pred"] = np.empty((nh, max_steps, N + 1, 5))
+            if plans:
+                more["hist_plan"] = np.empty((nh, max_steps, N, 2))
+            _check(lib().mpc_closed_loop_traced(*args, _pi(look) if look.size else None, int(look.size),
+                                                _p(more.get("gapq")), g(more.get("hist_pred")),
+                                                g(more.get("hist_plan"))), "mpc_closed_loop_traced")
         quant[:, 0] += lo
         extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
         return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
                     hist_ua=ha, hist_xm=hm, hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl,
-                    hist_lead=hd)
+                    hist_lead=hd, **more)
 
     def noise_draw(self, seed, ego, step, channel):
         """mpc_noise_draw on this context's backend: the Philox words [n,4] (uint32) and the variates z [n] of

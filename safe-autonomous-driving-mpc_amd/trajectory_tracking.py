@@ -607,6 +607,37 @@ def run_noisy_sweep(mpc, trajectory, x_init, noise, seeds, W=1, K=0, lead_range=
     return r
 
 
+def run_simulation_traced(mpc, fsms, trajectory, hist_egos=None, max_steps=2000, x_init=None):
+    """run_simulation (trajectory_tracking.py:377-443) for a list of ObstaclesFSM scenarios (None: no scenario) in
+    one library call that keeps every step's prediction (mpc_closed_loop_traced): ego b runs fsms[b] restated as a
+    two-actor script, from x_init[b] (default: the reference start [0,0,0,0,0.5], :382) while s <= s_max - 1.
+    Returns, for each ego of hist_egos (default: every ego), the reference's tuple
+        hist_x [n+1,5], hist_u [n,2], hist_t [n], hist_preds, hist_obs_s, hist_tl_state, trajectory
+    cut at the ego's n steps: hist_preds a list of n (N+1, 5) arrays, hist_obs_s a list of car positions (NaN: no
+    car), hist_tl_state a list of 'RED' / 'GREEN', hist_t the step times of the whole batch in seconds.  The tuple
+    feeds driving_animation and plot_tracking_results as run_simulation's does.  Prints nothing and runs no
+    sanity check."""
+    fsms = list(fsms)
+    B = len(fsms)
+    if x_init is None:
+        x_init = np.tile(np.array([0.0, 0.0, 0.0, 0.0, 0.5]), (B, 1))
+    x_init = np.asarray(x_init, np.float64).reshape(-1, 5)
+    if x_init.shape[0] != B:
+        raise ValueError("one start state per scenario")
+    hist_egos = list(range(B)) if hist_egos is None else [int(e) for e in hist_egos]
+    scripts = [TrafficScript.from_fsm(f).actors for f in fsms]
+    r = mpc.solver(max_obs=0).closed_loop_traced(x_init, scripts=scripts, max_steps=max_steps, s_max=trajectory.s_max,
+                                                 hist_egos=hist_egos, preds=True)
+    out = []
+    for k, b in enumerate(hist_egos):
+        n = int(r["n_steps"][b])
+        green = (r["hist_tl"][k, :n] & 2) != 0            # actor 1 of the script is the light
+        out.append((r["hist_x"][k, :n + 1].copy(), r["hist_u"][k, :n].copy(), r["step_ms"][:n] / 1000.0,
+                    [r["hist_pred"][k, t].copy() for t in range(n)], [float(v) for v in r["hist_car_s"][k, :n]],
+                    ["GREEN" if g else "RED" for g in green], trajectory))
+    return out
+
+
 def closed_loop_checks(mpc, fsm, trajectory, r, verbose=False):
     """The restated trajectory_tracking_check (sanity_checks.py:79-184) on every ego of a closed_loop()
     result (mpcqp.Solver.closed_loop layout); returns the per-ego verdicts [B] (bool)."""
