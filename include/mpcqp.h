@@ -35,8 +35,8 @@ extern "C" {
  * 4: mpc_closed_loop_sweep, mpc_cl_verdicts; nothing else changed.
  * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
  *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
- *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device and
- *    mpc_closed_loop_traced. */
+ *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device,
+ *    mpc_closed_loop_traced and mpc_closed_loop_warm / mpc_default_warm. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -512,6 +512,57 @@ int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double lead_range, c
                            double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
                            int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
                            const int* lookahead, int n_look, double* gapq, double* hist_pred, double* hist_plan);
+
+/* Closed-loop warm starts: mpc_closed_loop_traced whose steps may linearise about the ego's own previous plan, the
+ * real-time iteration: one QP per step that follows the nonlinear optimum across steps.  The arguments are
+ * mpc_closed_loop_traced's, in its order, followed by `warm` (NULL: mpc_default_warm) and the warm outputs.  No
+ * version step: the entry is detected by the presence of the symbol.
+ * Per step and ego still in the loop, with xm the state and (slab, n_obs) the slab copy the solver is handed (after
+ * the noisy entry's measure step):
+ *   ref[k], k = 0 .. N-1   the reference warm start of (xm[0], xm[4], the slab positions, brake_distance,
+ *                brake_accel): the bits the solver computes for itself when ubar == NULL.
+ *   reset        the ego has no kept plan (its first step), the kept plan has a non-finite element, the kept status
+ *                (masked with MPC_STATUS_MASK: MPC_SQP_UNCONVERGED never resets) is MPC_NUMERICAL, or the condition
+ *                of a bit of warm->reset holds.  MPC_WARM_REFERENCE: always.
+ *   ubar[k]      ref[k] if reset; else clamp(Uprev[k+1]) for k < N-1, and for k == N-1 ref[N-1]
+ *                (MPC_WTAIL_REFERENCE) or clamp(Uprev[N-1]) (MPC_WTAIL_HOLD); clamp is per component to the context's
+ *                u_min / u_max.  ubar is the solver's linearisation point (with sqp_iters > 1: the first QP's).
+ *   after the solve the ego's U (exactly as returned), its status and this step's n_obs are kept, and
+ *                move_t = max over k, c of |U[k][c] - ubar[k][c]| (the sweep's NaN rule) enters warmq.
+ *   warmq        [B][MPC_WQ_NQ], optional: the MPC_WQ_* columns of every ego.
+ *   hist_ubar    [n_hist][max_steps][N][2], optional: the ubar the solver was handed.  NaN past n_steps.
+ * MPC_WARM_REFERENCE with warmq == hist_ubar == NULL: the call launches exactly the traced entry's kernels, ubar stays
+ * NULL, and every output equals mpc_closed_loop_traced's bit for bit.  MPC_WARM_REFERENCE with either output
+ * requested: ref is handed to the solver as an explicit ubar every step (MPC_WQ_N_RESET == n_steps), and every
+ * output the traced entry has still equals the traced entry's bit for bit.
+ * Misuse: the traced entry's cases, mode or tail outside their values, unknown bits in reset, hist_ubar with
+ * n_hist == 0, sqp_iters == 0 with MPC_WARM_CARRY: MPC_E_ARG.
+ * Device memory is the traced entry's plus, only when carrying or when a warm output is requested, O(B * N) for the
+ * kept plans, the packed ubar and the solver's U, and O(n_hist * max_steps * N) for hist_ubar. */
+#define MPC_WARM_REFERENCE 0      /* ubar = the reference warm start every step (the other entries' behaviour)    */
+#define MPC_WARM_CARRY 1          /* ubar = the ego's previous plan shifted by one stage                          */
+#define MPC_WTAIL_REFERENCE 0     /* last stage of a carried ubar: the reference warm start's stage N-1           */
+#define MPC_WTAIL_HOLD 1          /* ... : the kept plan's last control again                                     */
+#define MPC_WRESET_NOBS 1         /* optional reset: n_obs handed to the solver differs from the last step's      */
+#define MPC_WRESET_INFEASIBLE 2   /* optional reset: last masked status == MPC_INFEASIBLE                         */
+#define MPC_WRESET_MAX_ITER 4     /* optional reset: last masked status == MPC_MAX_ITER                           */
+typedef struct mpc_warm {
+    int mode, tail, reset;
+} mpc_warm;
+void mpc_default_warm(mpc_warm* w);             /* MPC_WARM_REFERENCE, MPC_WTAIL_REFERENCE, 0 */
+#define MPC_WQ_N_RESET 0          /* steps whose ubar was the reference warm start (the first step included)      */
+#define MPC_WQ_MAX_MOVE 1         /* max over steps of move_t (the sweep's NaN rule); NaN if the ego never ran    */
+#define MPC_WQ_STEP_MAX_MOVE 2    /* its step: the earliest on ties, the first NaN step if any; -1.0 if never ran */
+#define MPC_WQ_SUM_MOVE 3         /* running sum from 0 of move_t in step order                                   */
+#define MPC_WQ_NQ 4
+int mpc_closed_loop_warm(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                         const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
+                         unsigned long long seed, long long ego_offset, int max_steps, double s_stop, double* quant,
+                         double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u,
+                         double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                         int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
+                         const int* lookahead, int n_look, double* gapq, double* hist_pred, double* hist_plan,
+                         const mpc_warm* warm, double* warmq, double* hist_ubar);
 
 /* ---- Multi-GPU: ego shards, one gather ----------------------------------------------------
  * Every ego is independent; a batch splits into contiguous per-rank shards (one process per GPU) with no

@@ -1,5 +1,5 @@
-// closed_loop_host.h -- the host-side driver behind the six closed-loop entries of the C ABI (mpc_closed_loop,
-// _sweep, _traffic, _convoy, _noisy, _traced).  Included by mpcqp.hip below launch_solve: it uses that file's fail(), mpc_ctx
+// closed_loop_host.h -- the host-side driver behind the seven closed-loop entries of the C ABI (mpc_closed_loop,
+// _sweep, _traffic, _convoy, _noisy, _traced, _warm).  Included by mpcqp.hip below launch_solve: it uses that file's fail(), mpc_ctx
 // and launch_solve, and the state structs of the closed-loop kernel headers.
 //
 // An entry checks its arguments, declares its buffers and outputs on a ClDriver, launches its own init kernels and
@@ -259,10 +259,12 @@ struct ClDriver {
     // runs on the egos still in the loop: the list is rebuilt at the every-8-steps host sync whenever egos have
     // left, so retired egos stop costing solver work (results are per ego, unchanged).  timed: record the ring.
     // Ua [B][N][2], Xpa [B][N+1][5] (device, optional): the solver's U and Xpred of the listed egos, by list
-    // position, for the plant callable to use; u0 and the status do not depend on whether they are asked for
+    // position, for the plant callable to use; u0 and the status do not depend on whether they are asked for.
+    // ubara [B][N][2] (device, optional): the solver's linearisation point of the listed egos, by list position,
+    // which pre() has filled; without it the solver computes the reference warm start for itself
     template <typename Pre, typename Plant>
     int run(const KParams& kp, bool with_obs, bool timed, Pre pre, Plant plant, double* Ua = nullptr,
-            double* Xpa = nullptr) {
+            double* Xpa = nullptr, const double* ubara = nullptr) {
         if (timed) {
             for (auto& e : ev)
                 if (hipEventCreate(&e) != hipSuccess) {
@@ -278,7 +280,7 @@ struct ClDriver {
             for (int step = 0; step < max_steps && nl > 0; ++step) {
                 const dim3 lg((nl + 255) / 256);
                 pre(step, nl, lg);
-                rc = launch_solve(c, kp, nl, C.xa, with_obs ? C.obsa : nullptr, with_obs ? C.nobsa : nullptr, nullptr,
+                rc = launch_solve(c, kp, nl, C.xa, with_obs ? C.obsa : nullptr, with_obs ? C.nobsa : nullptr, ubara,
                                   C.u0a, Ua, Xpa, C.sta, nullptr, st);
                 if (rc) break;
                 if (hipMemsetAsync(C.n_active, 0, 4, st) != hipSuccess) {

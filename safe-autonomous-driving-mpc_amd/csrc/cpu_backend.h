@@ -1259,7 +1259,9 @@ struct Backend {
     // n_obs; one batched solve over the list (with the slab when with_obs, p.max_obs == ow); then
     // plant(step, b, u0, status) per listed ego.  The step times go to E.ms and the optional E.step_ms.
     // planned: the solver is also asked for its U and Xpred, and after the plant steps trace(step, b, U, Xpred)
-    // runs per listed ego
+    // runs per listed ego.  carried: before the solve carry(step, b, xs, obs, n_obs, ubar) fills the listed ego's
+    // row of the ubar [N][2] the solver is handed, the solver is asked for its U, and after the plant steps (and
+    // trace) keep(step, b, U, ubar, status, n_obs) runs per listed ego
     template <typename Rank, typename Sense, typename Plant>
     void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
                   Plant plant) const {
@@ -1268,8 +1270,15 @@ struct Backend {
     template <typename Rank, typename Sense, typename Plant, typename Trace>
     void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
                   Plant plant, bool planned, Trace trace) const {
+        run_loop(p, E, max_steps, with_obs, ow, rank, sense, plant, planned, trace, false,
+                 [](int, int, const double*, const double*, int, double*) {},
+                 [](int, int, const double*, const double*, int, int) {});
+    }
+    template <typename Rank, typename Sense, typename Plant, typename Trace, typename Carry, typename Keep>
+    void run_loop(const mpc_params& p, LoopEgos& E, int max_steps, bool with_obs, size_t ow, Rank rank, Sense sense,
+                  Plant plant, bool planned, Trace trace, bool carried, Carry carry, Keep keep) const {
         std::vector<int> alist, nobsa, sta;
-        std::vector<double> xa, obsa, u0a, Ua, Xpa;
+        std::vector<double> xa, obsa, u0a, Ua, Xpa, ubara;
         const size_t nu = 2 * (size_t)p.N, nxp = 5 * ((size_t)p.N + 1);
         for (int step = 0; step < max_steps; ++step) {
             const auto t0 = std::chrono::steady_clock::now();
@@ -1286,15 +1295,24 @@ struct Backend {
             sta.assign(nl, 0);
             for (int i = 0; i < nl; ++i)
                 nobsa[i] = sense(step, alist[i], xa.data() + 5 * (size_t)i, obsa.data() + (size_t)i * ow * 2);
-            if (planned) {
-                Ua.assign((size_t)nl * nu, 0.0);
-                Xpa.assign((size_t)nl * nxp, 0.0);
+            if (planned || carried) Ua.assign((size_t)nl * nu, 0.0);
+            if (planned) Xpa.assign((size_t)nl * nxp, 0.0);
+            if (carried) {
+                ubara.assign((size_t)nl * nu, 0.0);
+                for (int i = 0; i < nl; ++i)
+                    carry(step, alist[i], xa.data() + 5 * (size_t)i, obsa.data() + (size_t)i * ow * 2,
+                          with_obs ? nobsa[i] : 0, ubara.data() + (size_t)i * nu);
             }
-            solve_batch(p, nl, xa.data(), with_obs ? obsa.data() : nullptr, with_obs ? nobsa.data() : nullptr, nullptr,
-                        u0a.data(), planned ? Ua.data() : nullptr, planned ? Xpa.data() : nullptr, sta.data(), nullptr);
+            solve_batch(p, nl, xa.data(), with_obs ? obsa.data() : nullptr, with_obs ? nobsa.data() : nullptr,
+                        carried ? ubara.data() : nullptr, u0a.data(), planned || carried ? Ua.data() : nullptr,
+                        planned ? Xpa.data() : nullptr, sta.data(), nullptr);
             for (int i = 0; i < nl; ++i) plant(step, alist[i], u0a.data() + 2 * (size_t)i, sta[i]);
             if (planned)
                 for (int i = 0; i < nl; ++i) trace(step, alist[i], Ua.data() + (size_t)i * nu, Xpa.data() + (size_t)i * nxp);
+            if (carried)
+                for (int i = 0; i < nl; ++i)
+                    keep(step, alist[i], Ua.data() + (size_t)i * nu, ubara.data() + (size_t)i * nu, sta[i],
+                         with_obs ? nobsa[i] : 0);
             E.ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             if (E.step_ms) E.step_ms[step] = E.ms.back();
         }
@@ -1366,6 +1384,10 @@ struct Backend {
     //     plant step every ego stores stage j of its prediction in its ring for lookahead j and compares its new true
     //     state with the prediction made j - 1 steps before (loop_steps.h, trace_gap); gapq is
     //     [B][n_look][MPC_TG_NQ], hist_pred [n_hist][max_steps][N+1][5], hist_plan [n_hist][max_steps][N][2].
+    //   warm starts (warm != NULL): the solver is handed an explicit ubar, the reference warm start restated or the
+    //     ego's kept plan shifted by one stage (loop_steps.h, warm_reset and warm_source); after the plant step the
+    //     solver's U, its status and the step's n_obs are kept and the move from ubar enters warmq
+    //     [B][MPC_WQ_NQ]; hist_ubar is [n_hist][max_steps][N][2].
     // extra is [B][nx] (MPC_TR_NX; MPC_CV_NX with worlds; MPC_NZ_NX with noise); extra, n_steps, step_ms and every
     // history are optional; hist_slab is [n_hist][max_steps][A+K][2], hist_lead [n_hist][max_steps][K]
     int closed_loop_scripted(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
@@ -1375,7 +1397,8 @@ struct Backend {
                              double* hist_u, double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl,
                              int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
                              double* step_ms, const int* lookahead = nullptr, int n_look = 0, double* gapq = nullptr,
-                             double* hist_pred = nullptr, double* hist_plan = nullptr) const {
+                             double* hist_pred = nullptr, double* hist_plan = nullptr, const mpc_warm* warm = nullptr,
+                             double* warmq = nullptr, double* hist_ubar = nullptr) const {
         mpc_params p = p0;
         const int AK = A + K;
         p.max_obs = with_slab ? AK : 0;
@@ -1391,6 +1414,11 @@ struct Backend {
         const size_t nu = 2 * (size_t)p.N, nxp = 5 * ((size_t)p.N + 1);
         hist_prefill(hist_pred, nh * ns * nxp, (double)NAN);
         hist_prefill(hist_plan, nh * ns * nu, (double)NAN);
+        hist_prefill(hist_ubar, nh * ns * nu, (double)NAN);
+        // the kept plan [N][2], status (-1: none yet) and n_obs of every ego, and its warm row
+        std::vector<double> kplan(warm ? nb * nu : 0, 0.0), wq(warm ? nb * MPC_WQ_NQ : 0);
+        std::vector<int> kstatus(warm ? nb : 0, -1), knobs(warm ? nb : 0, 0);
+        for (size_t b = 0; warm && b < nb; ++b) warm_init(wq.data() + b * MPC_WQ_NQ);
         size_t slots = 0;                                 // ring slots of one ego, lookahead i's from ring0[i] on
         size_t ring0[MPC_MAX_LOOK] = {};
         for (int i = 0; i < n_look; ++i) {
@@ -1520,8 +1548,42 @@ struct Backend {
                      const size_t h = (size_t)slot[b] * ns + step;
                      if (hist_pred) std::memcpy(hist_pred + h * nxp, Xp, nxp * sizeof(double));
                      if (hist_plan) std::memcpy(hist_plan + h * nu, U, nu * sizeof(double));
+                 },
+                 warm != nullptr,
+                 [&](int step, int b, const double* xm, const double* oa, int nobs, double* ub) {
+                     const int N = p.N;
+                     const double* kp = kplan.data() + (size_t)b * nu;
+                     bool finite = true;
+                     if (kstatus[b] >= 0 && warm->mode == MPC_WARM_CARRY)
+                         for (size_t e = 0; e < nu; ++e) finite = finite && warm_finite(kp[e]);
+                     const bool reset = warm_reset(*warm, kstatus[b], finite, knobs[b], nobs);
+                     const bool walk = reset || warm->tail == MPC_WTAIL_REFERENCE;
+                     WarmRef w = warm_ref_begin(xm);
+                     for (int k = 0; k < N; ++k) {
+                         const int src = reset ? -1 : warm_source(k, N, warm->tail);
+                         if (walk) warm_ref_advance(w, k, p.dt, oa, nobs, p.brake_distance);
+                         if (src < 0) {
+                             warm_ref_control(w, p.brake_accel, [&](double s, double* ur) { ref->control(s, ur); },
+                                              ub[2 * k], ub[2 * k + 1]);
+                         } else {
+                             ub[2 * k] = clamp_control(kp[2 * src], p.u_min[0], p.u_max[0]);
+                             ub[2 * k + 1] = clamp_control(kp[2 * src + 1], p.u_min[1], p.u_max[1]);
+                         }
+                     }
+                     if (reset) wq[(size_t)b * MPC_WQ_NQ + MPC_WQ_N_RESET] += 1.0;
+                     if (hist_ubar && slot[b] >= 0)
+                         std::memcpy(hist_ubar + ((size_t)slot[b] * ns + step) * nu, ub, nu * sizeof(double));
+                 },
+                 [&](int step, int b, const double* U, const double* ub, int status, int nobs) {
+                     double move = 0.0;
+                     for (size_t e = 0; e < nu; ++e) warm_move_element(move, U[e], ub[e]);
+                     std::memcpy(kplan.data() + (size_t)b * nu, U, nu * sizeof(double));
+                     kstatus[b] = status;
+                     knobs[b] = nobs;
+                     warm_move(wq.data() + (size_t)b * MPC_WQ_NQ, step, move);
                  });
         E.finish(n_steps);
+        if (warmq) std::memcpy(warmq, wq.data(), nb * MPC_WQ_NQ * sizeof(double));
         if (extra) std::memcpy(extra, ex.data(), nb * nxs * sizeof(double));
         return MPC_SUCCESS;
     }
@@ -1576,6 +1638,22 @@ struct Backend {
                                     seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
                                     hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
                                     hist_lead, n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan);
+    }
+
+    // mpc_closed_loop_warm on the host: the traced loop whose solver is handed the warm start `warm` describes
+    int closed_loop_warm(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
+                         const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
+                         int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
+                         double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
+                         double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
+                         int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
+                         const int* lookahead, int n_look, double* gapq, double* hist_pred, double* hist_plan,
+                         const mpc_warm& warm, double* warmq, double* hist_ubar) const {
+        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
+                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
+                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
+                                    hist_lead, n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan, &warm,
+                                    warmq, hist_ubar);
     }
 };
 

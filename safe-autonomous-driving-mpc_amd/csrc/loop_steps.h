@@ -296,6 +296,9 @@ LOOP_STEP inline double noise_add(double x, double sigma, const NoiseAt& at, int
     return sigma != 0.0 ? x + (scale * sigma) * noise_z(at, channel) : x;
 }
 
+// the actuation clamp of one component
+LOOP_STEP inline double clamp_control(double t, double lo, double hi) { return t < lo ? lo : (t > hi ? hi : t); }
+
 // the applied control of one channel: the commanded u plus its draw, clamped to [lo, hi]; clamped is set if the
 // clamp changed it.  Sigma 0: u as it is, unclamped
 LOOP_STEP inline double apply_actuation(double u, double sigma, const NoiseAt& at, int channel, double lo, double hi,
@@ -303,5 +306,80 @@ LOOP_STEP inline double apply_actuation(double u, double sigma, const NoiseAt& a
     if (sigma == 0.0) return u;
     const double t = noise_add(u, sigma, at, channel);
     clamped = clamped || t < lo || t > hi;
-    return t < lo ? lo : (t > hi ? hi : t);
+    return clamp_control(t, lo, hi);
+}
+
+// ------------------------------------------------------------------------------------------
+// the warm starts of mpc_closed_loop_warm (include/mpcqp.h, MPC_WARM_*, MPC_WQ_*)
+// ------------------------------------------------------------------------------------------
+// The reference warm start (trajectory_tracking.py:224-246) one stage after the other, the arithmetic the solver
+// runs for itself without a ubar: s advances by repeated addition of v * dt, the brake flag is sticky once a slab
+// position is within brake_distance of s, the reference control is looked up at s.  The stages are walked in order
+// (warm_ref_advance) and the control is looked up at those that need it (warm_ref_control); ctl(s, ur) is the
+// caller's get_control on its own table
+struct WarmRef {
+    double s, v;
+    bool brake;
+};
+LOOP_STEP inline WarmRef warm_ref_begin(const double* xm) { return WarmRef{xm[0], xm[4], false}; }
+
+// stage k's s and brake flag from stage k - 1's (k = 0: from warm_ref_begin's)
+LOOP_STEP inline void warm_ref_advance(WarmRef& w, int k, double dt, const double* obs, int nobs,
+                                       double brake_distance) {
+    if (k > 0) w.s += w.v * dt;
+    for (int i = 0; i < nobs; ++i)
+        if ((obs[2 * i] - w.s) < brake_distance) w.brake = true;
+}
+
+// the warm start's control of the stage w stands at
+template <typename Ctl>
+LOOP_STEP inline void warm_ref_control(const WarmRef& w, double brake_accel, Ctl ctl, double& u1, double& u2) {
+    double ur[2];
+    ctl(w.s, ur);
+    u1 = ur[0];
+    u2 = w.brake ? brake_accel : ur[1];
+}
+
+// an element of a kept plan that may be carried
+LOOP_STEP inline bool warm_finite(double u) { return u - u == 0.0; }
+
+// Does this step start from the reference warm start?  kept_status: the status of the ego's last solve, -1 before
+// its first; plan_finite: every element of the kept plan is; kept_nobs / nobs: the n_obs the solver was handed at
+// the last step and is handed now
+LOOP_STEP inline bool warm_reset(const mpc_warm& w, int kept_status, bool plan_finite, int kept_nobs, int nobs) {
+    if (w.mode != MPC_WARM_CARRY || kept_status < 0 || !plan_finite) return true;
+    const int code = kept_status & MPC_STATUS_MASK;
+    if (code == MPC_NUMERICAL) return true;
+    if ((w.reset & MPC_WRESET_NOBS) && nobs != kept_nobs) return true;
+    if ((w.reset & MPC_WRESET_INFEASIBLE) && code == MPC_INFEASIBLE) return true;
+    return (w.reset & MPC_WRESET_MAX_ITER) && code == MPC_MAX_ITER;
+}
+
+// the stage of the kept plan that stage k of a carried ubar takes (clamped), -1: the reference warm start's stage k
+LOOP_STEP inline int warm_source(int k, int N, int tail) {
+    return k < N - 1 ? k + 1 : (tail == MPC_WTAIL_HOLD ? N - 1 : -1);
+}
+
+// the row of an ego before its first step, which one that never runs keeps
+template <typename Q>
+LOOP_STEP inline void warm_init(Q w) {
+    w[MPC_WQ_N_RESET] = 0.0;
+    w[MPC_WQ_MAX_MOVE] = NAN;
+    w[MPC_WQ_STEP_MAX_MOVE] = -1.0;
+    w[MPC_WQ_SUM_MOVE] = 0.0;
+}
+
+// move <- max(move, |u - ub|) over the elements of a plan, from 0.0: a NaN enters and stays
+LOOP_STEP inline void warm_move_element(double& move, double u, double ub) { keep_max(move, fabs(u - ub)); }
+
+// Step `step` moved the plan by `move` from its ubar.  Step 0, which every ego that runs at all runs, seeds the
+// maximum; its step moves only when the maximum grows or turns NaN (trace_gap's rule for MAX_DD)
+template <typename Q>
+LOOP_STEP inline void warm_move(Q w, int step, double move) {
+    const double m = w[MPC_WQ_MAX_MOVE];
+    if (step == 0 || move > m || (move != move && m == m)) {
+        w[MPC_WQ_MAX_MOVE] = move;
+        w[MPC_WQ_STEP_MAX_MOVE] = (double)step;
+    }
+    w[MPC_WQ_SUM_MOVE] = w[MPC_WQ_SUM_MOVE] + move;
 }

@@ -26,6 +26,7 @@
 //   convoy_kernels.h       the convoys' leader-ranking kernel (a workgroup per world)
 //   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
 //   trace_kernels.h        the plan traces' gap and history kernels (the solver's U / Xpred of every step)
+//   warm_kernels.h         the warm starts' carry and keep kernels (the previous plan as the next ubar)
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points; the driver the closed-loop entries share is closed_loop_host.h) and, last, the comm
@@ -52,6 +53,7 @@
 #include "convoy_kernels.h"
 #include "noise_kernels.h"
 #include "trace_kernels.h"
+#include "warm_kernels.h"
 #include "evaluate_kernel.h"
 
 // ------------------------------------------------------------------------------------------
@@ -803,9 +805,16 @@ extern "C" void mpc_actors_from_fsm(const mpc_fsm* f, mpc_actor out[2]) {
 
 extern "C" void mpc_default_noise(mpc_noise* n) { std::memset(n, 0, sizeof(*n)); }
 
-// What the four scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
-// worlds, K == 0), mpc_closed_loop_convoy, mpc_closed_loop_noisy (noisy; noise is then never NULL) and
-// mpc_closed_loop_traced (noisy, with the trace outputs at the end; the other three leave them empty)
+extern "C" void mpc_default_warm(mpc_warm* w) {
+    w->mode = MPC_WARM_REFERENCE;
+    w->tail = MPC_WTAIL_REFERENCE;
+    w->reset = 0;
+}
+
+// What the five scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
+// worlds, K == 0), mpc_closed_loop_convoy, mpc_closed_loop_noisy (noisy; noise is then never NULL),
+// mpc_closed_loop_traced (noisy, with the trace outputs; the first three leave them empty) and mpc_closed_loop_warm
+// (traced, with `warm` set when the solver is to be handed a ubar; the other four leave it and its outputs empty)
 struct ScriptedLoop {
     const char* label;
     int B, W, K;
@@ -833,6 +842,8 @@ struct ScriptedLoop {
     const int* lookahead;
     int n_look;
     double *gapq, *hist_pred, *hist_plan;
+    const mpc_warm* warm;
+    double *warmq, *hist_ubar;
 };
 
 // The loop of the scripted entries around tr_fsm_kernel and an (A + K)-wide slab.  With worlds, cv_lead_kernel
@@ -840,7 +851,8 @@ struct ScriptedLoop {
 // wide).  Noisy: nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel, on the field-major
 // sigma table [14][B] for per-ego noise; the other kernels are reused untouched and see the true states.  Traced
 // (any trace output asked for): the solver also writes its U and Xpred of the listed egos, and tg_gap_kernel and
-// tg_hist_kernel follow the plant kernel
+// tg_hist_kernel follow the plant kernel.  Warm (a.warm set): ws_carry_kernel fills the solver's ubar after the
+// measure kernel, the solver is asked for its U, and ws_keep_kernel follows the plant kernel
 static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     const int B = a.B, A = a.A, K = a.K, AK = A + K, max_steps = a.max_steps;
     std::vector<int> slot;
@@ -857,6 +869,13 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     if (c->cpu)
         return host_loop([&] {
             const int hsc = nsc == 0 ? 1 : nsc;
+            if (a.warm)
+                return c->cpu->closed_loop_warm(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
+                                                a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
+                                                a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
+                                                a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
+                                                a.hist_slab, a.hist_lead, a.n_steps, a.step_ms, a.lookahead, a.n_look,
+                                                a.gapq, a.hist_pred, a.hist_plan, *a.warm, a.warmq, a.hist_ubar);
             if (traced)
                 return c->cpu->closed_loop_traced(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
                                                   a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
@@ -951,6 +970,34 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
         G.hist_pred = D.out(a.hist_pred, nhs * (nN + 1) * 5);
         G.hist_plan = D.out(a.hist_plan, nhs * nN * 2);
     }
+    WsState Ws = {};
+    std::vector<double> hwq;                // the warm rows as the device keeps them, [MPC_WQ_NQ][B]
+    if (a.warm) {
+        const size_t nN = (size_t)c->p.N;
+        try {
+            hwq.resize(a.warmq ? MPC_WQ_NQ * D.nb : 0);
+        } catch (const std::bad_alloc&) {
+            return fail(MPC_E_ALLOC, "warm table");
+        }
+        if (!d_U) d_U = D.mem.alloc<double>(D.nb * nN * 2);
+        Ws.warm = *a.warm;
+        Ws.N = c->p.N;
+        Ws.max_obs = kp.max_obs;
+        Ws.dt = kp.dt;
+        Ws.brake_distance = kp.brake_distance;
+        Ws.brake_accel = kp.brake_accel;
+        Ws.u_min0 = kp.u_min0;
+        Ws.u_min1 = kp.u_min1;
+        Ws.u_max0 = kp.u_max0;
+        Ws.u_max1 = kp.u_max1;
+        Ws.ubara = D.mem.alloc<double>(D.nb * nN * 2);
+        Ws.Ua = d_U;
+        Ws.plan = D.mem.alloc<double>(D.nb * nN * 2);
+        Ws.status = D.mem.alloc<int>(D.nb);
+        Ws.nobs = D.mem.alloc<int>(D.nb);
+        Ws.wq = a.warmq ? D.out(hwq.data(), hwq.size(), false) : D.mem.alloc<double>(MPC_WQ_NQ * D.nb);
+        Ws.hist_ubar = D.out(a.hist_ubar, nhs * nN * 2);
+    }
     rc = D.begin();
     if (rc) return rc;
     const dim3 tb = D.tb, tg = D.tg;
@@ -959,12 +1006,14 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     if (a.W) hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
     if (a.noisy) hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
     if (G.n_look) hipLaunchKernelGGL(tg_init_kernel, tg, tb, 0, st, B, G);
+    if (a.warm) hipLaunchKernelGGL(ws_init_kernel, tg, tb, 0, st, B, Ws);
     rc = D.run(kp, a.with_slab, true,
                [&](int step, int nl, dim3 lg) {
                    hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
                    if (a.W) hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
                    if (a.noisy) hipLaunchKernelGGL(nz_measure_kernel, lg, tb, 0, st, nl, B, AK, C, S, T, Z, step, max_steps);
                    else hipLaunchKernelGGL(tr_gather_kernel, lg, tb, 0, st, nl, B, AK, C, T);
+                   if (a.warm) hipLaunchKernelGGL(ws_carry_kernel, lg, tb, 0, st, c->tab, nl, B, C, S, Ws, step, max_steps);
                },
                [&](int step, int nl, dim3 lg) {
                    if (a.noisy)
@@ -979,12 +1028,16 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
                        hipLaunchKernelGGL(tg_hist_kernel, dim3((unsigned)((ne + 255) / 256)), tb, 0, st, nl, C, S, G, step,
                                           max_steps);
                    }
+                   if (a.warm) hipLaunchKernelGGL(ws_keep_kernel, lg, tb, 0, st, nl, B, C, S, Ws, step);
                },
-               d_U, d_Xp);
+               d_U, d_Xp, Ws.ubara);
     if (rc == MPC_SUCCESS) rc = D.finish(S, T.ex, a.nx, a.quant, a.extra, a.n_steps, a.step_ms);
     if (rc == MPC_SUCCESS)                  // field-major on the device, one row per ego and lookahead outside
         for (size_t b = 0; b < D.nb; ++b)
             for (size_t k = 0; k < (size_t)a.n_look * MPC_TG_NQ; ++k) a.gapq[b * a.n_look * MPC_TG_NQ + k] = hgap[k * D.nb + b];
+    if (rc == MPC_SUCCESS && a.warmq)
+        for (size_t b = 0; b < D.nb; ++b)
+            for (size_t k = 0; k < MPC_WQ_NQ; ++k) a.warmq[b * MPC_WQ_NQ + k] = hwq[k * D.nb + b];
     return rc;
 }
 
@@ -1043,7 +1096,8 @@ static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, doubl
                        double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u, double* hist_ua,
                        double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
                        double* hist_slab, int* hist_lead, int* n_steps, double* step_ms, const int* lookahead,
-                       int n_look, double* gapq, double* hist_pred, double* hist_plan) {
+                       int n_look, double* gapq, double* hist_pred, double* hist_plan, const mpc_warm* warm = nullptr,
+                       double* warmq = nullptr, double* hist_ubar = nullptr) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
     int rc = cl_check_world(B, W, K, A, lead_range);
@@ -1055,8 +1109,22 @@ static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, doubl
         return fail(MPC_E_ARG, "n_noise must be B (a struct per ego), 1 (shared) or 0 with noise NULL");
     if (ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
     rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status ||
-                                             hist_nobs || hist_slab || hist_lead || hist_pred || hist_plan);
+                                             hist_nobs || hist_slab || hist_lead || hist_pred || hist_plan ||
+                                             hist_ubar);
     if (rc) return rc;
+    mpc_warm wdef;
+    mpc_default_warm(&wdef);
+    if (!warm) warm = &wdef;
+    if (warm->mode != MPC_WARM_REFERENCE && warm->mode != MPC_WARM_CARRY)
+        return fail(MPC_E_ARG, "warm.mode is neither MPC_WARM_REFERENCE nor MPC_WARM_CARRY");
+    if (warm->tail != MPC_WTAIL_REFERENCE && warm->tail != MPC_WTAIL_HOLD)
+        return fail(MPC_E_ARG, "warm.tail is neither MPC_WTAIL_REFERENCE nor MPC_WTAIL_HOLD");
+    if (warm->reset & ~(MPC_WRESET_NOBS | MPC_WRESET_INFEASIBLE | MPC_WRESET_MAX_ITER))
+        return fail(MPC_E_ARG, "warm.reset has unknown bits");
+    if (warm->mode == MPC_WARM_CARRY && c->p.sqp_iters == 0)
+        return fail(MPC_E_ARG, "MPC_WARM_CARRY needs sqp_iters >= 1 (sqp_iters == 0 returns ubar itself)");
+    // the reference warm start with no warm output: the solver computes it for itself, the traced entry's kernels
+    const bool warm_on = warm->mode == MPC_WARM_CARRY || warmq || hist_ubar;
     if (n_look < 0 || n_look > MPC_MAX_LOOK) return fail(MPC_E_ARG, "n_look out of range [0, 4]");
     if (n_look > 0 && !lookahead) return fail(MPC_E_ARG, "lookahead is NULL but n_look > 0");
     if (n_look > 0 ? !gapq : gapq != nullptr)
@@ -1077,7 +1145,8 @@ static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, doubl
     const ScriptedLoop a = {label, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, true, noise, n_noise,
                             seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, hist_egos, hist_x,
                             hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead,
-                            n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan};
+                            n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan, warm_on ? warm : nullptr,
+                            warmq, hist_ubar};
     return scripted_loop(c, a);
 }
 
@@ -1107,6 +1176,21 @@ extern "C" int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double le
                        ego_offset, max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm,
                        hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, lookahead,
                        n_look, gapq, hist_pred, hist_plan);
+}
+
+// mpc_closed_loop_traced whose solver may be handed the ego's previous plan as its ubar (include/mpcqp.h)
+extern "C" int mpc_closed_loop_warm(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
+                                    const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
+                                    unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
+                                    double* quant, double* extra, int n_hist, const int* hist_egos, double* hist_x,
+                                    double* hist_u, double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl,
+                                    int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
+                                    double* step_ms, const int* lookahead, int n_look, double* gapq, double* hist_pred,
+                                    double* hist_plan, const mpc_warm* warm, double* warmq, double* hist_ubar) {
+    return noisy_entry("warm-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed, ego_offset,
+                       max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
+                       hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, lookahead, n_look, gapq,
+                       hist_pred, hist_plan, warm, warmq, hist_ubar);
 }
 
 // the draws of mpc_closed_loop_noisy on their own (include/mpcqp.h), on the context's backend

@@ -59,6 +59,11 @@ class MpcNoise(C.Structure):
                 ("perc_sigma", C.c_double * 2)]
 
 
+class MpcWarm(C.Structure):
+    """`mpc_warm` of include/mpcqp.h: how mpc_closed_loop_warm picks each step's linearisation point."""
+    _fields_ = [("mode", C.c_int), ("tail", C.c_int), ("reset", C.c_int)]
+
+
 class MpcError(RuntimeError):
     pass
 
@@ -67,7 +72,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_closed_loop_traced", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -98,6 +103,14 @@ MAX_LOOK = 4
 TG_N_CMP, TG_MAX_DS, TG_MAX_DD, TG_MAX_DV, TG_STEP_DD = 0, 1, 2, 3, 4
 TG_NQ = 5
 TG_FIELDS = ("n_cmp", "max_ds", "max_dd", "max_dv", "step_dd")
+# mpc_closed_loop_warm: the modes, tails and reset bits of MpcWarm (MPC_WARM_*, MPC_WTAIL_*, MPC_WRESET_*) and the
+# columns of a warmq row (MPC_WQ_*)
+WARM_REFERENCE, WARM_CARRY = 0, 1
+WTAIL_REFERENCE, WTAIL_HOLD = 0, 1
+WRESET_NOBS, WRESET_INFEASIBLE, WRESET_MAX_ITER = 1, 2, 4
+WQ_N_RESET, WQ_MAX_MOVE, WQ_STEP_MAX_MOVE, WQ_SUM_MOVE = 0, 1, 2, 3
+WQ_NQ = 4
+WQ_FIELDS = ("n_reset", "max_move", "step_max_move", "sum_move")
 # mpc_evaluate_batch: the columns of its per-instance summary (MPC_EVQ_*)
 EVQ_COST, EVQ_MIN_ROW, EVQ_ARGMIN_STAGE, EVQ_ARGMIN_KIND, EVQ_L1, EVQ_N_NEG = 0, 1, 2, 3, 4, 5
 EVQ_MIN_LANE, EVQ_MIN_OBS, EVQ_MIN_V, EVQ_BOX = 6, 7, 8, 9
@@ -170,6 +183,11 @@ def lib():
                                         _ip, _ip, _dp, _ip, _ip, _dp]
     L.mpc_closed_loop_traced.restype = C.c_int
     L.mpc_closed_loop_traced.argtypes = L.mpc_closed_loop_noisy.argtypes + [_ip, C.c_int, _dp, _dp, _dp]
+    if hasattr(L, "mpc_closed_loop_warm"):          # no version step: the entry is detected by its symbol
+        L.mpc_default_warm.restype = None
+        L.mpc_default_warm.argtypes = [C.POINTER(MpcWarm)]
+        L.mpc_closed_loop_warm.restype = C.c_int
+        L.mpc_closed_loop_warm.argtypes = L.mpc_closed_loop_traced.argtypes + [C.POINTER(MpcWarm), _dp, _dp]
     L.mpc_noise_draw.restype = C.c_int
     L.mpc_noise_draw.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.POINTER(C.c_longlong), _ip, _ip,
                                  C.POINTER(C.c_uint), _dp]
@@ -227,6 +245,16 @@ def default_noise(**kw):
         for i, x in enumerate(vals):
             arr[i] = float(x)
     return n
+
+
+def default_warm(**kw):
+    """mpc_default_warm (WARM_REFERENCE, WTAIL_REFERENCE, no optional reset) with the given fields set: mode, tail,
+    reset (an OR of WRESET_* bits)."""
+    w = MpcWarm()
+    lib().mpc_default_warm(C.byref(w))
+    for k, v in kw.items():
+        setattr(w, k, int(v))
+    return w
 
 
 def car(trigger_s, start_s, v, end_s):
@@ -541,9 +569,21 @@ class Solver:
         return self._closed_loop_noisy(x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise,
                                        seed, lo, (lookahead, preds, plans))
 
+    def closed_loop_warm(self, x_init, W=1, K=0, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
+                         s_max=None, hist_egos=(), noise=None, seed=0, lo=0, lookahead=(), preds=False, plans=False,
+                         warm=None, warmq=False, ubars=False):
+        """mpc_closed_loop_warm: closed_loop_traced whose steps may linearise about the ego's previous plan shifted by
+        one stage (the real-time iteration).  warm: an MpcWarm (default_warm(mode=WARM_CARRY, ...)), None for the
+        defaults (the reference warm start every step: closed_loop_traced).
+        Returns closed_loop_traced's dict, plus warmq [B,4] (columns WQ_FIELDS) with warmq=True and hist_ubar
+        [n_hist,max_steps,N,2] (the linearisation point the solver was handed; NaN past n_steps) with ubars=True."""
+        return self._closed_loop_noisy(x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise,
+                                       seed, lo, (lookahead, preds, plans), (warm, warmq, ubars))
+
     def _closed_loop_noisy(self, x_init, W, K, lead_range, scripts, max_steps, s_stop, s_max, hist_egos, noise, seed,
-                           lo, trace):
-        """closed_loop_noisy (trace None) or closed_loop_traced (trace = (lookahead, preds, plans))."""
+                           lo, trace, warm=None):
+        """closed_loop_noisy (trace None), closed_loop_traced (trace = (lookahead, preds, plans)) or closed_loop_warm
+        (warm = (MpcWarm or None, warmq, ubars) as well)."""
         x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
         B = x_init.shape[0]
         if s_stop is None:
@@ -593,9 +633,18 @@ class Solver:
                 more["hist_pred"] = np.empty((nh, max_steps, N + 1, 5))
             if plans:
                 more["hist_plan"] = np.empty((nh, max_steps, N, 2))
-            _check(lib().mpc_closed_loop_traced(*args, _pi(look) if look.size else None, int(look.size),
-                                                _p(more.get("gapq")), g(more.get("hist_pred")),
-                                                g(more.get("hist_plan"))), "mpc_closed_loop_traced")
+            targs = args + (_pi(look) if look.size else None, int(look.size), _p(more.get("gapq")),
+                            g(more.get("hist_pred")), g(more.get("hist_plan")))
+            if warm is None:
+                _check(lib().mpc_closed_loop_traced(*targs), "mpc_closed_loop_traced")
+            else:
+                how, want_q, want_ubar = warm
+                if want_q:
+                    more["warmq"] = np.empty((B, WQ_NQ))
+                if want_ubar:
+                    more["hist_ubar"] = np.empty((nh, max_steps, N, 2))
+                _check(lib().mpc_closed_loop_warm(*targs, None if how is None else C.byref(how), _p(more.get("warmq")),
+                                                  g(more.get("hist_ubar"))), "mpc_closed_loop_warm")
         quant[:, 0] += lo
         extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
         return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,

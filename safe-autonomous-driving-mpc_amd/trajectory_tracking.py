@@ -617,6 +617,19 @@ def run_simulation_traced(mpc, fsms, trajectory, hist_egos=None, max_steps=2000,
     car), hist_tl_state a list of 'RED' / 'GREEN', hist_t the step times of the whole batch in seconds.  The tuple
     feeds driving_animation and plot_tracking_results as run_simulation's does.  Prints nothing and runs no
     sanity check."""
+    return _run_simulation_batched(mpc, fsms, trajectory, hist_egos, max_steps, x_init, None)
+
+
+def run_simulation_carried(mpc, fsms, trajectory, hist_egos=None, max_steps=2000, x_init=None, tail=None, reset=0):
+    """run_simulation_traced with the carried loop (mpc_closed_loop_warm, WARM_CARRY): every step's QP is linearised
+    about the ego's previous plan shifted by one stage instead of the reference warm start.  tail: mpcqp.WTAIL_*
+    (default WTAIL_REFERENCE); reset: an OR of mpcqp.WRESET_* bits.  The same return values per named ego."""
+    warm = mpcqp.default_warm(mode=mpcqp.WARM_CARRY, tail=mpcqp.WTAIL_REFERENCE if tail is None else tail, reset=reset)
+    return _run_simulation_batched(mpc, fsms, trajectory, hist_egos, max_steps, x_init, warm)
+
+
+def _run_simulation_batched(mpc, fsms, trajectory, hist_egos, max_steps, x_init, warm):
+    """run_simulation_traced (warm None) or run_simulation_carried (warm: the MpcWarm of the loop)."""
     fsms = list(fsms)
     B = len(fsms)
     if x_init is None:
@@ -626,8 +639,9 @@ def run_simulation_traced(mpc, fsms, trajectory, hist_egos=None, max_steps=2000,
         raise ValueError("one start state per scenario")
     hist_egos = list(range(B)) if hist_egos is None else [int(e) for e in hist_egos]
     scripts = [TrafficScript.from_fsm(f).actors for f in fsms]
-    r = mpc.solver(max_obs=0).closed_loop_traced(x_init, scripts=scripts, max_steps=max_steps, s_max=trajectory.s_max,
-                                                 hist_egos=hist_egos, preds=True)
+    kw = dict(scripts=scripts, max_steps=max_steps, s_max=trajectory.s_max, hist_egos=hist_egos, preds=True)
+    slv = mpc.solver(max_obs=0)
+    r = slv.closed_loop_traced(x_init, **kw) if warm is None else slv.closed_loop_warm(x_init, warm=warm, **kw)
     out = []
     for k, b in enumerate(hist_egos):
         n = int(r["n_steps"][b])
