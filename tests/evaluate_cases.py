@@ -15,9 +15,9 @@ _solvers = {}
 
 
 def solver(env, traj, N, mo, device=None, **kw):
-    """A cached context per (device, trajectory, N, max_obs, solver knobs)."""
+    """A cached context per (device, trajectory, N, max_obs, mpc_params fields given in kw)."""
     device = env["device"] if device is None else device
-    key = (device, traj, N, mo, tuple(sorted(kw.items())))
+    key = (device, traj, N, mo, tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items())))
     if key not in _solvers:
         mpcqp = env["mpcqp"]
         _solvers[key] = mpcqp.Solver(*traj_arrays(traj), mpcqp.default_params(N=N, max_obs=mo, **kw), device=device)
@@ -42,23 +42,27 @@ def reference_vector(rows, n_obs):
 # ---------------------------------------------------------------------------------------------
 # 1. reference pin
 # ---------------------------------------------------------------------------------------------
-def golden_groups():
-    """The 60 model_golden cases batched per (trajectory, N, obstacle count)."""
-    cases, _ = golden_cases("model_golden")
-    assert len(cases) == 60
+def golden_groups(cases=None):
+    """The 60 model_golden cases (or the given `cases` in model_golden's record format) batched per
+    (trajectory, N, obstacle count)."""
+    if cases is None:
+        cases, _ = golden_cases("model_golden")
+        assert len(cases) == 60
     groups = {}
     for c in cases:
         groups.setdefault((int(c["traj"]), int(c["N"]), int(c["obs"].shape[0])), []).append(c)
     return groups
 
 
-def evaluate_golden(env):
-    """[(key, cases, result)] of the golden groups on env's device, computed once per device."""
+def evaluate_golden(env, cases=None, tag=None, **kw):
+    """[(key, cases, result)] of the golden groups on env's device, computed once per device; with `cases`, of those
+    records under the mpc_params fields kw (cached per device and `tag`)."""
     cache = env.setdefault("_golden", {})
-    if env["device"] not in cache:
+    ckey = env["device"] if cases is None else (env["device"], tag)
+    if ckey not in cache:
         out = []
-        for (ti, N, no), cs in sorted(golden_groups().items()):
-            slv = solver(env, ti, N, no)
+        for (ti, N, no), cs in sorted(golden_groups(cases).items()):
+            slv = solver(env, ti, N, no, **kw)
             x0 = np.array([c["x0"] for c in cs])
             U = np.array([c["U"].reshape(N, 2) for c in cs])
             obs = np.array([c["obs"] for c in cs]).reshape(len(cs), no, 2) if no else None
@@ -66,18 +70,18 @@ def evaluate_golden(env):
             for v in r.values():
                 v.setflags(write=False)
             out.append(((ti, N, no), cs, r))
-        cache[env["device"]] = out
-    return cache[env["device"]]
+        cache[ckey] = out
+    return cache[ckey]
 
 
-def check_reference_pin(env):
+def check_reference_pin(env, cases=None, tag=None, **kw):
     """Xpred, the cost and the rows are bit-equal to the reference's own predict / cost / constraints on all 60
-    cases, with the golden's exact row shape.  (The issue's bounds, 1e-12 (1 + |cost|) and 1e-12 per row, the ones
+    cases (or on all the given `cases`, recorded under the mpc_params fields kw), with the golden's exact row shape.  (The issue's bounds, 1e-12 (1 + |cost|) and 1e-12 per row, the ones
     tests/test_oracle_golden.py:41-44 holds the C oracle to, turned out to hold with no error at all on both
     backends, so equality is asserted.)"""
     TT = env["TT"]
     n = 0
-    for (ti, N, no), cs, r in evaluate_golden(env):
+    for (ti, N, no), cs, r in evaluate_golden(env, cases, tag, **kw):
         assert r["rows"].shape == (len(cs), N, 7 + no)
         for b, c in enumerate(cs):
             assert np.array_equal(r["Xpred"][b], c["X"]), (ti, N, no, b)
@@ -87,7 +91,7 @@ def check_reference_pin(env):
             assert same(g, reference_vector(r["rows"][b], no))
             assert np.array_equal(g, c["cons"]), (ti, N, no, b, float(np.abs(g - c["cons"]).max()))
             n += 1
-    assert n == 60
+    assert n == (60 if cases is None else len(cases))
 
 
 # ---------------------------------------------------------------------------------------------

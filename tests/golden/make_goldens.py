@@ -15,6 +15,8 @@ What it pins:
               polish (independent of the build's PDIP), hard and elastic (L1) variants.
   solve       reference solve() outputs (behavioural check)  trajectory_tracking.py:213-263
   closedloop  run_simulation histories                       trajectory_tracking.py:377-443
+  params      the qp, model and warmstart records under six non-default parameter sets (--only params;
+              params_golden.npz, not part of the default run and touching no other fixture)
 
 The trajectories are also converted (data only) to ../../safe-autonomous-driving-mpc_amd/data.
 
@@ -904,6 +906,145 @@ def gen_closedloop():
     save("closedloop_golden", **out)
 
 
+# ----------------------------------------------------------------------------------------
+# 7. the tracker away from its default parameters (params_golden.npz)
+# ----------------------------------------------------------------------------------------
+# name -> TrajectoryTracker attributes (== mpc_params fields) that differ from the reference's defaults.
+# A and B move everything at once, in opposite directions.  W, U, G and T move one group each (weights, control
+# bounds, lane / vehicle / obstacle geometry, dt), so a failure under one of them names its group.  Every set
+# keeps lane_width / 2 - vehicle_radius - safe_lane_margin > 0 and bounds that bracket 0.  The lane half-widths
+# (A 0.37, B 0.33, G 0.35; default 0.4) keep elastic instances in the 203-ego batches of tests/test_gpu_params.py.
+# cond(H) grows like (N dt)^4 w_d / w_u1: B's dt and w_u1 hold it at N = 40 to about 4 times the default problem's
+# (max over those batches 9e9 against 1.8e9), what the default problem has near N = 55; with dt = 0.3 and
+# w_u1 = 0.2 it was 2e11, a hundred times the conditioning the parity constants were measured at.
+PARAM_SETS = {
+    "A": dict(dt=0.15, w_d=3.0, w_o=25.0, w_v=0.4, w_u1=2.0, w_u2=0.05, u_min=[-0.35, -3.0], u_max=[0.45, 2.5],
+              vehicle_radius=0.8, lane_width=2.84, safe_lane_margin=0.25, wheelbase=3.4,
+              obstacle_safety_distance=8.0, max_time_2_obs=2.2),
+    "B": dict(dt=0.24, w_d=40.0, w_o=2.0, w_v=5.0, w_u1=1.5, w_u2=4.0, u_min=[-0.9, -6.0], u_max=[0.7, 5.0],
+              vehicle_radius=1.1, lane_width=2.96, safe_lane_margin=0.05, wheelbase=2.2,
+              obstacle_safety_distance=3.0, max_time_2_obs=0.9),
+    "W": dict(w_d=4.0, w_o=30.0, w_v=1.5, w_u1=3.0, w_u2=0.1),
+    "U": dict(u_min=[-0.3, -3.5], u_max=[0.5, 2.0]),
+    "G": dict(vehicle_radius=0.9, lane_width=3.1, safe_lane_margin=0.3, wheelbase=3.6,
+              obstacle_safety_distance=7.0, max_time_2_obs=2.0),
+    "T": dict(dt=0.25),
+}
+PARAMS_N = (10, 15, 20, 25, 30, 40)
+PARAMS_KINDS = (0, "fsm", 8)
+PARAMS_TRAJ = {0: 1, "fsm": 2, 8: 3}        # the trajectory each obstacle kind is drawn on, as in C2 / C3 / C5
+
+
+def param_tracker(ti, N, pset):
+    tr = tracker(ti, N)
+    for k, v in pset.items():
+        setattr(tr, k, np.array(v, np.float64) if k in ("u_min", "u_max") else float(v))
+    assert tr.lane_width / 2.0 - tr.vehicle_radius - tr.safe_lane_margin > 0.0
+    assert (tr.u_min < 0.0).all() and (tr.u_max > 0.0).all()
+    return tr
+
+
+def _obs_array(obs):
+    return np.array([[o["s"], o["v"]] for o in obs]).reshape(-1, 2)
+
+
+def params_qp_plan(name):
+    """[(N, obstacle kind, special)]: A and B take every (N, kind) pair plus gen_qp's two special draws (the
+    horizon past s_max, d pushed over the lane margin); the one-group sets take one kind per horizon, rotating, so
+    each of them still runs every horizon and every kind."""
+    if name in ("A", "B"):
+        plan = [(N, k, None) for N in PARAMS_N for k in PARAMS_KINDS]
+        return plan + [(20, 0, "past_s_max"), (25, "fsm", "over_margin"), (40, 8, "past_s_max"), (15, 0, "over_margin")]
+    rot = "WUGT".index(name)
+    return [(N, PARAMS_KINDS[(i + rot) % 3], None) for i, N in enumerate(PARAMS_N)]
+
+
+def gen_params_qp(name, pset, rng):
+    cases = []
+    for (N, kind, special) in params_qp_plan(name):
+        ti = PARAMS_TRAJ[kind]
+        ld = loader(ti)
+        tr = param_tracker(ti, N, pset)
+        sl = tr.lane_width / 2.0 - tr.vehicle_radius - tr.safe_lane_margin
+        for attempt in range(8):                 # a draw whose elastic QP misses the KKT certificate is drawn again:
+            x0 = draw_x0(ld, rng)                # every stored case is certified (ok_elastic)
+            if special == "past_s_max":
+                x0[0] = ld.s_max - rng.uniform(0.5, 5.0)
+            if special == "over_margin":
+                x0[1] += 0.75 * sl               # gen_qp's + 0.3 at the default half-width 0.4
+            obs = draw_obstacles(kind, x0, rng)
+            ubar = capture_warmstart(tr, x0, obs)
+            qp = build_qp(tr, ld, x0, obs, ubar)
+            xe, le, oke, kkte, _ = solve_qp_tight(qp, RHO_DEFAULT, hard=False)
+            if oke:
+                break
+            print(f"  params {name} N={N} kind={kind}: draw {attempt} not certified ({kkte}), drawn again", flush=True)
+        assert oke, (name, N, kind, special, kkte)
+        chk = fd_checks(tr, x0, obs, ubar, qp)
+        assert np.array_equal(qp["Xbar"], tr.predict(x0, ubar))
+        feasible = False
+        if kkte.get("nV", 1) == 0:
+            xh, lh, okh, _, _ = solve_qp_tight(qp, RHO_DEFAULT, hard=True)
+            feasible = bool(okh)
+            if feasible:
+                assert np.abs(xh - xe).max() < 1e-7 or lh.max() >= RHO_DEFAULT, (np.abs(xh - xe).max(), lh.max())
+        cases.append(dict(traj=ti, N=N, x0=x0, obs=_obs_array(obs), ubar=ubar, U_elastic=ubar + xe,
+                          ok_elastic=oke, feasible=feasible, fdcheck=json.dumps(chk)))
+        print(f"  params {name} qp {len(cases)} traj{ti} N={N} obs={len(obs)} {special or ''} feasible={feasible} "
+              f"nV={kkte.get('nV')} condH={np.linalg.cond(qp['H']):.2e} chk={chk}", flush=True)
+    return cases
+
+
+def gen_params_model(name, pset, rng):
+    cases = []
+    for (ti, N, kind) in [(1, 10, 0), (2, 20, "fsm"), (3, 40, 8), (2, 15, 2), (1, 30, 1), (3, 25, 0)]:
+        ld = loader(ti)
+        tr = param_tracker(ti, N, pset)
+        for rep in range(2):
+            x0 = draw_x0(ld, rng)
+            if rep == 1:
+                x0[0] = ld.s_max - rng.uniform(0, 3)      # horizon runs past s_max
+            obs = draw_obstacles(kind, x0, rng)
+            U = np.column_stack([rng.uniform(tr.u_min[0], tr.u_max[0], N), rng.uniform(tr.u_min[1], tr.u_max[1], N)]).ravel()
+            cases.append(dict(traj=ti, N=N, x0=x0, obs=_obs_array(obs), U=U, X=tr.predict(x0, U), cost=tr.cost(U, x0),
+                              cons=tr.constraints(x0, obs)["fun"](U)))
+    return cases
+
+
+def gen_params_warmstart(name, pset, rng):
+    cases = []
+    for (ti, N, kind) in [(1, 10, 1), (2, 20, "fsm"), (3, 40, 8), (1, 25, 0)]:
+        ld = loader(ti)
+        tr = param_tracker(ti, N, pset)
+        for rep in range(4):
+            x0 = draw_x0(ld, rng)
+            if rep == 2:
+                x0[0] = ld.s_max - rng.uniform(0, 4)
+            obs = draw_obstacles(kind, x0, rng)
+            if rep == 1 and kind != 0:       # obstacle just at the brake threshold, two steps ahead at this set's dt
+                obs = [{"s": x0[0] + 40.0 + x0[4] * tr.dt * 2 + 1e-9, "v": 1.0, "type": "car"}]
+            if rep == 3 and kind != 0:       # and just inside it from the start
+                obs = [{"s": x0[0] + 40.0 - 1e-9, "v": 1.0, "type": "car"}]
+            cases.append(dict(traj=ti, N=N, x0=x0, obs=_obs_array(obs), ubar=capture_warmstart(tr, x0, obs)))
+    return cases
+
+
+def gen_params():
+    """The qp, model and warmstart records of gen_qp / gen_model / gen_warmstart under each of PARAM_SETS, from a
+    reference TrajectoryTracker whose attributes are set to the set.  Keys: sets_json (the sets), rho, and per set
+    S and kind K in (qp, model, warmstart): S_K_n and S_K_c<j>_<field>."""
+    out = {"sets_json": np.array(json.dumps(PARAM_SETS)), "rho": np.array(RHO_DEFAULT)}
+    for si, (name, pset) in enumerate(PARAM_SETS.items()):
+        rng = np.random.default_rng(7000 + si)
+        for kind, gen in (("qp", gen_params_qp), ("model", gen_params_model), ("warmstart", gen_params_warmstart)):
+            cases = gen(name, pset, rng)
+            out[f"{name}_{kind}_n"] = np.array(len(cases))
+            for j, c in enumerate(cases):
+                for k, v in c.items():
+                    out[f"{name}_{kind}_c{j}_{k}"] = np.asarray(v)
+    save("params_golden", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -913,7 +1054,7 @@ def main():
                                               "solve", "closedloop"]
     fns = dict(convert=convert_trajectories, interp=gen_interp, pose=gen_pose, model=gen_model, warmstart=gen_warmstart,
                qpdata=gen_qpdata, qp=lambda: gen_qp(a.quick), solve=gen_solve, closedloop=gen_closedloop,
-               nlp=gen_nlp)
+               nlp=gen_nlp, params=gen_params)
     for t in todo:
         print(f"== {t}")
         fns[t]()

@@ -120,13 +120,14 @@ def _oracle(traj):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_solve(name, N, sqp=1, with_obs=True):
+def oracle_solve(name, N, sqp=1, with_obs=True, pset=()):
     """(oracle result, ctx of check_vs_oracle) of sweep_batch(name, N, with_obs): computed once per case and
-    shared by the tests (read only)."""
+    shared by the tests (read only).  pset: ((field, value), ...) of the mpc_params fields that differ from the
+    defaults (hashable: u_min / u_max as tuples)."""
     import oracle as O
     wb = sweep_batch(name, N, with_obs)
     orc = _oracle(wb["traj"])
-    po = O.default_params(N=wb["N"], max_obs=wb["max_obs"], sqp_iters=sqp)
+    po = O.default_params(N=wb["N"], max_obs=wb["max_obs"], sqp_iters=sqp, **dict(pset))
     ro = orc.solve_batch(po, wb["x0"], wb["obs"], wb["n_obs"])
     return ro, (orc, po, wb["x0"], wb["obs"], wb["n_obs"])
 
@@ -214,14 +215,14 @@ SQP_CASES = [("C2", 17, True), ("C2", 31, True), ("C2", 33, True), ("C3", 17, Tr
              ("C3", 33, True), ("C4", 30, False), ("C5", 40, False), ("C5", 40, True)]
 
 
-def last_linearisation_point(name, N, sqp, with_obs):
+def last_linearisation_point(name, N, sqp, with_obs, pset=()):
     """[B, N, 2]: the point each instance's last QP was linearised at in the oracle's run of at most `sqp` QPs:
     the warm start, or U after k QPs wherever QP k + 1 still ran (the run capped at k + 1 returns another U)."""
-    _, (orc, po, x0, obs, n_obs) = oracle_solve(name, N, 1, with_obs)
+    _, (orc, po, x0, obs, n_obs) = oracle_solve(name, N, 1, with_obs, pset)
     ub = np.stack([orc.warm_start(po, x0[i], None if obs is None else obs[i, :n_obs[i]]) for i in range(len(x0))])
     ub = ub.reshape(len(x0), N, 2)
     for k in range(1, sqp):
-        uk, uk1 = oracle_solve(name, N, k, with_obs)[0]["U"], oracle_solve(name, N, k + 1, with_obs)[0]["U"]
+        uk, uk1 = (oracle_solve(name, N, j, with_obs, pset)[0]["U"] for j in (k, k + 1))
         ran = (uk != uk1).reshape(len(x0), -1).any(axis=1)
         ub[ran] = uk[ran]
     return ub

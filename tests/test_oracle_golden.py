@@ -12,8 +12,10 @@ from conftest import golden_cases, load_golden
 import oracle as O
 
 
-def params(N, nobs=0, **kw):
-    return O.default_params(N=int(N), max_obs=int(nobs), **kw)
+def params(N, nobs=0, pset=None, **kw):
+    """Oracle parameters at horizon N; pset: mpc_params fields that differ from the defaults (a parameter set of
+    tests/golden/params_golden.npz)."""
+    return O.default_params(N=int(N), max_obs=int(nobs), **dict(pset or {}), **kw)
 
 
 @pytest.mark.parametrize("ti", [1, 2, 3])
