@@ -3,7 +3,9 @@
 // and launch_solve, and the state structs of the closed-loop kernel headers.
 //
 // An entry checks its arguments, declares its buffers and outputs on a ClDriver, launches its own init kernels and
-// hands the loop two callables: what runs before the solve of a step and the plant kernel after it.  Everything
+// hands the loop two callables: what runs before the solve of a step and the plant kernel after it.  The five
+// scripted entries do so in one place, scripted_loop() of mpcqp.hip, from the one ScriptedLoop request
+// (scripted_loop.h) that the host backend takes too, with what follows from its fields stated there.  Everything
 // else is here, once: the device-buffer owner, the output table (allocation, all-ones pre-fill and copy-back of a
 // host output from one binding), the step-time event ring, the loop with its every-8-steps host sync and list
 // compaction, and the copy-out of n_steps / quant / extra.

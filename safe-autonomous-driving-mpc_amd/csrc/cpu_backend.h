@@ -29,6 +29,7 @@
 
 #include "host_table.h"
 #include "loop_steps.h"
+#include "scripted_loop.h"
 
 namespace mpcqp_cpu {
 
@@ -1370,13 +1371,13 @@ struct Backend {
         return MPC_SUCCESS;
     }
 
-    // The loop behind the three scripted members below.  Ego b runs the script actors[(n_scripts == 1 ? 0 : b) * A
-    // + a] (script_step); the slab takes what its actors emit, then (s, v) of its leaders, n_obs entries of A + K.
-    // with_slab: the solver runs with max_obs = A + K.
+    // The five scripted entries on the host: the request `a` (scripted_loop.h) as the entry filled it, slot[b] the
+    // history row of ego b or -1.  Ego b runs the script a.script(b) (script_step); the slab takes what its actors
+    // emit, then (s, v) of its leaders, n_obs entries of A + K.  with_slab: the solver runs with max_obs = A + K.
     //   worlds (K > 0): per step every world's egos [w*W, (w+1)*W) still in the loop are sorted by the ahead-of
     //     order (the larger s first, on equal s the lower index) on the states before the step; an ego's leaders
     //     are its predecessors in that order, nearest first, at most K, cut at the first gap >= lead_range.
-    //   noise (noise != NULL, [n_noise], n_noise 1 or B; ego b draws as global ego ego_offset + b): the FSMs, the
+    //   noise (the sigmas a.noise_of(b); ego b draws as global ego ego_offset + b): the FSMs, the
     //     leader ranking, the gap quantities, hist_slab and the exit test use the true states; the solver receives
     //     x + meas_sigma * z and a perturbed copy of the slab; the plant integrates the clamped u + act_sigma * z
     //     and adds (dt * proc_sigma) * z.
@@ -1390,50 +1391,43 @@ struct Backend {
     //     [B][MPC_WQ_NQ]; hist_ubar is [n_hist][max_steps][N][2].
     // extra is [B][nx] (MPC_TR_NX; MPC_CV_NX with worlds; MPC_NZ_NX with noise); extra, n_steps, step_ms and every
     // history are optional; hist_slab is [n_hist][max_steps][A+K][2], hist_lead [n_hist][max_steps][K]
-    int closed_loop_scripted(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
-                             const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
-                             int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
-                             double* quant, double* extra, int nx, int n_hist, const int* slot, double* hist_x,
-                             double* hist_u, double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl,
-                             int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
-                             double* step_ms, const int* lookahead = nullptr, int n_look = 0, double* gapq = nullptr,
-                             double* hist_pred = nullptr, double* hist_plan = nullptr, const mpc_warm* warm = nullptr,
-                             double* warmq = nullptr, double* hist_ubar = nullptr) const {
+    int closed_loop_scripted(const mpc_params& p0, const ScriptedLoop& a, const int* slot) const {
+        const int B = a.B, W = a.W, K = a.K, A = a.A, nx = a.nx();
         mpc_params p = p0;
         const int AK = A + K;
-        p.max_obs = with_slab ? AK : 0;
-        const size_t nb = (size_t)B, ns = (size_t)max_steps, nh = (size_t)n_hist, na = (size_t)A, nk = (size_t)K;
+        p.max_obs = a.with_slab ? AK : 0;
+        const size_t nb = (size_t)B, ns = (size_t)a.max_steps, nh = (size_t)a.n_hist, na = (size_t)A, nk = (size_t)K;
         const size_t nak = (size_t)AK, nxs = (size_t)nx;
-        hist_prefill(hist_ua, nh * ns * 2, (double)NAN);
-        hist_prefill(hist_xm, nh * ns * 5, (double)NAN);
-        hist_prefill(hist_car_s, nh * ns, (double)NAN);
-        hist_prefill(hist_tl, nh * ns, -1);
-        hist_prefill(hist_nobs, nh * ns, -1);
-        hist_prefill(hist_slab, nh * ns * nak * 2, (double)NAN);
-        hist_prefill(hist_lead, nh * ns * nk, -1);
+        hist_prefill(a.hist_ua, nh * ns * 2, (double)NAN);
+        hist_prefill(a.hist_xm, nh * ns * 5, (double)NAN);
+        hist_prefill(a.hist_car_s, nh * ns, (double)NAN);
+        hist_prefill(a.hist_tl, nh * ns, -1);
+        hist_prefill(a.hist_nobs, nh * ns, -1);
+        hist_prefill(a.hist_slab, nh * ns * nak * 2, (double)NAN);
+        hist_prefill(a.hist_lead, nh * ns * nk, -1);
         const size_t nu = 2 * (size_t)p.N, nxp = 5 * ((size_t)p.N + 1);
-        hist_prefill(hist_pred, nh * ns * nxp, (double)NAN);
-        hist_prefill(hist_plan, nh * ns * nu, (double)NAN);
-        hist_prefill(hist_ubar, nh * ns * nu, (double)NAN);
+        hist_prefill(a.hist_pred, nh * ns * nxp, (double)NAN);
+        hist_prefill(a.hist_plan, nh * ns * nu, (double)NAN);
+        hist_prefill(a.hist_ubar, nh * ns * nu, (double)NAN);
         // the kept plan [N][2], status (-1: none yet) and n_obs of every ego, and its warm row
-        std::vector<double> kplan(warm ? nb * nu : 0, 0.0), wq(warm ? nb * MPC_WQ_NQ : 0);
-        std::vector<int> kstatus(warm ? nb : 0, -1), knobs(warm ? nb : 0, 0);
-        for (size_t b = 0; warm && b < nb; ++b) warm_init(wq.data() + b * MPC_WQ_NQ);
+        std::vector<double> kplan(a.warm ? nb * nu : 0, 0.0), wq(a.warm ? nb * MPC_WQ_NQ : 0);
+        std::vector<int> kstatus(a.warm ? nb : 0, -1), knobs(a.warm ? nb : 0, 0);
+        for (size_t b = 0; a.warm && b < nb; ++b) warm_init(wq.data() + b * MPC_WQ_NQ);
         size_t slots = 0;                                 // ring slots of one ego, lookahead i's from ring0[i] on
         size_t ring0[MPC_MAX_LOOK] = {};
-        for (int i = 0; i < n_look; ++i) {
+        for (int i = 0; i < a.n_look; ++i) {
             ring0[i] = slots;
-            slots += (size_t)lookahead[i];
+            slots += (size_t)a.lookahead[i];
         }
         std::vector<double> ring(nb * slots * 3, 0.0);
-        for (size_t k = 0; k < nb * (size_t)n_look; ++k) trace_init(gapq + k * MPC_TG_NQ);
-        LoopEgos E(B, x_init, max_steps, s_stop, quant, n_hist, slot, hist_x, hist_u, hist_status, step_ms);
-        const mpc_noise quiet = {};
+        for (size_t k = 0; k < nb * (size_t)a.n_look; ++k) trace_init(a.gapq + k * MPC_TG_NQ);
+        LoopEgos E(B, a.x_init, a.max_steps, a.s_stop, a.quant, a.n_hist, slot, a.hist_x, a.hist_u, a.hist_status,
+                   a.step_ms);
         std::vector<double> aval(nb * na, 0.0), ex(nb * nxs, 0.0);
         std::vector<int> aflags(nb * na, 0);
         std::vector<int> order(nb), rank(nb, -1), wbeg((size_t)(B / W) + 1, 0);
         for (int b = 0; b < B; ++b) {
-            const mpc_actor* sc = actors + (n_scripts == 1 ? 0 : (size_t)b * na);
+            const mpc_actor* sc = a.script(b);
             for (int a = 0; a < A; ++a)
                 if (sc[a].kind == MPC_ACTOR_CAR) aval[(size_t)b * na + a] = sc[a].pos_s;
             double* e = ex.data() + (size_t)b * nxs;
@@ -1443,7 +1437,7 @@ struct Backend {
                 e[MPC_CVX_MIN_LEAD_EGO] = -1.0;
             }
         }
-        run_loop(p, E, max_steps, with_slab, nak,
+        run_loop(p, E, a.max_steps, a.with_slab, nak,
                  [&](const std::vector<int>& alist) {
                      if (K == 0) return;
                      // alist is increasing, so each world's egos in the loop are one run of it: sort the run, and
@@ -1462,26 +1456,26 @@ struct Backend {
                      for (int i = 0; i < nl; ++i) rank[order[i]] = i;
                  },
                  [&](int step, int b, double* xm, double* oa) {
-                     const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
-                     const NoiseAt at = {(unsigned)seed, (unsigned)(seed >> 32),
-                                         (unsigned long long)ego_offset + (unsigned long long)b, step};
+                     const mpc_noise& Z = a.noise_of(b);
+                     const NoiseAt at = {(unsigned)a.seed, (unsigned)(a.seed >> 32),
+                                         (unsigned long long)a.ego_offset + (unsigned long long)b, step};
                      const double s = E.x[5 * (size_t)b], v = E.x[5 * (size_t)b + 4];
                      double o[2 * MPC_MAX_ACTORS];            // the true slab of this step
-                     double* q = quant + (size_t)b * MPC_CL_NQ;
+                     double* q = a.quant + (size_t)b * MPC_CL_NQ;
                      double* e = ex.data() + (size_t)b * nxs;
                      int green;
                      double car_s;
-                     int n = script_step(actors + (n_scripts == 1 ? 0 : (size_t)b * na), A, p.dt, s, v,
-                                         aflags.data() + (size_t)b * na, aval.data() + (size_t)b * na, o, q, e,
-                                         E.qflags[b], green, car_s);
+                     int n = script_step(a.script(b), A, p.dt, s, v, aflags.data() + (size_t)b * na,
+                                         aval.data() + (size_t)b * na, o, q, e, E.qflags[b], green, car_s);
                      if (K > 0) {                             // the leaders, nearest first
-                         int* hlead = hist_lead && slot[b] >= 0 ? hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
+                         int* hlead =
+                             a.hist_lead && slot[b] >= 0 ? a.hist_lead + ((size_t)slot[b] * ns + step) * nk : nullptr;
                          const int r = rank[b], r0 = wbeg[b / W];
                          int nlead = 0;
                          for (; nlead < K && r - 1 - nlead >= r0; ++nlead) {
                              const int j = order[r - 1 - nlead];
                              const double sj = E.x[5 * (size_t)j], gap = sj - s;
-                             if (gap >= lead_range) break;
+                             if (gap >= a.lead_range) break;
                              o[2 * n] = sj;
                              o[2 * n + 1] = E.x[5 * (size_t)j + 4];
                              ++n;
@@ -1501,18 +1495,19 @@ struct Backend {
                          oa[j] = noise_add(o[j], Z.perc_sigma[j & 1], at, MPC_NZ_CH_PERC + j);
                      if (slot[b] >= 0) {
                          const size_t h = (size_t)slot[b] * ns + step;
-                         if (hist_car_s) hist_car_s[h] = car_s;
-                         if (hist_tl) hist_tl[h] = green;
-                         if (hist_nobs) hist_nobs[h] = n;
-                         if (hist_slab && n) std::memcpy(hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
-                         if (hist_xm) std::memcpy(hist_xm + h * 5, xm, 5 * sizeof(double));
+                         if (a.hist_car_s) a.hist_car_s[h] = car_s;
+                         if (a.hist_tl) a.hist_tl[h] = green;
+                         if (a.hist_nobs) a.hist_nobs[h] = n;
+                         if (a.hist_slab && n)
+                             std::memcpy(a.hist_slab + h * nak * 2, o, (size_t)n * 2 * sizeof(double));
+                         if (a.hist_xm) std::memcpy(a.hist_xm + h * 5, xm, 5 * sizeof(double));
                      }
                      return n;
                  },
                  [&](int step, int b, const double* u, int status) {
-                     const mpc_noise& Z = noise ? noise[n_noise == 1 ? 0 : b] : quiet;
-                     const NoiseAt at = {(unsigned)seed, (unsigned)(seed >> 32),
-                                         (unsigned long long)ego_offset + (unsigned long long)b, step};
+                     const mpc_noise& Z = a.noise_of(b);
+                     const NoiseAt at = {(unsigned)a.seed, (unsigned)(a.seed >> 32),
+                                         (unsigned long long)a.ego_offset + (unsigned long long)b, step};
                      double ua[2];                            // the applied control
                      bool clamped = false;
                      for (int k = 0; k < 2; ++k)
@@ -1524,16 +1519,16 @@ struct Backend {
                      });
                      if (nx < MPC_NZ_NX) return;
                      double* e = ex.data() + (size_t)b * nxs;
-                     if (slot[b] >= 0 && hist_ua)
-                         std::memcpy(hist_ua + ((size_t)slot[b] * ns + step) * 2, ua, sizeof(ua));
+                     if (slot[b] >= 0 && a.hist_ua)
+                         std::memcpy(a.hist_ua + ((size_t)slot[b] * ns + step) * 2, ua, sizeof(ua));
                      extremes4(e, MPC_NZX_U1A_MIN, step, ua[0], ua[1]);
                      if (clamped) e[MPC_NZX_N_CLAMPED] += 1.0;
                  },
-                 n_look > 0 || hist_pred || hist_plan,
+                 a.traced(),
                  [&](int step, int b, const double* U, const double* Xp) {
                      const double* x = E.x.data() + 5 * (size_t)b;       // the true state after the step
-                     for (int i = 0; i < n_look; ++i) {
-                         const int j = lookahead[i];
+                     for (int i = 0; i < a.n_look; ++i) {
+                         const int j = a.lookahead[i];
                          double* rg = ring.data() + ((size_t)b * slots + ring0[i]) * 3;
                          double* w = rg + 3 * (size_t)trace_slot(step, j);
                          w[0] = Xp[5 * j];
@@ -1542,25 +1537,26 @@ struct Backend {
                          if (!trace_pair(step, j)) continue;
                          const int t0 = step + 1 - j;                    // j == 1: the slot just written
                          const double* r = rg + 3 * (size_t)trace_slot(t0, j);
-                         trace_gap(gapq + ((size_t)b * n_look + i) * MPC_TG_NQ, t0, r[0], r[1], r[2], x[0], x[1], x[4]);
+                         trace_gap(a.gapq + ((size_t)b * a.n_look + i) * MPC_TG_NQ, t0, r[0], r[1], r[2], x[0], x[1],
+                                   x[4]);
                      }
                      if (slot[b] < 0) return;
                      const size_t h = (size_t)slot[b] * ns + step;
-                     if (hist_pred) std::memcpy(hist_pred + h * nxp, Xp, nxp * sizeof(double));
-                     if (hist_plan) std::memcpy(hist_plan + h * nu, U, nu * sizeof(double));
+                     if (a.hist_pred) std::memcpy(a.hist_pred + h * nxp, Xp, nxp * sizeof(double));
+                     if (a.hist_plan) std::memcpy(a.hist_plan + h * nu, U, nu * sizeof(double));
                  },
-                 warm != nullptr,
+                 a.warm != nullptr,
                  [&](int step, int b, const double* xm, const double* oa, int nobs, double* ub) {
                      const int N = p.N;
                      const double* kp = kplan.data() + (size_t)b * nu;
                      bool finite = true;
-                     if (kstatus[b] >= 0 && warm->mode == MPC_WARM_CARRY)
+                     if (kstatus[b] >= 0 && a.warm->mode == MPC_WARM_CARRY)
                          for (size_t e = 0; e < nu; ++e) finite = finite && warm_finite(kp[e]);
-                     const bool reset = warm_reset(*warm, kstatus[b], finite, knobs[b], nobs);
-                     const bool walk = reset || warm->tail == MPC_WTAIL_REFERENCE;
+                     const bool reset = warm_reset(*a.warm, kstatus[b], finite, knobs[b], nobs);
+                     const bool walk = reset || a.warm->tail == MPC_WTAIL_REFERENCE;
                      WarmRef w = warm_ref_begin(xm);
                      for (int k = 0; k < N; ++k) {
-                         const int src = reset ? -1 : warm_source(k, N, warm->tail);
+                         const int src = reset ? -1 : warm_source(k, N, a.warm->tail);
                          if (walk) warm_ref_advance(w, k, p.dt, oa, nobs, p.brake_distance);
                          if (src < 0) {
                              warm_ref_control(w, p.brake_accel, [&](double s, double* ur) { ref->control(s, ur); },
@@ -1571,8 +1567,8 @@ struct Backend {
                          }
                      }
                      if (reset) wq[(size_t)b * MPC_WQ_NQ + MPC_WQ_N_RESET] += 1.0;
-                     if (hist_ubar && slot[b] >= 0)
-                         std::memcpy(hist_ubar + ((size_t)slot[b] * ns + step) * nu, ub, nu * sizeof(double));
+                     if (a.hist_ubar && slot[b] >= 0)
+                         std::memcpy(a.hist_ubar + ((size_t)slot[b] * ns + step) * nu, ub, nu * sizeof(double));
                  },
                  [&](int step, int b, const double* U, const double* ub, int status, int nobs) {
                      double move = 0.0;
@@ -1582,79 +1578,12 @@ struct Backend {
                      knobs[b] = nobs;
                      warm_move(wq.data() + (size_t)b * MPC_WQ_NQ, step, move);
                  });
-        E.finish(n_steps);
-        if (warmq) std::memcpy(warmq, wq.data(), nb * MPC_WQ_NQ * sizeof(double));
-        if (extra) std::memcpy(extra, ex.data(), nb * nxs * sizeof(double));
+        E.finish(a.n_steps);
+        if (a.warmq) std::memcpy(a.warmq, wq.data(), nb * MPC_WQ_NQ * sizeof(double));
+        if (a.extra) std::memcpy(a.extra, ex.data(), nb * nxs * sizeof(double));
         return MPC_SUCCESS;
     }
 
-    // mpc_closed_loop_traffic on the host: the sweep with a script of A actors per ego, no worlds, no noise
-    int closed_loop_traffic(const mpc_params& p0, int B, const double* x_init, const mpc_actor* actors, int A,
-                            int n_scripts, bool with_slab, int max_steps, double s_stop, double* quant,
-                            double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
-                            double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs, double* hist_slab,
-                            int* n_steps, double* step_ms) const {
-        return closed_loop_scripted(p0, B, 1, 0, INFINITY, x_init, actors, A, n_scripts, with_slab, nullptr, 1, 0, 0,
-                                    max_steps, s_stop, quant, extra, MPC_TR_NX, n_hist, slot, hist_x, hist_u, nullptr,
-                                    nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps,
-                                    step_ms);
-    }
-
-    // mpc_closed_loop_convoy on the host: the egos [w*W, (w+1)*W) of a world as each other's obstacles
-    int closed_loop_convoy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
-                           const mpc_actor* actors, int A, int n_scripts, bool with_slab, int max_steps,
-                           double s_stop, double* quant, double* extra, int n_hist, const int* slot, double* hist_x,
-                           double* hist_u, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
-                           double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
-        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, nullptr, 1, 0, 0,
-                                    max_steps, s_stop, quant, extra, MPC_CV_NX, n_hist, slot, hist_x, hist_u, nullptr,
-                                    nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps,
-                                    step_ms);
-    }
-
-    // mpc_closed_loop_noisy on the host: the convoy with seeded noise between the world and the solver
-    int closed_loop_noisy(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
-                          const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
-                          int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
-                          double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
-                          double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
-                          int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) const {
-        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
-                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
-                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
-                                    hist_lead, n_steps, step_ms);
-    }
-
-    // mpc_closed_loop_traced on the host: the noisy loop with the plans kept and the plan-vs-outcome gaps
-    int closed_loop_traced(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
-                           const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
-                           int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
-                           double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
-                           double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
-                           int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
-                           const int* lookahead, int n_look, double* gapq, double* hist_pred,
-                           double* hist_plan) const {
-        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
-                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
-                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
-                                    hist_lead, n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan);
-    }
-
-    // mpc_closed_loop_warm on the host: the traced loop whose solver is handed the warm start `warm` describes
-    int closed_loop_warm(const mpc_params& p0, int B, int W, int K, double lead_range, const double* x_init,
-                         const mpc_actor* actors, int A, int n_scripts, bool with_slab, const mpc_noise* noise,
-                         int n_noise, unsigned long long seed, long long ego_offset, int max_steps, double s_stop,
-                         double* quant, double* extra, int n_hist, const int* slot, double* hist_x, double* hist_u,
-                         double* hist_ua, double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status,
-                         int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
-                         const int* lookahead, int n_look, double* gapq, double* hist_pred, double* hist_plan,
-                         const mpc_warm& warm, double* warmq, double* hist_ubar) const {
-        return closed_loop_scripted(p0, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, noise, n_noise,
-                                    seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, slot, hist_x,
-                                    hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab,
-                                    hist_lead, n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan, &warm,
-                                    warmq, hist_ubar);
-    }
 };
 
 // MPC_CLQ_MAX_STEP_MS of every ego: the prefix max of the step times over the steps it ran, max(ms[:n]) with

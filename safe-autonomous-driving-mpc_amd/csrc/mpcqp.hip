@@ -811,48 +811,20 @@ extern "C" void mpc_default_warm(mpc_warm* w) {
     w->reset = 0;
 }
 
-// What the five scripted entries hand on once their arguments are checked: mpc_closed_loop_traffic (W == 0: no
-// worlds, K == 0), mpc_closed_loop_convoy, mpc_closed_loop_noisy (noisy; noise is then never NULL),
-// mpc_closed_loop_traced (noisy, with the trace outputs; the first three leave them empty) and mpc_closed_loop_warm
-// (traced, with `warm` set when the solver is to be handed a ubar; the other four leave it and its outputs empty)
-struct ScriptedLoop {
-    const char* label;
-    int B, W, K;
-    double lead_range;
-    const double* x_init;
-    const mpc_actor* actors;
-    int A, n_scripts;
-    bool with_slab, noisy;
-    const mpc_noise* noise;
-    int n_noise;
-    unsigned long long seed;
-    long long ego_offset;
-    int max_steps;
-    double s_stop;
-    double *quant, *extra;
-    int nx;                                 // the width of extra: MPC_TR_NX, MPC_CV_NX or MPC_NZ_NX
-    int n_hist;
-    const int* hist_egos;
-    double *hist_x, *hist_u, *hist_ua, *hist_xm, *hist_car_s;
-    int *hist_tl, *hist_status, *hist_nobs;
-    double* hist_slab;
-    int* hist_lead;
-    int* n_steps;
-    double* step_ms;
-    const int* lookahead;
-    int n_look;
-    double *gapq, *hist_pred, *hist_plan;
-    const mpc_warm* warm;
-    double *warmq, *hist_ubar;
-};
-
-// The loop of the scripted entries around tr_fsm_kernel and an (A + K)-wide slab.  With worlds, cv_lead_kernel
+// The five scripted entries check their arguments and fill one ScriptedLoop (scripted_loop.h) by name:
+// mpc_closed_loop_traffic (no worlds), mpc_closed_loop_convoy (worlds), mpc_closed_loop_noisy (noisy worlds),
+// mpc_closed_loop_traced (with the trace outputs) and mpc_closed_loop_warm (with `warm` set when the solver is to be
+// handed a ubar).  scripted_loop() derives the history slots once and passes the request on as it is: to
+// Backend::closed_loop_scripted on a host context, to the kernels below otherwise.
+//
+// The device loop of the scripted entries around tr_fsm_kernel and an (A + K)-wide slab.  With worlds, cv_lead_kernel
 // ranks the leaders between the FSM and the gather and writes the slab histories (tr_fsm_kernel's rows are A
-// wide).  Noisy: nz_measure_kernel for tr_gather_kernel and nz_plant_kernel for sw_plant_kernel, on the field-major
-// sigma table [14][B] for per-ego noise; the other kernels are reused untouched and see the true states.  Traced
-// (any trace output asked for): the solver also writes its U and Xpred of the listed egos, and tg_gap_kernel and
-// tg_hist_kernel follow the plant kernel.  Warm (a.warm set): ws_carry_kernel fills the solver's ubar after the
-// measure kernel, the solver is asked for its U, and ws_keep_kernel follows the plant kernel
+// wide); without worlds no cv_* kernel is launched.  Noisy: nz_measure_kernel for tr_gather_kernel and
+// nz_plant_kernel for sw_plant_kernel, on the field-major sigma table [14][B] for per-ego noise; the other kernels
+// are reused untouched and see the true states.  Traced (any trace output asked for): the solver also writes its U
+// and Xpred of the listed egos, and tg_gap_kernel and tg_hist_kernel follow the plant kernel.  Warm (a.warm set):
+// ws_carry_kernel fills the solver's ubar after the measure kernel, the solver is asked for its U, and
+// ws_keep_kernel follows the plant kernel
 static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     const int B = a.B, A = a.A, K = a.K, AK = A + K, max_steps = a.max_steps;
     std::vector<int> slot;
@@ -862,42 +834,8 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     if (!a.x_init) return fail(MPC_E_ARG, "x_init is required");
     rc = check_params(&c->p);
     if (rc) return rc;
-    const bool per_ego = a.n_scripts == B && B > 1;  // n_scripts == B == 1 is the shared case
-    const int nsc = per_ego ? B : (a.actors ? 1 : 0);
-    const bool nz_per_ego = a.noisy && a.n_noise == B && B > 1;
-    const bool traced = a.n_look > 0 || a.hist_pred || a.hist_plan;
-    if (c->cpu)
-        return host_loop([&] {
-            const int hsc = nsc == 0 ? 1 : nsc;
-            if (a.warm)
-                return c->cpu->closed_loop_warm(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
-                                                a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
-                                                a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
-                                                a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
-                                                a.hist_slab, a.hist_lead, a.n_steps, a.step_ms, a.lookahead, a.n_look,
-                                                a.gapq, a.hist_pred, a.hist_plan, *a.warm, a.warmq, a.hist_ubar);
-            if (traced)
-                return c->cpu->closed_loop_traced(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
-                                                  a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
-                                                  a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
-                                                  a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
-                                                  a.hist_slab, a.hist_lead, a.n_steps, a.step_ms, a.lookahead, a.n_look,
-                                                  a.gapq, a.hist_pred, a.hist_plan);
-            if (a.noisy)
-                return c->cpu->closed_loop_noisy(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
-                                                 a.noise, nz_per_ego ? B : 1, a.seed, a.ego_offset, max_steps, a.s_stop,
-                                                 a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_ua,
-                                                 a.hist_xm, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
-                                                 a.hist_slab, a.hist_lead, a.n_steps, a.step_ms);
-            if (a.W)
-                return c->cpu->closed_loop_convoy(c->p, B, a.W, K, a.lead_range, a.x_init, a.actors, A, hsc, a.with_slab,
-                                                  max_steps, a.s_stop, a.quant, a.extra, a.n_hist, slot.data(), a.hist_x,
-                                                  a.hist_u, a.hist_car_s, a.hist_tl, a.hist_status, a.hist_nobs,
-                                                  a.hist_slab, a.hist_lead, a.n_steps, a.step_ms);
-            return c->cpu->closed_loop_traffic(c->p, B, a.x_init, a.actors, A, hsc, a.with_slab, max_steps, a.s_stop,
-                                               a.quant, a.extra, a.n_hist, slot.data(), a.hist_x, a.hist_u, a.hist_car_s,
-                                               a.hist_tl, a.hist_status, a.hist_nobs, a.hist_slab, a.n_steps, a.step_ms);
-        });
+    if (c->cpu) return host_loop([&] { return c->cpu->closed_loop_scripted(c->p, a, slot.data()); });
+    const bool per_ego = a.per_ego(), nz_per_ego = a.nz_per_ego(), traced = a.traced();
     KParams kp = kparams(&c->p);
     kp.max_obs = a.with_slab ? AK : 0;      // every actor and every leader adds at most one entry
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
@@ -918,12 +856,12 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     D.cl_state(a.x_init, (size_t)AK, false);
     const ClState& C = D.C;
     SwState S = D.sw_state(slot.data(), a.n_hist, a.hist_x, a.hist_u, a.hist_car_s, a.hist_tl, a.hist_status);
-    TrState T = D.tr_state(a.actors, A, nsc, per_ego, (size_t)AK, a.nx, a.n_hist, a.hist_nobs);
+    TrState T = D.tr_state(a.actors, A, a.nsc(), per_ego, (size_t)AK, a.nx(), a.n_hist, a.hist_nobs);
     CvState V = {};
     V.W = a.W;
     V.K = K;
     V.lead_range = a.lead_range;
-    if (a.W) {
+    if (a.worlds) {
         V.hist_slab = D.out(a.hist_slab, nhs * (size_t)AK * 2);
         V.hist_lead = D.out(a.hist_lead, nhs * (size_t)K);
     } else {
@@ -931,10 +869,8 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     }
     NzState Z = {};
     if (a.noisy) {
-        mpc_noise zero;
-        mpc_default_noise(&zero);
         Z.sig = nz_per_ego ? D.in(hsig.data(), hsig.size(), hsig.size()) : nullptr;
-        Z.shared = nz_per_ego ? zero : a.noise[0];
+        Z.shared = nz_per_ego ? a.quiet : a.noise_of(0);
         Z.k0 = (unsigned)(a.seed & 0xffffffffull);
         Z.k1 = (unsigned)(a.seed >> 32);
         Z.g0 = (unsigned long long)a.ego_offset;
@@ -1001,16 +937,16 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
     rc = D.begin();
     if (rc) return rc;
     const dim3 tb = D.tb, tg = D.tg;
-    const dim3 wb(64 * ((a.W + 63) / 64)), wg(a.W ? B / a.W : 1);    // a workgroup per world
+    const dim3 wb(64 * ((a.W + 63) / 64)), wg(B / a.W);              // a workgroup per world
     hipLaunchKernelGGL(tr_init_kernel, tg, tb, 0, st, B, A, C, S, T, D.xinit, a.s_stop, max_steps);
-    if (a.W) hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
+    if (a.worlds) hipLaunchKernelGGL(cv_init_kernel, tg, tb, 0, st, B, T);
     if (a.noisy) hipLaunchKernelGGL(nz_init_kernel, tg, tb, 0, st, B, T);
     if (G.n_look) hipLaunchKernelGGL(tg_init_kernel, tg, tb, 0, st, B, G);
     if (a.warm) hipLaunchKernelGGL(ws_init_kernel, tg, tb, 0, st, B, Ws);
     rc = D.run(kp, a.with_slab, true,
                [&](int step, int nl, dim3 lg) {
                    hipLaunchKernelGGL(tr_fsm_kernel, tg, tb, 0, st, B, A, kp.dt, C, S, T, step, max_steps);
-                   if (a.W) hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
+                   if (a.worlds) hipLaunchKernelGGL(cv_lead_kernel, wg, wb, 0, st, B, A, C, S, T, V, step, max_steps);
                    if (a.noisy) hipLaunchKernelGGL(nz_measure_kernel, lg, tb, 0, st, nl, B, AK, C, S, T, Z, step, max_steps);
                    else hipLaunchKernelGGL(tr_gather_kernel, lg, tb, 0, st, nl, B, AK, C, T);
                    if (a.warm) hipLaunchKernelGGL(ws_carry_kernel, lg, tb, 0, st, c->tab, nl, B, C, S, Ws, step, max_steps);
@@ -1031,7 +967,7 @@ static int scripted_loop(mpc_ctx* c, const ScriptedLoop& a) {
                    if (a.warm) hipLaunchKernelGGL(ws_keep_kernel, lg, tb, 0, st, nl, B, C, S, Ws, step);
                },
                d_U, d_Xp, Ws.ubara);
-    if (rc == MPC_SUCCESS) rc = D.finish(S, T.ex, a.nx, a.quant, a.extra, a.n_steps, a.step_ms);
+    if (rc == MPC_SUCCESS) rc = D.finish(S, T.ex, a.nx(), a.quant, a.extra, a.n_steps, a.step_ms);
     if (rc == MPC_SUCCESS)                  // field-major on the device, one row per ego and lookahead outside
         for (size_t b = 0; b < D.nb; ++b)
             for (size_t k = 0; k < (size_t)a.n_look * MPC_TG_NQ; ++k) a.gapq[b * a.n_look * MPC_TG_NQ + k] = hgap[k * D.nb + b];
@@ -1049,16 +985,18 @@ extern "C" int mpc_closed_loop_traffic(mpc_ctx* c, int B, const double* x_init, 
                                        double* hist_slab, int* n_steps, double* step_ms) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
-    bool with_slab = false;
-    int rc = cl_check_script(actors, A, n_scripts, B, with_slab);
+    ScriptedLoop a;
+    a.label = "traffic";
+    int rc = cl_check_script(actors, A, n_scripts, B, a.with_slab);
     if (rc) return rc;
     rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs || hist_slab);
     if (rc) return rc;
     if (hist_slab && A == 0) return fail(MPC_E_ARG, "hist_slab is given but A == 0");
-    const ScriptedLoop a = {"traffic", B, 0, 0, INFINITY, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
-                            max_steps, s_stop, quant, extra, MPC_TR_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
-                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, nullptr, n_steps, step_ms,
-                            nullptr, 0, nullptr, nullptr, nullptr};
+    a.B = B; a.x_init = x_init; a.max_steps = max_steps; a.s_stop = s_stop;
+    a.actors = actors; a.A = A; a.n_scripts = n_scripts;
+    a.quant = quant; a.extra = extra; a.n_hist = n_hist; a.hist_egos = hist_egos; a.hist_x = hist_x; a.hist_u = hist_u;
+    a.hist_car_s = hist_car_s; a.hist_tl = hist_tl; a.hist_status = hist_status; a.hist_nobs = hist_nobs;
+    a.hist_slab = hist_slab; a.n_steps = n_steps; a.step_ms = step_ms;
     return scripted_loop(c, a);
 }
 
@@ -1073,48 +1011,47 @@ extern "C" int mpc_closed_loop_convoy(mpc_ctx* c, int B, int W, int K, double le
     if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
     int rc = cl_check_world(B, W, K, A, lead_range);
     if (rc) return rc;
-    bool with_slab = K > 0 && W > 1;
-    rc = cl_check_script(actors, A, n_scripts, B, with_slab);
+    ScriptedLoop a;
+    a.label = "convoy";
+    a.with_slab = K > 0 && W > 1;
+    rc = cl_check_script(actors, A, n_scripts, B, a.with_slab);
     if (rc) return rc;
     rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_car_s || hist_tl || hist_status || hist_nobs ||
                                              hist_slab || hist_lead);
     if (rc) return rc;
     if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
     if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
-    const ScriptedLoop a = {"convoy", B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, false, nullptr, 0, 0, 0,
-                            max_steps, s_stop, quant, extra, MPC_CV_NX, n_hist, hist_egos, hist_x, hist_u, nullptr,
-                            nullptr, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms,
-                            nullptr, 0, nullptr, nullptr, nullptr};
+    a.B = B; a.x_init = x_init; a.max_steps = max_steps; a.s_stop = s_stop;
+    a.actors = actors; a.A = A; a.n_scripts = n_scripts;
+    a.worlds = true; a.W = W; a.K = K; a.lead_range = lead_range;
+    a.quant = quant; a.extra = extra; a.n_hist = n_hist; a.hist_egos = hist_egos; a.hist_x = hist_x; a.hist_u = hist_u;
+    a.hist_car_s = hist_car_s; a.hist_tl = hist_tl; a.hist_status = hist_status; a.hist_nobs = hist_nobs;
+    a.hist_slab = hist_slab; a.hist_lead = hist_lead; a.n_steps = n_steps; a.step_ms = step_ms;
     return scripted_loop(c, a);
 }
 
-// mpc_closed_loop_noisy and mpc_closed_loop_traced (include/mpcqp.h) behind one argument check: the noisy entry is
-// the traced one with no trace output.  noise == NULL runs the same kernels on an all-zero shared struct
-static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
-                       const mpc_actor* actors, int A, int n_scripts, const mpc_noise* noise, int n_noise,
-                       unsigned long long seed, long long ego_offset, int max_steps, double s_stop, double* quant,
-                       double* extra, int n_hist, const int* hist_egos, double* hist_x, double* hist_u, double* hist_ua,
-                       double* hist_xm, double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
-                       double* hist_slab, int* hist_lead, int* n_steps, double* step_ms, const int* lookahead,
-                       int n_look, double* gapq, double* hist_pred, double* hist_plan, const mpc_warm* warm = nullptr,
-                       double* warmq = nullptr, double* hist_ubar = nullptr) {
+// mpc_closed_loop_noisy, _traced and _warm (include/mpcqp.h) behind one argument check: each fills the request with
+// the arguments it has (the noisy entry has no trace output, the traced one no warm start), this sets what follows
+// from them.  noise == NULL runs the same kernels on an all-zero shared struct
+static int noisy_entry(mpc_ctx* c, ScriptedLoop& a) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0 || max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
-    int rc = cl_check_world(B, W, K, A, lead_range);
+    if (a.B < 0 || a.max_steps < 1) return fail(MPC_E_ARG, "B < 0 or max_steps < 1");
+    int rc = cl_check_world(a.B, a.W, a.K, a.A, a.lead_range);
     if (rc) return rc;
-    bool with_slab = K > 0 && W > 1;
-    rc = cl_check_script(actors, A, n_scripts, B, with_slab);
+    a.worlds = a.noisy = true;
+    a.with_slab = a.K > 0 && a.W > 1;
+    rc = cl_check_script(a.actors, a.A, a.n_scripts, a.B, a.with_slab);
     if (rc) return rc;
-    if (noise ? !(n_noise == 1 || n_noise == B) : n_noise != 0)
+    if (a.noise ? !(a.n_noise == 1 || a.n_noise == a.B) : a.n_noise != 0)
         return fail(MPC_E_ARG, "n_noise must be B (a struct per ego), 1 (shared) or 0 with noise NULL");
-    if (ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
-    rc = cl_check_outputs(quant, n_hist, hist_x || hist_u || hist_ua || hist_xm || hist_car_s || hist_tl || hist_status ||
-                                             hist_nobs || hist_slab || hist_lead || hist_pred || hist_plan ||
-                                             hist_ubar);
+    if (a.ego_offset < 0) return fail(MPC_E_ARG, "ego_offset < 0");
+    rc = cl_check_outputs(a.quant, a.n_hist, a.hist_x || a.hist_u || a.hist_ua || a.hist_xm || a.hist_car_s || a.hist_tl ||
+                                                 a.hist_status || a.hist_nobs || a.hist_slab || a.hist_lead ||
+                                                 a.hist_pred || a.hist_plan || a.hist_ubar);
     if (rc) return rc;
     mpc_warm wdef;
     mpc_default_warm(&wdef);
-    if (!warm) warm = &wdef;
+    const mpc_warm* warm = a.warm ? a.warm : &wdef;
     if (warm->mode != MPC_WARM_REFERENCE && warm->mode != MPC_WARM_CARRY)
         return fail(MPC_E_ARG, "warm.mode is neither MPC_WARM_REFERENCE nor MPC_WARM_CARRY");
     if (warm->tail != MPC_WTAIL_REFERENCE && warm->tail != MPC_WTAIL_HOLD)
@@ -1124,29 +1061,21 @@ static int noisy_entry(const char* label, mpc_ctx* c, int B, int W, int K, doubl
     if (warm->mode == MPC_WARM_CARRY && c->p.sqp_iters == 0)
         return fail(MPC_E_ARG, "MPC_WARM_CARRY needs sqp_iters >= 1 (sqp_iters == 0 returns ubar itself)");
     // the reference warm start with no warm output: the solver computes it for itself, the traced entry's kernels
-    const bool warm_on = warm->mode == MPC_WARM_CARRY || warmq || hist_ubar;
-    if (n_look < 0 || n_look > MPC_MAX_LOOK) return fail(MPC_E_ARG, "n_look out of range [0, 4]");
-    if (n_look > 0 && !lookahead) return fail(MPC_E_ARG, "lookahead is NULL but n_look > 0");
-    if (n_look > 0 ? !gapq : gapq != nullptr)
+    a.warm = warm->mode == MPC_WARM_CARRY || a.warmq || a.hist_ubar ? warm : nullptr;
+    if (a.n_look < 0 || a.n_look > MPC_MAX_LOOK) return fail(MPC_E_ARG, "n_look out of range [0, 4]");
+    if (a.n_look > 0 && !a.lookahead) return fail(MPC_E_ARG, "lookahead is NULL but n_look > 0");
+    if (a.n_look > 0 ? !a.gapq : a.gapq != nullptr)
         return fail(MPC_E_ARG, "gapq is required with n_look > 0 and must be NULL with n_look == 0");
-    for (int i = 0; i < n_look; ++i) {
-        if (lookahead[i] < 1 || lookahead[i] > c->p.N) return fail(MPC_E_ARG, "a lookahead is outside [1, N]");
+    for (int i = 0; i < a.n_look; ++i) {
+        if (a.lookahead[i] < 1 || a.lookahead[i] > c->p.N) return fail(MPC_E_ARG, "a lookahead is outside [1, N]");
         for (int k = 0; k < i; ++k)
-            if (lookahead[k] == lookahead[i]) return fail(MPC_E_ARG, "a lookahead is repeated");
+            if (a.lookahead[k] == a.lookahead[i]) return fail(MPC_E_ARG, "a lookahead is repeated");
     }
-    if (hist_slab && A + K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
-    if (hist_lead && K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
-    for (size_t k = 0; k < (size_t)n_noise * NZ_NSIG; ++k)       // mpc_noise is NZ_NSIG doubles, no padding
-        if (!(reinterpret_cast<const double*>(noise)[k] >= 0.0))
+    if (a.hist_slab && a.A + a.K == 0) return fail(MPC_E_ARG, "hist_slab is given but A + K == 0");
+    if (a.hist_lead && a.K == 0) return fail(MPC_E_ARG, "hist_lead is given but K == 0");
+    for (size_t k = 0; k < (size_t)a.n_noise * NZ_NSIG; ++k)     // mpc_noise is NZ_NSIG doubles, no padding
+        if (!(reinterpret_cast<const double*>(a.noise)[k] >= 0.0))
             return fail(MPC_E_ARG, "a noise sigma is negative or NaN");
-    mpc_noise zero;
-    mpc_default_noise(&zero);
-    if (!noise) noise = &zero;
-    const ScriptedLoop a = {label, B, W, K, lead_range, x_init, actors, A, n_scripts, with_slab, true, noise, n_noise,
-                            seed, ego_offset, max_steps, s_stop, quant, extra, MPC_NZ_NX, n_hist, hist_egos, hist_x,
-                            hist_u, hist_ua, hist_xm, hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead,
-                            n_steps, step_ms, lookahead, n_look, gapq, hist_pred, hist_plan, warm_on ? warm : nullptr,
-                            warmq, hist_ubar};
     return scripted_loop(c, a);
 }
 
@@ -1157,10 +1086,16 @@ extern "C" int mpc_closed_loop_noisy(mpc_ctx* c, int B, int W, int K, double lea
                                      double* hist_x, double* hist_u, double* hist_ua, double* hist_xm,
                                      double* hist_car_s, int* hist_tl, int* hist_status, int* hist_nobs,
                                      double* hist_slab, int* hist_lead, int* n_steps, double* step_ms) {
-    return noisy_entry("noisy-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed, ego_offset,
-                       max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
-                       hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, nullptr, 0, nullptr,
-                       nullptr, nullptr);
+    ScriptedLoop a;
+    a.label = "noisy-loop";
+    a.B = B; a.x_init = x_init; a.max_steps = max_steps; a.s_stop = s_stop;
+    a.actors = actors; a.A = A; a.n_scripts = n_scripts;
+    a.W = W; a.K = K; a.lead_range = lead_range;
+    a.noise = noise; a.n_noise = n_noise; a.seed = seed; a.ego_offset = ego_offset;
+    a.quant = quant; a.extra = extra; a.n_hist = n_hist; a.hist_egos = hist_egos; a.hist_x = hist_x; a.hist_u = hist_u;
+    a.hist_ua = hist_ua; a.hist_xm = hist_xm; a.hist_car_s = hist_car_s; a.hist_tl = hist_tl; a.hist_status = hist_status;
+    a.hist_nobs = hist_nobs; a.hist_slab = hist_slab; a.hist_lead = hist_lead; a.n_steps = n_steps; a.step_ms = step_ms;
+    return noisy_entry(c, a);
 }
 
 extern "C" int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double lead_range, const double* x_init,
@@ -1172,10 +1107,17 @@ extern "C" int mpc_closed_loop_traced(mpc_ctx* c, int B, int W, int K, double le
                                       double* hist_slab, int* hist_lead, int* n_steps, double* step_ms,
                                       const int* lookahead, int n_look, double* gapq, double* hist_pred,
                                       double* hist_plan) {
-    return noisy_entry("traced-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed,
-                       ego_offset, max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm,
-                       hist_car_s, hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, lookahead,
-                       n_look, gapq, hist_pred, hist_plan);
+    ScriptedLoop a;
+    a.label = "traced-loop";
+    a.B = B; a.x_init = x_init; a.max_steps = max_steps; a.s_stop = s_stop;
+    a.actors = actors; a.A = A; a.n_scripts = n_scripts;
+    a.W = W; a.K = K; a.lead_range = lead_range;
+    a.noise = noise; a.n_noise = n_noise; a.seed = seed; a.ego_offset = ego_offset;
+    a.quant = quant; a.extra = extra; a.n_hist = n_hist; a.hist_egos = hist_egos; a.hist_x = hist_x; a.hist_u = hist_u;
+    a.hist_ua = hist_ua; a.hist_xm = hist_xm; a.hist_car_s = hist_car_s; a.hist_tl = hist_tl; a.hist_status = hist_status;
+    a.hist_nobs = hist_nobs; a.hist_slab = hist_slab; a.hist_lead = hist_lead; a.n_steps = n_steps; a.step_ms = step_ms;
+    a.lookahead = lookahead; a.n_look = n_look; a.gapq = gapq; a.hist_pred = hist_pred; a.hist_plan = hist_plan;
+    return noisy_entry(c, a);
 }
 
 // mpc_closed_loop_traced whose solver may be handed the ego's previous plan as its ubar (include/mpcqp.h)
@@ -1187,10 +1129,18 @@ extern "C" int mpc_closed_loop_warm(mpc_ctx* c, int B, int W, int K, double lead
                                     int* hist_status, int* hist_nobs, double* hist_slab, int* hist_lead, int* n_steps,
                                     double* step_ms, const int* lookahead, int n_look, double* gapq, double* hist_pred,
                                     double* hist_plan, const mpc_warm* warm, double* warmq, double* hist_ubar) {
-    return noisy_entry("warm-loop", c, B, W, K, lead_range, x_init, actors, A, n_scripts, noise, n_noise, seed, ego_offset,
-                       max_steps, s_stop, quant, extra, n_hist, hist_egos, hist_x, hist_u, hist_ua, hist_xm, hist_car_s,
-                       hist_tl, hist_status, hist_nobs, hist_slab, hist_lead, n_steps, step_ms, lookahead, n_look, gapq,
-                       hist_pred, hist_plan, warm, warmq, hist_ubar);
+    ScriptedLoop a;
+    a.label = "warm-loop";
+    a.B = B; a.x_init = x_init; a.max_steps = max_steps; a.s_stop = s_stop;
+    a.actors = actors; a.A = A; a.n_scripts = n_scripts;
+    a.W = W; a.K = K; a.lead_range = lead_range;
+    a.noise = noise; a.n_noise = n_noise; a.seed = seed; a.ego_offset = ego_offset;
+    a.quant = quant; a.extra = extra; a.n_hist = n_hist; a.hist_egos = hist_egos; a.hist_x = hist_x; a.hist_u = hist_u;
+    a.hist_ua = hist_ua; a.hist_xm = hist_xm; a.hist_car_s = hist_car_s; a.hist_tl = hist_tl; a.hist_status = hist_status;
+    a.hist_nobs = hist_nobs; a.hist_slab = hist_slab; a.hist_lead = hist_lead; a.n_steps = n_steps; a.step_ms = step_ms;
+    a.lookahead = lookahead; a.n_look = n_look; a.gapq = gapq; a.hist_pred = hist_pred; a.hist_plan = hist_plan;
+    a.warm = warm; a.warmq = warmq; a.hist_ubar = hist_ubar;
+    return noisy_entry(c, a);
 }
 
 // the draws of mpc_closed_loop_noisy on their own (include/mpcqp.h), on the context's backend

@@ -302,6 +302,15 @@ def _check(rc, what):
         raise MpcError(f"{what} failed (rc={rc}): {last_error()}")
 
 
+def _s_stop(s_stop, s_max):
+    """Where the closed loops end: s_stop, by default s_max - 1 (trajectory_tracking.py:395)."""
+    if s_stop is None:
+        if s_max is None:
+            raise ValueError("give s_stop or s_max")
+        s_stop = s_max - 1.0
+    return s_stop
+
+
 def _script_array(scripts):
     """(mpc_actor pointer, A, n_scripts) of closed_loop_traffic's `scripts` argument: None, one sequence of
     MpcActor (shared), or a sequence of such sequences of one length."""
@@ -420,10 +429,7 @@ class Solver:
         hist_tl [B,max_steps], hist_status [B,max_steps], n_steps [B], step_ms [max_steps])."""
         x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
         B = x_init.shape[0]
-        if s_stop is None:
-            if s_max is None:
-                raise ValueError("give s_stop or s_max")
-            s_stop = s_max - 1.0
+        s_stop = _s_stop(s_stop, s_max)
         hx = np.empty((B, max_steps + 1, 5)); hu = np.empty((B, max_steps, 2)); ho = np.empty((B, max_steps))
         ht = np.empty((B, max_steps), np.int32); hs = np.empty((B, max_steps), np.int32)
         ns = np.empty(B, np.int32); sm = np.empty(max_steps)
@@ -442,10 +448,7 @@ class Solver:
         hist_obs_s, hist_tl, hist_status [n_hist,max_steps]: row k belongs to ego hist_egos[k])."""
         x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
         B = x_init.shape[0]
-        if s_stop is None:
-            if s_max is None:
-                raise ValueError("give s_stop or s_max")
-            s_stop = s_max - 1.0
+        s_stop = _s_stop(s_stop, s_max)
         if scenarios is None:
             fsm, n_fsm = None, 0
         elif isinstance(scenarios, MpcFsm):
@@ -484,29 +487,8 @@ class Solver:
         Returns closed_loop_sweep's dict with hist_car_s in place of hist_obs_s and hist_tl a bitmask (bit a:
         actor a is a GREEN light), plus extra [B,3] (columns TRX_FIELDS), hist_nobs [n_hist,max_steps] and
         hist_slab [n_hist,max_steps,A,2] (NaN past n_obs)."""
-        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
-        B = x_init.shape[0]
-        if s_stop is None:
-            if s_max is None:
-                raise ValueError("give s_stop or s_max")
-            s_stop = s_max - 1.0
-        arr, A, n_scripts = _script_array(scripts)
-        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
-        nh = he.size
-        quant = np.empty((B, CL_NQ)); extra = np.empty((B, TR_NX))
-        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
-        hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
-        ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
-        hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, A, 2))
-        g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
-        gi = (lambda a: _pi(a) if nh else None)
-        _check(lib().mpc_closed_loop_traffic(self.h, B, _p(x_init), arr, int(A), int(n_scripts), int(max_steps),
-                                             float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(hc),
-                                             gi(ht), gi(hs), gi(hn), g(hl) if A else None, _pi(ns), _p(sm)),
-               "mpc_closed_loop_traffic")
-        quant[:, 0] += lo
-        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
-                    hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl)
+        return self._closed_loop_scripted("mpc_closed_loop_traffic", TR_NX, x_init, scripts, max_steps, s_stop, s_max,
+                                          hist_egos, lo)
 
     def closed_loop_convoy(self, x_init, W, K, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
                            s_max=None, hist_egos=(), lo=0):
@@ -517,33 +499,8 @@ class Solver:
         Returns closed_loop_traffic's dict with extra [B,6] (columns CVX_FIELDS; min_lead_ego is a batch index,
         the shard offset `lo` is added to it), hist_slab [n_hist,max_steps,A+K,2] and hist_lead
         [n_hist,max_steps,K] (the leaders' batch indices of this call in slab order, -1 past them)."""
-        x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
-        B = x_init.shape[0]
-        if s_stop is None:
-            if s_max is None:
-                raise ValueError("give s_stop or s_max")
-            s_stop = s_max - 1.0
-        arr, A, n_scripts = _script_array(scripts)
-        K = int(K)
-        he = np.ascontiguousarray(hist_egos, np.int32).ravel()
-        nh = he.size
-        quant = np.empty((B, CL_NQ)); extra = np.empty((B, CV_NX))
-        ns = np.empty(B, np.int32); sm = np.empty(max_steps)
-        hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
-        ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
-        hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, max(A + K, 0), 2))
-        hd = np.empty((nh, max_steps, max(K, 0)), np.int32)
-        g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
-        gi = (lambda a: _pi(a) if nh else None)
-        _check(lib().mpc_closed_loop_convoy(self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A),
-                                            int(n_scripts), int(max_steps), float(s_stop), _p(quant), _p(extra), nh,
-                                            gi(he), g(hx), g(hu), g(hc), gi(ht), gi(hs), gi(hn),
-                                            g(hl) if A + K > 0 else None, gi(hd) if K > 0 else None, _pi(ns),
-                                            _p(sm)), "mpc_closed_loop_convoy")
-        quant[:, 0] += lo
-        extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
-        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
-                    hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl, hist_lead=hd)
+        return self._closed_loop_scripted("mpc_closed_loop_convoy", CV_NX, x_init, scripts, max_steps, s_stop, s_max,
+                                          hist_egos, lo, world=(W, K, lead_range))
 
     def closed_loop_noisy(self, x_init, W=1, K=0, lead_range=np.inf, scripts=None, max_steps=2000, s_stop=None,
                           s_max=None, hist_egos=(), noise=None, seed=0, lo=0):
@@ -584,72 +541,85 @@ class Solver:
                            lo, trace, warm=None):
         """closed_loop_noisy (trace None), closed_loop_traced (trace = (lookahead, preds, plans)) or closed_loop_warm
         (warm = (MpcWarm or None, warmq, ubars) as well)."""
+        entry = "mpc_closed_loop_" + ("noisy" if trace is None else "traced" if warm is None else "warm")
+        return self._closed_loop_scripted(entry, NZ_NX, x_init, scripts, max_steps, s_stop, s_max, hist_egos, lo,
+                                          world=(W, K, lead_range), noise=(noise, seed), trace=trace, warm=warm)
+
+    def _closed_loop_scripted(self, entry, nx, x_init, scripts, max_steps, s_stop, s_max, hist_egos, lo, world=None,
+                              noise=None, trace=None, warm=None):
+        """The body of closed_loop_traffic (world None), closed_loop_convoy (world = (W, K, lead_range)) and
+        _closed_loop_noisy (noise = (noise, seed) as well; trace and warm as there): allocates the outputs (extra is
+        [B,nx]), calls the library's `entry` and adds `lo` to the index columns."""
         x_init = np.ascontiguousarray(x_init, np.float64).reshape(-1, 5)
         B = x_init.shape[0]
-        if s_stop is None:
-            if s_max is None:
-                raise ValueError("give s_stop or s_max")
-            s_stop = s_max - 1.0
+        s_stop = _s_stop(s_stop, s_max)
         arr, A, n_scripts = _script_array(scripts)
-        if noise is None:
-            nz, n_noise = None, 0
-        elif isinstance(noise, MpcNoise):
-            nz, n_noise = C.pointer(noise), 1
-        else:
-            n_noise = len(noise)
-            if isinstance(noise, C.Array):
-                buf = noise
-            else:
-                buf = (MpcNoise * max(n_noise, 1))()
-                for i, z in enumerate(noise):
-                    C.memmove(C.byref(buf, i * C.sizeof(MpcNoise)), C.byref(z), C.sizeof(MpcNoise))
-            nz = C.cast(buf, C.POINTER(MpcNoise))
+        W, K, lead_range = world or (1, 0, np.inf)
         K = int(K)
+        noisy = noise is not None
+        if noisy:
+            noise, seed = noise
+            if noise is None:
+                nz, n_noise = None, 0
+            elif isinstance(noise, MpcNoise):
+                nz, n_noise = C.pointer(noise), 1
+            else:
+                n_noise = len(noise)
+                if isinstance(noise, C.Array):
+                    buf = noise
+                else:
+                    buf = (MpcNoise * max(n_noise, 1))()
+                    for i, z in enumerate(noise):
+                        C.memmove(C.byref(buf, i * C.sizeof(MpcNoise)), C.byref(z), C.sizeof(MpcNoise))
+                nz = C.cast(buf, C.POINTER(MpcNoise))
         he = np.ascontiguousarray(hist_egos, np.int32).ravel()
         nh = he.size
-        quant = np.empty((B, CL_NQ)); extra = np.empty((B, NZ_NX))
+        quant = np.empty((B, CL_NQ)); extra = np.empty((B, nx))
         ns = np.empty(B, np.int32); sm = np.empty(max_steps)
         hx = np.empty((nh, max_steps + 1, 5)); hu = np.empty((nh, max_steps, 2)); hc = np.empty((nh, max_steps))
-        ha = np.empty((nh, max_steps, 2)); hm = np.empty((nh, max_steps, 5))
         ht = np.empty((nh, max_steps), np.int32); hs = np.empty((nh, max_steps), np.int32)
         hn = np.empty((nh, max_steps), np.int32); hl = np.empty((nh, max_steps, max(A + K, 0), 2))
-        hd = np.empty((nh, max_steps, max(K, 0)), np.int32)
         g = (lambda a: _p(a) if nh else None)          # no history pointer without a history ego
         gi = (lambda a: _pi(a) if nh else None)
-        args = (self.h, B, int(W), K, float(lead_range), _p(x_init), arr, int(A), int(n_scripts), nz, int(n_noise),
-                int(seed), int(lo), int(max_steps), float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu), g(ha),
-                g(hm), g(hc), gi(ht), gi(hs), gi(hn), g(hl) if A + K > 0 else None, gi(hd) if K > 0 else None, _pi(ns),
-                _p(sm))
-        more = {}
-        if trace is None:
-            _check(lib().mpc_closed_loop_noisy(*args), "mpc_closed_loop_noisy")
-        else:
+        out = dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu)
+        args = (self.h, B) + ((int(W), K, float(lead_range)) if world else ())     # the entry's order from here on
+        args += (_p(x_init), arr, int(A), int(n_scripts))
+        if noisy:
+            args += (nz, int(n_noise), int(seed), int(lo))
+            out.update(hist_ua=np.empty((nh, max_steps, 2)), hist_xm=np.empty((nh, max_steps, 5)))
+        args += (int(max_steps), float(s_stop), _p(quant), _p(extra), nh, gi(he), g(hx), g(hu))
+        if noisy:
+            args += (g(out["hist_ua"]), g(out["hist_xm"]))
+        args += (g(hc), gi(ht), gi(hs), gi(hn), g(hl) if A + K > 0 else None)
+        out.update(hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl)
+        if world:
+            out["hist_lead"] = np.empty((nh, max_steps, max(K, 0)), np.int32)
+            args += (gi(out["hist_lead"]) if K > 0 else None,)
+        args += (_pi(ns), _p(sm))
+        if trace is not None:
             lookahead, preds, plans = trace
             N = self.params.N
             look = np.ascontiguousarray(lookahead, np.int32).ravel()
             if look.size:
-                more["gapq"] = np.empty((B, look.size, TG_NQ))
+                out["gapq"] = np.empty((B, look.size, TG_NQ))
             if preds:
-                more["hist_pred"] = np.empty((nh, max_steps, N + 1, 5))
+                out["hist_pred"] = np.empty((nh, max_steps, N + 1, 5))
             if plans:
-                more["hist_plan"] = np.empty((nh, max_steps, N, 2))
-            targs = args + (_pi(look) if look.size else None, int(look.size), _p(more.get("gapq")),
-                            g(more.get("hist_pred")), g(more.get("hist_plan")))
-            if warm is None:
-                _check(lib().mpc_closed_loop_traced(*targs), "mpc_closed_loop_traced")
-            else:
-                how, want_q, want_ubar = warm
-                if want_q:
-                    more["warmq"] = np.empty((B, WQ_NQ))
-                if want_ubar:
-                    more["hist_ubar"] = np.empty((nh, max_steps, N, 2))
-                _check(lib().mpc_closed_loop_warm(*targs, None if how is None else C.byref(how), _p(more.get("warmq")),
-                                                  g(more.get("hist_ubar"))), "mpc_closed_loop_warm")
+                out["hist_plan"] = np.empty((nh, max_steps, N, 2))
+            args += (_pi(look) if look.size else None, int(look.size), _p(out.get("gapq")), g(out.get("hist_pred")),
+                     g(out.get("hist_plan")))
+        if warm is not None:
+            how, want_q, want_ubar = warm
+            if want_q:
+                out["warmq"] = np.empty((B, WQ_NQ))
+            if want_ubar:
+                out["hist_ubar"] = np.empty((nh, max_steps, N, 2))
+            args += (None if how is None else C.byref(how), _p(out.get("warmq")), g(out.get("hist_ubar")))
+        _check(getattr(lib(), entry)(*args), entry)
         quant[:, 0] += lo
-        extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
-        return dict(quant=quant, extra=extra, n_steps=ns, step_ms=sm, hist_egos=he, hist_x=hx, hist_u=hu,
-                    hist_ua=ha, hist_xm=hm, hist_car_s=hc, hist_tl=ht, hist_status=hs, hist_nobs=hn, hist_slab=hl,
-                    hist_lead=hd, **more)
+        if world:
+            extra[:, CVX_MIN_LEAD_EGO] += np.where(extra[:, CVX_MIN_LEAD_EGO] >= 0, lo, 0)
+        return out
 
     def noise_draw(self, seed, ego, step, channel):
         """mpc_noise_draw on this context's backend: the Philox words [n,4] (uint32) and the variates z [n] of

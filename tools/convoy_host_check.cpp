@@ -1,10 +1,10 @@
-// Stand-alone sanitizer check of the host backend's convoy loop (csrc/cpu_backend.h: closed_loop_convoy), built
-// and run by tools/convoy_host_check.py with -fsanitize=address,undefined:
+// Stand-alone sanitizer check of the host backend's convoy loop (csrc/cpu_backend.h: closed_loop_scripted with
+// worlds), built and run by tools/convoy_host_check.py with -fsanitize=address,undefined:
 //   convoy_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
 // Runs on 3 worker threads, N = 5, 12 egos: (1) worlds of one ego with K = 3 and worlds of four with K = 0, each
-// ego with a script of a car and a light, against closed_loop_traffic: every quantity column but the step time,
-// extras 0..2 and n_steps must be equal byte for byte; (2) three worlds of four (a tie pair, an ego that starts
-// past s_stop, a leader that leaves mid-run) with K = 3, K = 14 beside the two actors (A + K = 16), a finite
+// ego with a script of a car and a light, against the traffic loop (no worlds): every quantity column but the step
+// time, extras 0..2 and n_steps must be equal byte for byte; (2) three worlds of four (a tie pair, an ego that
+// starts past s_stop, a leader that leaves mid-run) with K = 3, K = 14 beside the two actors (A + K = 16), a finite
 // lead_range, two selected egos, no history and no extras, and no script: every leader recorded must belong to
 // the ego's world and the leader counts must stay within K.
 // Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
@@ -89,12 +89,18 @@ int main(int argc, char** argv) {
         std::vector<int> ht((size_t)nh * ns), hs((size_t)nh * ns), hn((size_t)nh * ns), hd((size_t)nh * ns * K);
         bool with_slab = K > 0 && Wc > 1;
         for (const mpc_actor& a : sc) with_slab = with_slab || a.kind != MPC_ACTOR_NONE;
-        const int rc = be.closed_loop_convoy(
-            p, B, Wc, K, range, x0.data(), sc.empty() ? nullptr : sc.data(), Ac, n_scripts, with_slab, ms, s_stop,
-            quant.data(), extras ? extra.data() : nullptr, nh, slot.data(), nh ? hx.data() : nullptr,
-            nh ? hu.data() : nullptr, nh ? hc.data() : nullptr, nh ? ht.data() : nullptr, nh ? hs.data() : nullptr,
-            nh ? hn.data() : nullptr, nh && AK ? hl.data() : nullptr, nh && K ? hd.data() : nullptr,
-            extras ? n_steps.data() : nullptr, extras ? step_ms.data() : nullptr);
+        ScriptedLoop a;
+        a.B = B; a.x_init = x0.data(); a.max_steps = ms; a.s_stop = s_stop;
+        a.actors = sc.empty() ? nullptr : sc.data(); a.A = Ac; a.n_scripts = n_scripts; a.with_slab = with_slab;
+        a.worlds = true; a.W = Wc; a.K = K; a.lead_range = range;
+        a.quant = quant.data(); a.n_hist = nh;
+        if (extras) { a.extra = extra.data(); a.n_steps = n_steps.data(); a.step_ms = step_ms.data(); }
+        if (nh) {
+            a.hist_x = hx.data(); a.hist_u = hu.data(); a.hist_car_s = hc.data(); a.hist_tl = ht.data();
+            a.hist_status = hs.data(); a.hist_nobs = hn.data(); a.hist_slab = AK ? hl.data() : nullptr;
+            a.hist_lead = K ? hd.data() : nullptr;
+        }
+        const int rc = be.closed_loop_scripted(p, a, slot.data());
         if (rc != MPC_SUCCESS) ++bad;
         for (int k = 0; k < nh; ++k)                       // recorded leaders: this ego's world, counts within K
             for (size_t t = 0; t < ns; ++t) {
@@ -120,10 +126,11 @@ int main(int argc, char** argv) {
     // (1) the anchor: the traffic loop on the same inputs
     std::vector<double> tq((size_t)B * MPC_CL_NQ), tx((size_t)B * MPC_TR_NX), step_ms(ns);
     std::vector<int> tn(B), slot(B, -1);
-    if (be.closed_loop_traffic(p, B, x0.data(), scripts.data(), A, B, true, ms, s_stop, tq.data(), tx.data(), 0,
-                               slot.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tn.data(),
-                               step_ms.data()) != MPC_SUCCESS)
-        ++bad;
+    ScriptedLoop t;
+    t.B = B; t.x_init = x0.data(); t.max_steps = ms; t.s_stop = s_stop;
+    t.actors = scripts.data(); t.A = A; t.n_scripts = B; t.with_slab = true;
+    t.quant = tq.data(); t.extra = tx.data(); t.n_steps = tn.data(); t.step_ms = step_ms.data();
+    if (be.closed_loop_scripted(p, t, slot.data()) != MPC_SUCCESS) ++bad;
     std::vector<double> q, ex;
     std::vector<int> n;
     const int anchors[2][2] = {{1, 3}, {4, 0}};

@@ -1,19 +1,23 @@
-// Stand-alone sanitizer check of the host backend's noisy loop (csrc/cpu_backend.h: closed_loop_noisy, noise_draw),
-// built and run by tools/noise_host_check.py with -fsanitize=address,undefined:
+// Stand-alone sanitizer check of the host backend's noisy loop (csrc/cpu_backend.h: closed_loop_scripted with noise,
+// traces and warm starts; noise_draw), built and run by tools/noise_host_check.py with -fsanitize=address,undefined:
 //   noise_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
 // Runs on 3 worker threads, N = 5, 12 egos in worlds of 4, each ego with a script of a car and a light:
 // (1) the known answer of Philox4x32-10 for the all-zero counter and key, and the variate's bound over 4096 draws;
-// (2) an all-zero shared struct and all-zero per-ego structs against closed_loop_convoy: every quantity column but
+// (2) an all-zero shared struct and all-zero per-ego structs against the convoy loop: every quantity column but
 //     the step time, extras 0..5 and n_steps equal byte for byte, the applied extremes equal to the commanded ones
 //     and no clamped step;
 // (3) noisy runs over every argument variant (shared and per-ego structs, K = 14 beside the two actors, a finite
 //     lead_range, two selected egos with every history, no history and no extras, no script, a large ego_offset,
 //     an actuator that clamps): recorded leaders belong to the ego's world, the applied controls stay inside the
-//     bounds, hist_xm and hist_ua are written for exactly the steps that ran, and a run repeated is identical.
+//     bounds, hist_xm and hist_ua are written for exactly the steps that ran, and a run repeated is identical;
+// (4) a traced run (lookahead 1, 3, N; hist_pred and hist_plan of the two selected egos) and the same run with the
+//     plans carried (MPC_WARM_CARRY, MPC_WTAIL_HOLD, MPC_WRESET_NOBS; warmq, hist_ubar): gapq and warmq are written
+//     for every ego, hist_plan and hist_ubar are numbers for exactly the steps that ran.
 // Exit 0: clean and equal; 1: a mismatch; 2: bad input.  The sanitizers abort on their own findings.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "../include/mpcqp.h"
@@ -118,6 +122,7 @@ int main(int argc, char** argv) {
         std::vector<double> quant, extra, hx, hu, ha, hm, hl;
         std::vector<int> n_steps, hd, hn;
     };
+    std::function<void(ScriptedLoop&)> more = [](ScriptedLoop&) {};     // (4) adds its trace and warm fields here
     auto noisy = [&](int Wc, int K, double range, const std::vector<mpc_actor>& sc, int Ac, int n_scripts,
                      const std::vector<mpc_noise>& nz, unsigned long long seed, long long offset,
                      const std::vector<int>& egos, bool extras, Out& o) {
@@ -133,15 +138,22 @@ int main(int argc, char** argv) {
         o.hd.assign((size_t)nh * ns * K, 0); o.hn.assign((size_t)nh * ns, 0);
         std::vector<double> hc((size_t)nh * ns), step_ms(ns);
         std::vector<int> ht((size_t)nh * ns), hs((size_t)nh * ns);
-        bool with_slab = K > 0 && Wc > 1;
-        for (const mpc_actor& a : sc) with_slab = with_slab || a.kind != MPC_ACTOR_NONE;
-        const int rc = be.closed_loop_noisy(
-            p, B, Wc, K, range, x0.data(), sc.empty() ? nullptr : sc.data(), Ac, n_scripts, with_slab, nz.data(),
-            (int)nz.size(), seed, offset, ms, s_stop, o.quant.data(), extras ? o.extra.data() : nullptr, nh,
-            slot.data(), nh ? o.hx.data() : nullptr, nh ? o.hu.data() : nullptr, nh ? o.ha.data() : nullptr,
-            nh ? o.hm.data() : nullptr, nh ? hc.data() : nullptr, nh ? ht.data() : nullptr, nh ? hs.data() : nullptr,
-            nh ? o.hn.data() : nullptr, nh && AK ? o.hl.data() : nullptr, nh && K ? o.hd.data() : nullptr,
-            o.n_steps.data(), extras ? step_ms.data() : nullptr);
+        ScriptedLoop a;
+        a.B = B; a.x_init = x0.data(); a.max_steps = ms; a.s_stop = s_stop;
+        a.actors = sc.empty() ? nullptr : sc.data(); a.A = Ac; a.n_scripts = n_scripts;
+        a.with_slab = K > 0 && Wc > 1;
+        for (const mpc_actor& act : sc) a.with_slab = a.with_slab || act.kind != MPC_ACTOR_NONE;
+        a.worlds = true; a.W = Wc; a.K = K; a.lead_range = range;
+        a.noisy = true; a.noise = nz.data(); a.n_noise = (int)nz.size(); a.seed = seed; a.ego_offset = offset;
+        a.quant = o.quant.data(); a.n_hist = nh; a.n_steps = o.n_steps.data();
+        if (extras) { a.extra = o.extra.data(); a.step_ms = step_ms.data(); }
+        if (nh) {
+            a.hist_x = o.hx.data(); a.hist_u = o.hu.data(); a.hist_ua = o.ha.data(); a.hist_xm = o.hm.data();
+            a.hist_car_s = hc.data(); a.hist_tl = ht.data(); a.hist_status = hs.data(); a.hist_nobs = o.hn.data();
+            a.hist_slab = AK ? o.hl.data() : nullptr; a.hist_lead = K ? o.hd.data() : nullptr;
+        }
+        more(a);
+        const int rc = be.closed_loop_scripted(p, a, slot.data());
         if (rc != MPC_SUCCESS) ++bad;
         for (int k = 0; k < nh; ++k) {
             const int e = egos[k], n = o.n_steps[e];
@@ -181,10 +193,12 @@ int main(int argc, char** argv) {
     const int K = 3;
     std::vector<double> cq((size_t)B * MPC_CL_NQ), cx((size_t)B * MPC_CV_NX), step_ms(ns);
     std::vector<int> cn(B), slot(B, -1);
-    if (be.closed_loop_convoy(p, B, W, K, INFINITY, x0.data(), scripts.data(), A, B, true, ms, s_stop, cq.data(),
-                              cx.data(), 0, slot.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, cn.data(), step_ms.data()) != MPC_SUCCESS)
-        ++bad;
+    ScriptedLoop cv;
+    cv.B = B; cv.x_init = x0.data(); cv.max_steps = ms; cv.s_stop = s_stop;
+    cv.actors = scripts.data(); cv.A = A; cv.n_scripts = B; cv.with_slab = true;
+    cv.worlds = true; cv.W = W; cv.K = K;
+    cv.quant = cq.data(); cv.extra = cx.data(); cv.n_steps = cn.data(); cv.step_ms = step_ms.data();
+    if (be.closed_loop_scripted(p, cv, slot.data()) != MPC_SUCCESS) ++bad;
     Out o, o2;
     const std::vector<mpc_noise> shared_quiet(1, quiet()), each_quiet(B, quiet());
     for (const auto* nz : {&shared_quiet, &each_quiet}) {
@@ -227,6 +241,32 @@ int main(int argc, char** argv) {
     double clamped = 0.0;
     for (int b = 0; b < B; ++b) clamped += o.extra[(size_t)b * MPC_NZ_NX + MPC_NZX_N_CLAMPED];
     if (clamped == 0.0) ++bad;
+    // (4) the traces, then the same run with the plans carried
+    const int N = p.N, n_look = 3, look[n_look] = {1, 3, N};
+    const size_t nu = 2 * (size_t)N, nxp = 5 * ((size_t)N + 1), n2 = two.size();
+    mpc_warm carry;
+    carry.mode = MPC_WARM_CARRY; carry.tail = MPC_WTAIL_HOLD; carry.reset = MPC_WRESET_NOBS;
+    for (const mpc_warm* warm : {(const mpc_warm*)nullptr, (const mpc_warm*)&carry}) {
+        std::vector<double> gapq((size_t)B * n_look * MPC_TG_NQ, -7.0), warmq((size_t)B * MPC_WQ_NQ, -7.0);
+        std::vector<double> hpred(n2 * ns * nxp, 0.0), hplan(n2 * ns * nu, 0.0), hubar(n2 * ns * nu, 0.0);
+        more = [&](ScriptedLoop& a) {
+            a.lookahead = look; a.n_look = n_look; a.gapq = gapq.data();
+            a.hist_pred = hpred.data(); a.hist_plan = hplan.data();
+            if (warm) { a.warm = warm; a.warmq = warmq.data(); a.hist_ubar = hubar.data(); }
+        };
+        noisy(W, K, INFINITY, scripts, A, B, each, 7, 0, two, true, o);
+        for (double g : gapq) bad += g == -7.0;                // written for every ego
+        for (double w : warmq) bad += warm && w == -7.0;
+        for (size_t k = 0; k < n2; ++k)
+            for (size_t t = 0; t < ns; ++t) {                  // a number for a step that ran, NaN after
+                const bool ran = (int)t < o.n_steps[two[k]];
+                for (size_t j = 0; j < nxp; ++j) bad += std::isnan(hpred[(k * ns + t) * nxp + j]) == ran;
+                for (size_t j = 0; j < nu; ++j) {
+                    bad += std::isnan(hplan[(k * ns + t) * nu + j]) == ran;
+                    bad += warm && std::isnan(hubar[(k * ns + t) * nu + j]) == ran;
+                }
+            }
+    }
     std::printf("noise_host_check: %s\n", bad ? "MISMATCH" : "clean and equal");
     return bad ? 1 : 0;
 }

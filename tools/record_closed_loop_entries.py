@@ -1,8 +1,8 @@
-"""Records what the five closed-loop entries return on one small case set: tests/golden/closed_loop_entries.npz,
+"""Records what the seven closed-loop entries return on one small case set: tests/golden/closed_loop_entries.npz,
 the absolute pin behind tests/test_closed_loop_recorded_cpu.py and tests/test_gpu_closed_loop_recorded.py (the
 anchor tests compare one entry with the next; this file says what each of them gave when it was recorded).
 
-Only the public mpcqp.Solver API is used, so the script runs on any commit that has the five entries:
+Only the public mpcqp.Solver API is used, so the script runs on any commit that has the seven entries:
 
     python tools/record_closed_loop_entries.py --device -1      # the host section (CPU only)
     python tools/record_closed_loop_entries.py --device 0       # the device section (one GPU)
@@ -15,7 +15,9 @@ The case set (trajectory2, N = 20, the default single QP per step, 24 steps: thr
 six egos as two worlds of W = 3 with K = 2 leaders and A = 2 actors (a car and a light) per ego, ego 5 so close to
 s_stop that it leaves before the first sync (the list is compacted); per-ego scripts, scenarios and noise (every
 sigma non-zero), seed 2024, ego_offset 5, hist_egos = [4, 1] with every history array; every entry again in its
-shared form (one scenario / script / noise struct) and with B = 1."""
+shared form (one scenario / script / noise struct) and with B = 1.  The traced and warm calls are the noisy ones
+with lookahead = (1, 5, 20); the warm ones carry the plans (WARM_CARRY, WTAIL_HOLD, WRESET_NOBS) and return warmq
+and hist_ubar; hist_pred and hist_plan are kept in the per-ego forms only."""
 import argparse
 import os
 import sys
@@ -74,6 +76,17 @@ def entries(mpcqp, traj, slv):
     out["noisy_per_ego"] = slv.closed_loop_noisy(x, 3, 2, lead_range=40.0, scripts=scripts, noise=noises, **nz, **kh)
     out["noisy_shared"] = slv.closed_loop_noisy(x, 3, 2, scripts=scripts[0], noise=noises[2], **nz, **kh)
     out["noisy_b1"] = slv.closed_loop_noisy(x1, 1, 2, scripts=[scripts[1]], noise=[noises[1]], **nz, **k1)
+    tr = dict(nz, lookahead=(1, 5, 20))
+    out["traced_per_ego"] = slv.closed_loop_traced(x, 3, 2, lead_range=40.0, scripts=scripts, noise=noises,
+                                                   preds=True, plans=True, **tr, **kh)
+    out["traced_shared"] = slv.closed_loop_traced(x, 3, 2, scripts=scripts[0], noise=noises[2], **tr, **kh)
+    out["traced_b1"] = slv.closed_loop_traced(x1, 1, 2, scripts=[scripts[1]], noise=[noises[1]], **tr, **k1)
+    wm = dict(tr, warm=mpcqp.default_warm(mode=mpcqp.WARM_CARRY, tail=mpcqp.WTAIL_HOLD, reset=mpcqp.WRESET_NOBS),
+              warmq=True, ubars=True)
+    out["warm_per_ego"] = slv.closed_loop_warm(x, 3, 2, lead_range=40.0, scripts=scripts, noise=noises,
+                                               preds=True, plans=True, **wm, **kh)
+    out["warm_shared"] = slv.closed_loop_warm(x, 3, 2, scripts=scripts[0], noise=noises[2], **wm, **kh)
+    out["warm_b1"] = slv.closed_loop_warm(x1, 1, 2, scripts=[scripts[1]], noise=[noises[1]], **wm, **k1)
     return out
 
 

@@ -1,4 +1,5 @@
-// Stand-alone sanitizer check of the host backend's traffic loop (csrc/cpu_backend.h: closed_loop_traffic),
+// Stand-alone sanitizer check of the host backend's traffic loop (csrc/cpu_backend.h: closed_loop_scripted
+// without worlds or noise),
 // built and run by tools/traffic_host_check.py with -fsanitize=address,undefined:
 //   traffic_host_check <traj.bin>        traj.bin: int32 T, Tu; f64 X[T][5], U[Tu][2] (trajectory2)
 // Runs on 3 worker threads, N = 5: (1) the six scenarios of tools/sweep_host_check.cpp as two-actor scripts
@@ -95,13 +96,16 @@ int main(int argc, char** argv) {
         r.hc.assign((size_t)nh * ns, 0.0); r.hl.assign((size_t)nh * ns * A * 2, 0.0);
         r.ht.assign((size_t)nh * ns, 0); r.hs.assign((size_t)nh * ns, 0); r.hn.assign((size_t)nh * ns, 0);
         r.n_steps.assign(B, 0); r.step_ms.assign(ns, 0.0);
-        r.rc = be.closed_loop_traffic(p, B, x0.data(), scripts.empty() ? nullptr : scripts.data(), A, n_scripts,
-                                      with_slab, ms, s_stop, r.quant.data(), extras ? r.extra.data() : nullptr, nh,
-                                      slot.data(), nh ? r.hx.data() : nullptr, nh ? r.hu.data() : nullptr,
-                                      nh ? r.hc.data() : nullptr, nh ? r.ht.data() : nullptr,
-                                      nh ? r.hs.data() : nullptr, nh ? r.hn.data() : nullptr,
-                                      nh && A ? r.hl.data() : nullptr, extras ? r.n_steps.data() : nullptr,
-                                      extras ? r.step_ms.data() : nullptr);
+        ScriptedLoop a;
+        a.B = B; a.x_init = x0.data(); a.max_steps = ms; a.s_stop = s_stop;
+        a.actors = scripts.empty() ? nullptr : scripts.data(); a.A = A; a.n_scripts = n_scripts; a.with_slab = with_slab;
+        a.quant = r.quant.data(); a.n_hist = nh;
+        if (extras) { a.extra = r.extra.data(); a.n_steps = r.n_steps.data(); a.step_ms = r.step_ms.data(); }
+        if (nh) {
+            a.hist_x = r.hx.data(); a.hist_u = r.hu.data(); a.hist_car_s = r.hc.data(); a.hist_tl = r.ht.data();
+            a.hist_status = r.hs.data(); a.hist_nobs = r.hn.data(); a.hist_slab = A ? r.hl.data() : nullptr;
+        }
+        r.rc = be.closed_loop_scripted(p, a, slot.data());
         return r;
     };
     auto quant_differs = [&](const std::vector<double>& a, const std::vector<double>& b) {
