@@ -1,6 +1,7 @@
 // plan_evaluate_host.h -- the host backend's evaluator (plan_evaluate_chunks on a device = -1 context, and
-// plan_check_verdicts): the operation sequence of plan_evaluate_kernel (plan_evaluate_kernel.h) in IEEE double,
-// one chunk per task on std::thread workers.  The sums run in the orders include/mpcplan_evaluate.h states, so a chunk's
+// plan_check_verdicts): what plan_evaluate_kernel (plan_evaluate_kernel.h) computes, in IEEE double, one chunk per
+// task on std::thread workers.  What a stage contributes is plan_model.h's, shared with the kernel; here are the
+// sequential accumulation and the thread pool.  The sums run in the orders include/mpcplan_evaluate.h states, so a chunk's
 // result does not depend on B, on Nmax or on the number of workers; the comparisons (min / max / abs columns, NaN
 // placement, integer columns) equal the device's bit for bit, the arithmetic differs by libm's sin / cos.
 #pragma once
@@ -8,15 +9,6 @@
 #include "plan_host.h"
 
 namespace plan_host {
-
-inline void ev_min(double& m, bool& nan, double r) {
-    if (r != r) nan = true;
-    else if (r < m) m = r;
-}
-inline void ev_max(double& m, bool& nan, double r) {
-    if (r != r) nan = true;
-    else if (r > m) m = r;
-}
 
 // one chunk; X [N+1][5], U [N][2], S [N] or NULL (this chunk's slices); sum [PLAN_EV_NQ], def [Nmax][5],
 // rows [Nmax+1][PLAN_EV_NR], each may be NULL
@@ -45,19 +37,14 @@ inline void evaluate_one(const route* rt, const plan_params* p, int N, int Nmax,
             u1 = U[2 * (size_t)k];
             u2 = U[2 * (size_t)k + 1];
             sl = S ? S[k] : 0.0;
-            defect(rt, p, x, x + 5, u1, u2, df);
+            defect(*rt, *p, x, x + 5, u1, u2, df);
             for (int i = 0; i < 5; ++i) {
                 const double ad = fabs(df[i]);
                 ev_max(dmax, dnan, ad);
                 l1eq = l1eq + ad;
                 if (def) def[5 * (size_t)k + i] = df[i];
             }
-            const double t1 = p->w_y * (x[1] * x[1] + x[2] * x[2]);
-            const double e = (s_total - x[0]) / cden;
-            const double t2 = p->w_s * (e * e);
-            const double t3 = p->w_u * (u1 * u1 + u2 * u2);
-            const double t4 = p->w_slack * (sl * sl);
-            cost = cost + (((t1 + t2) + t3) + t4);
+            cost = cost + ev_stage_cost(*p, x, u1, u2, sl, s_total, cden);
             ev_max(slmax, slnan, fabs(sl));
             ev_min(u1lo, u1nan, u1);
             ev_max(u1hi, u1nan, u1);
@@ -66,41 +53,7 @@ inline void evaluate_one(const route* rt, const plan_params* p, int N, int Nmax,
         }
         ev_min(vmin, vnan, x[4]);
         ev_max(latmax, latnan, fabs(x[1]));
-        const double vs = x[4] + sl;
-        const double kvv = x[3] * (x[4] * x[4]);
-        const bool term = !iv && !fin;
-        double* ro = rows ? rows + (size_t)k * PLAN_EV_NR : nullptr;
-        double p1 = 0.0;
-        for (int kind = 0; kind < PLAN_EV_NR; ++kind) {
-            double r;
-            bool on;
-            switch (kind) {
-                case PLAN_EVR_VMIN: r = vs - p->v_min; on = true; break;
-                case PLAN_EVR_VMAX: r = route_vmax_at(rt, x[0]) - vs; on = true; break;
-                case PLAN_EVR_LATP: r = p->a_max - kvv; on = true; break;
-                case PLAN_EVR_LATM: r = p->a_max + kvv; on = true; break;
-                case PLAN_EVR_KMIN: r = x[3] - p->k_min; on = true; break;
-                case PLAN_EVR_KMAX: r = p->k_max - x[3]; on = true; break;
-                case PLAN_EVR_U1MIN: r = u1 - p->u_min[0]; on = iv; break;
-                case PLAN_EVR_U1MAX: r = p->u_max[0] - u1; on = iv; break;
-                case PLAN_EVR_U2MIN: r = u2 - p->u_min[1]; on = iv; break;
-                case PLAN_EVR_U2MAX: r = p->u_max[1] - u2; on = iv; break;
-                case PLAN_EVR_S: r = sl; on = iv; break;
-                default: r = x[0] - starget / 2.0; on = term; break;
-            }
-            if (on) {
-                if (!rnan && (r != r || r < rmin)) {
-                    rmin = r;
-                    rstage = k;
-                    rkind = kind;
-                    rnan = r != r;
-                }
-                p1 = p1 + (r != r ? r : (r < 0.0 ? -r : 0.0));
-                nneg += r < 0.0 ? 1 : 0;
-            }
-            if (ro) ro[kind] = on ? r : qnan;
-        }
-        l1in = l1in + p1;
+        l1in = l1in + ev_stage_rows(*rt, *p, k, x, u1, u2, sl, iv, !iv && !fin, starget, rows, rmin, rnan, rstage, rkind, nneg);
     }
     if (rows)
         for (size_t i = (size_t)(N + 1) * PLAN_EV_NR; i < (size_t)(Nmax + 1) * PLAN_EV_NR; ++i) rows[i] = qnan;

@@ -1,7 +1,9 @@
 // plan_evaluate_kernel.h -- the planner's batched evaluator (plan_evaluate_chunks, include/mpcplan_evaluate.h): for any
 // z = [X, U, S] the reference NLP's cost (trajectory_planning.py:128-170), Hermite-Simpson defects (:181-210),
 // inequality rows (:238-349) and a per-chunk summary of them.  No QP, no solver state; included by plan.hip after
-// plan_kernel.h, whose route_kappa / route_vmax / dyn / defect and wave reductions it reuses.
+// plan_kernel.h, whose route view and wave reductions it reuses.  What a stage contributes -- its defect, cost term,
+// rows and their argmin / L1 / count update -- is plan_model.h's, shared with plan_host::evaluate_one
+// (plan_evaluate_host.h); here are the mapping of stages to lanes, the ordered sums and the wave reductions.
 //
 // One 64-lane wavefront (one workgroup) per chunk, blockIdx.x the chunk.  The horizon is not bounded by
 // PLAN_MAX_N: lane l owns stages l, l + 64, ... and the wave walks the chunk in passes of 64 stages.  For stage k
@@ -12,7 +14,6 @@
 // tile of one pass: every lane stores its stage's terms, then lanes 0, 1 and 2 each add one of the three
 // sequences in order of k, carrying their running sum from pass to pass (the orders: include/mpcplan_evaluate.h).
 // Row kinds are visited in a fully unrolled loop (no per-lane array indexed at run time: no scratch memory).
-// Host restatement, the same operation sequence: plan_host::evaluate_one (plan_evaluate_host.h).
 #pragma once
 #include "../../include/mpcplan_evaluate.h"
 #include "plan_kernel.h"
@@ -36,15 +37,6 @@ struct EArgs {
     double *sum, *def, *rows;
 };
 
-// numpy's min / max over a sequence that may hold NaN: the value part skips NaN, the flag remembers one
-__device__ __forceinline__ void ev_min(double& m, bool& nan, double r) {
-    if (r != r) nan = true;
-    else if (r < m) m = r;
-}
-__device__ __forceinline__ void ev_max(double& m, bool& nan, double r) {
-    if (r != r) nan = true;
-    else if (r > m) m = r;
-}
 __device__ __forceinline__ bool wany(bool f) { return __ballot(f) != 0ull; }
 
 }  // namespace
@@ -100,12 +92,7 @@ __global__ void __launch_bounds__(WAVE) plan_evaluate_kernel(EArgs a) {
                     ev_max(dmax, dnan, ad[i]);
                     if (defb) defb[5 * (size_t)k + i] = df[i];
                 }
-                const double t1 = P.w_y * (x[1] * x[1] + x[2] * x[2]);
-                const double e = (s_total - x[0]) / cden;
-                const double t2 = P.w_s * (e * e);
-                const double t3 = P.w_u * (u1 * u1 + u2 * u2);
-                const double t4 = P.w_slack * (sl * sl);
-                tcost = ((t1 + t2) + t3) + t4;
+                tcost = ev_stage_cost(P, x, u1, u2, sl, s_total, cden);
                 ev_max(slmax, slnan, fabs(sl));
                 ev_min(u1lo, u1nan, u1);
                 ev_max(u1hi, u1nan, u1);
@@ -115,42 +102,7 @@ __global__ void __launch_bounds__(WAVE) plan_evaluate_kernel(EArgs a) {
             ev_min(vmin, vnan, x[4]);
             ev_max(latmax, latnan, fabs(x[1]));
 
-            // the rows, in column order
-            const double vs = x[4] + sl;
-            const double kvv = x[3] * (x[4] * x[4]);
-            const bool term = !iv && !fin;
-            double* ro = rowb ? rowb + (size_t)k * PLAN_EV_NR : nullptr;
-#pragma unroll
-            for (int kind = 0; kind < PLAN_EV_NR; ++kind) {
-                double r;
-                bool on;
-                switch (kind) {
-                    case PLAN_EVR_VMIN: r = vs - P.v_min; on = true; break;
-                    case PLAN_EVR_VMAX: r = route_vmax(a.R, x[0]) - vs; on = true; break;
-                    case PLAN_EVR_LATP: r = P.a_max - kvv; on = true; break;
-                    case PLAN_EVR_LATM: r = P.a_max + kvv; on = true; break;
-                    case PLAN_EVR_KMIN: r = x[3] - P.k_min; on = true; break;
-                    case PLAN_EVR_KMAX: r = P.k_max - x[3]; on = true; break;
-                    case PLAN_EVR_U1MIN: r = u1 - P.u_min[0]; on = iv; break;
-                    case PLAN_EVR_U1MAX: r = P.u_max[0] - u1; on = iv; break;
-                    case PLAN_EVR_U2MIN: r = u2 - P.u_min[1]; on = iv; break;
-                    case PLAN_EVR_U2MAX: r = P.u_max[1] - u2; on = iv; break;
-                    case PLAN_EVR_S: r = sl; on = iv; break;
-                    default: r = x[0] - starget / 2.0; on = term; break;
-                }
-                if (on) {
-                    // np.argmin: the first NaN wins for good, else the first strictly smaller row
-                    if (!rnan && (r != r || r < rmin)) {
-                        rmin = r;
-                        rstage = k;
-                        rkind = kind;
-                        rnan = r != r;
-                    }
-                    p1 = p1 + (r != r ? r : (r < 0.0 ? -r : 0.0));
-                    nneg += r < 0.0 ? 1 : 0;
-                }
-                if (ro) ro[kind] = on ? r : qnan;
-            }
+            p1 = ev_stage_rows(a.R, P, k, x, u1, u2, sl, iv, !iv && !fin, starget, rowb, rmin, rnan, rstage, rkind, nneg);
         }
         tile[EV_TC + ln] = tcost;
 #pragma unroll

@@ -8,6 +8,8 @@
 // the equality-constrained polish -- and performs oracle/plan_oracle.c's sequence of IEEE operations, so
 // tests/test_plan_host.py finds the two bit-identical.  It does not include, link or call the oracle.  The
 // reference's planner is CPU code (scipy SLSQP, :381-387); this is the library's CPU path of the same C ABI.
+// The model itself -- constants, row kinds, route functions, dynamics and derivatives, defect -- is plan_model.h's,
+// shared with the kernel; here are the host's storage, its sequential solver and its way-point searches.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -20,34 +22,15 @@
 #include <vector>
 
 #include "../../include/mpcplan.h"
+#include "plan_model.h"
 
 namespace plan_host {
 
+using namespace plan_model;
 
-#define NZ 8                  /* stage variables: x (s, d, o, k, v), w (u1, u2, S) */
-#define NR 11                 /* rows per stage at most */
-#define MAXNP (PLAN_MAX_N + 1)
-#define NZMAX (5 * (PLAN_MAX_N + 1) + 3 * PLAN_MAX_N)
-#define RHO 1e8               /* penalty of the active rows in the equality-constrained solve */
-#define AL_STEPS 4            /* refinement + multiplier updates of that solve */
-#define AL_TOL 1e-13        /* stop the refinements once the multiplier update is at rounding level */
-#define POLISH_ROUNDS 6
-#define WARM_ROUNDS 5         /* active-set rounds from the previous QP's classification before the interior point */
-#define MU_CHECK 1e-4         /* interior-point checkpoint: a polish is tried once mu and phi are below this ... */
-#define CHECK_SEP 100.0       /* ... and every row's s and lambda differ by this factor (no near-tie to classify) */
-#define CHECK_ROUNDS 2        /* polish rounds at the checkpoint (the interior point resumes if they fail) */
-#define SHIFT0 1.0            /* interior-point start: s = max(row, 0) + SHIFT0, lambda = 1 */
-#define TAU 0.995
-#define CYCLE_REL 1e-6
-#define DELTA0 1e-6           /* first Hessian regularisation when a pivot fails; x10 per retry */
-#define DELTA_MAX 1e4
-#define EXACT_STEP 0.1        /* exact Lagrangian Hessian once the last SQP step is at most this (max norm) ... */
-#define EXACT_AFTER 20        /* ... or from this SQP iteration on (a Gauss-Newton SQP can zigzag with steps of ~0.2
-                                 around an active lateral-acceleration row without ever meeting EXACT_STEP) */
-#define LS_ARMIJO 1e-4        /* line search on the L1 merit f + mu * violation: sufficient decrease */
-#define LS_STEPS 12           /* halvings at most (the last one is taken regardless) */
-#define LS_FULL 1e-3          /* steps at most this long (max norm) are taken whole (local phase) */
-#define LS_MEMORY 4           /* non-monotone line search: decrease against the largest of the last merits */
+
+constexpr int MAXNP = PLAN_MAX_N + 1;
+constexpr int NZMAX = 5 * (PLAN_MAX_N + 1) + 3 * PLAN_MAX_N;
 
 inline void default_params(plan_params* p) {
     memset(p, 0, sizeof(*p));
@@ -69,9 +52,32 @@ inline void default_params(plan_params* p) {
 /* ------------------------------------------------------------------------------------------------ */
 /* route: k_ref_fun and v_max_fun of optimize_full_trajectory (trajectory_planning.py:437-477)       */
 /* ------------------------------------------------------------------------------------------------ */
+/* first index i with s[i] >= v (numpy searchsorted side='left') */
+static int lower_bound(const double* x, int n, double v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        int m = (lo + hi) >> 1;
+        if (x[m] < v) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+/* first index i with s[i] > v (side='right') */
+static int upper_bound(const double* x, int n, double v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        int m = (lo + hi) >> 1;
+        if (x[m] <= v) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
 struct route {
     int M;
     double *s, *cx, *cy, *vmax;
+    /* the searches of plan_model.h's route view */
+    int lower(double v) const { return lower_bound(s, M, v); }
+    int upper(double v) const { return upper_bound(s, M, v); }
 };
 
 inline int route_create(const double* s, int M, const double* cx, const double* cy, const double* vmax,
@@ -101,172 +107,8 @@ inline void route_destroy(route* r) {
 
 inline double route_s_total(const route* r) { return r->s[r->M - 1]; }
 
-/* first index i with s[i] >= v (numpy searchsorted side='left') */
-static int lower_bound(const double* x, int n, double v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int m = (lo + hi) >> 1;
-        if (x[m] < v) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
-
-/* first index i with s[i] > v (side='right') */
-static int upper_bound(const double* x, int n, double v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int m = (lo + hi) >> 1;
-        if (x[m] <= v) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
-
-/* k_ref_fun (:445-459): t = s_to_t(s) (interp1d linear, extrapolated, :440-442: searchsorted left, index
- * clipped to [1, M-1]); curvature of the CubicSpline pair at t (PPoly: interval floor(t) clipped to
- * [0, M-2]); first and second derivatives in s on the same pieces (t is linear in s there). */
-static double route_kappa(const route* r, double s, double* dkds, double* d2kds2) {
-    const int M = r->M;
-    int i = lower_bound(r->s, M, s);
-    if (i < 1) i = 1;
-    if (i > M - 1) i = M - 1;
-    const double slope = 1.0 / (r->s[i] - r->s[i - 1]);
-    const double t = slope * (s - r->s[i - 1]) + (double)(i - 1);
-    int j = (int)floor(t);
-    if (j < 0) j = 0;
-    if (j > M - 2) j = M - 2;
-    const double tau = t - (double)j;
-    const double* a = r->cx + 4 * j;
-    const double* b = r->cy + 4 * j;
-    const double x1 = (3.0 * a[0] * tau + 2.0 * a[1]) * tau + a[2], x2 = 6.0 * a[0] * tau + 2.0 * a[1], x3 = 6.0 * a[0];
-    const double y1 = (3.0 * b[0] * tau + 2.0 * b[1]) * tau + b[2], y2 = 6.0 * b[0] * tau + 2.0 * b[1], y3 = 6.0 * b[0];
-    const double num = x1 * y2 - y1 * x2;
-    const double q = x1 * x1 + y1 * y1;
-    const double sq = sqrt(q);
-    double den = q * sq + 1e-9;
-    const int clamp = den < 1e-8;
-    if (clamp) den = 1e-8;
-    const double k = num / den;
-    if (dkds) {
-        const double dnum = x1 * y3 - y1 * x3;
-        const double dden = clamp ? 0.0 : 3.0 * sq * (x1 * x2 + y1 * y2);
-        const double kt = (dnum - k * dden) / den;
-        *dkds = kt * slope;
-        if (d2kds2) {
-            /* num'' = x2 y3 - y2 x3 (cubic pieces); den'' = 3/4 q^-1/2 q'^2 + 3/2 q^1/2 q'' */
-            const double d2num = x2 * y3 - y2 * x3;
-            const double qd = 2.0 * (x1 * x2 + y1 * y2), qdd = 2.0 * (x2 * x2 + x1 * x3 + y2 * y2 + y1 * y3);
-            const double d2den = (clamp || sq == 0.0) ? 0.0 : 0.75 * qd * qd / sq + 1.5 * sq * qdd;
-            *d2kds2 = (d2num - 2.0 * kt * dden - k * d2den) / den * slope * slope;
-        }
-    }
-    return k;
-}
-
-inline double route_kappa_at(const route* r, double s, double* dkds) { return route_kappa(r, s, dkds, NULL); }
-
-/* v_max_fun (:470-473): interp1d kind='previous' (below the first knot: the first limit, see mpcplan.h) */
-inline double route_vmax_at(const route* r, double s) {
-    const int i = upper_bound(r->s, r->M, s);
-    return r->vmax[i > 0 ? i - 1 : 0];
-}
-
-/* ------------------------------------------------------------------------------------------------ */
-/* the NLP's functions and derivatives                                                                */
-/* ------------------------------------------------------------------------------------------------ */
-static double guard_den(double den) {       /* :74-77 */
-    if (fabs(den) < 1e-4) den = den > 0.0 ? 1e-4 : (den < 0.0 ? -1e-4 : 1e-4);
-    return den;
-}
-
-/* TrajectoryOptimizer.dynamics (:50-89) */
-inline void dynamics(const double x[5], double u1, double u2, double kref, double f[5]) {
-    const double den = guard_den(1.0 - x[1] * kref);
-    const double sd = (x[4] * cos(x[2])) / den;
-    f[0] = sd;
-    f[1] = x[4] * sin(x[2]);
-    f[2] = x[4] * x[3] - sd * kref;
-    f[3] = u1;
-    f[4] = u2;
-}
-
-/* d f / d x with kappa = kappa(s): F row-major 5x5 (d f / d u = e3, e4 for u1, u2) */
-static void dyn_jac(const double x[5], double kref, double dk, double F[25]) {
-    const double d = x[1], o = x[2], k = x[3], v = x[4];
-    const double raw = 1.0 - d * kref;
-    const int guarded = fabs(raw) < 1e-4;
-    const double den = guard_den(raw);
-    const double c = cos(o), sn = sin(o);
-    const double sd = v * c / den;
-    double ds[5];
-    ds[0] = guarded ? 0.0 : v * c * d * dk / (den * den);
-    ds[1] = guarded ? 0.0 : v * c * kref / (den * den);
-    ds[2] = -v * sn / den;
-    ds[3] = 0.0;
-    ds[4] = c / den;
-    memset(F, 0, sizeof(double) * 25);
-    for (int j = 0; j < 5; ++j) {
-        F[j] = ds[j];
-        F[10 + j] = -kref * ds[j];
-    }
-    F[5 + 2] = v * c;
-    F[5 + 4] = sn;
-    F[10 + 0] += -dk * sd;
-    F[10 + 3] += v;
-    F[10 + 4] += k;
-}
-
-/* W = sum_i y_i d2 f_i / dx2 at x, kappa = kappa(s) with derivatives k1, k2 (f3, f4 are linear) */
-static void hess_f(const double x[5], double kr, double k1, double k2, const double y[5], double W[25]) {
-    const double d = x[1], o = x[2], v = x[4];
-    const double raw = 1.0 - d * kr;
-    const int gu = fabs(raw) < 1e-4;
-    const double g = 1.0 / guard_den(raw);
-    const double c = cos(o), sn = sin(o);
-    /* g = 1 / (1 - d kappa(s)) and its derivatives (constant when guarded) */
-    const double gs = gu ? 0.0 : d * k1 * g * g, gd = gu ? 0.0 : kr * g * g;
-    const double gss = gu ? 0.0 : d * k2 * g * g + 2.0 * d * d * k1 * k1 * g * g * g;
-    const double gsd = gu ? 0.0 : k1 * g * g + 2.0 * d * k1 * kr * g * g * g;
-    const double gdd = gu ? 0.0 : 2.0 * kr * kr * g * g * g;
-    double Hs[25], ds[5];
-    memset(Hs, 0, sizeof(Hs));
-    /* s_dot = v cos(o) g */
-    Hs[0] = v * c * gss;
-    Hs[1] = Hs[5] = v * c * gsd;
-    Hs[6] = v * c * gdd;
-    Hs[2] = Hs[10] = -v * sn * gs;
-    Hs[7] = Hs[11] = -v * sn * gd;
-    Hs[12] = -v * c * g;
-    Hs[4] = Hs[20] = c * gs;
-    Hs[9] = Hs[21] = c * gd;
-    Hs[14] = Hs[22] = -sn * g;
-    ds[0] = v * c * gs; ds[1] = v * c * gd; ds[2] = -v * sn * g; ds[3] = 0.0; ds[4] = c * g;
-    const double sd = v * c * g;
-    for (int i = 0; i < 25; ++i) W[i] = (y[0] - y[2] * kr) * Hs[i];
-    /* f1 = v sin(o) */
-    W[12] += -y[1] * v * sn;
-    W[14] += y[1] * c;
-    W[22] += y[1] * c;
-    /* f2 = v k - s_dot kappa(s): the v k term, and -(grad s_dot x grad kappa + transpose + s_dot kappa'') */
-    W[19] += y[2];
-    W[23] += y[2];
-    for (int j = 0; j < 5; ++j) {
-        W[j] += -y[2] * k1 * ds[j];
-        W[5 * j] += -y[2] * k1 * ds[j];
-    }
-    W[0] += -y[2] * sd * k2;
-}
-
-/* Hermite-Simpson defect of interval k (:183-208): x_{k+1} - (x_k + sign * dt/6 (f_k + 4 f_mid + f_{k+1})) */
-inline void defect(const route* r, const plan_params* p, const double xa[5], const double xb[5], double u1,
-                     double u2, double def[5]) {
-    const double h = p->dt;
-    double fa[5], fb[5], fm[5], xm[5];
-    dynamics(xa, u1, u2, route_kappa_at(r, xa[0], NULL), fa);
-    dynamics(xb, u1, u2, route_kappa_at(r, xb[0], NULL), fb);
-    for (int i = 0; i < 5; ++i) xm[i] = 0.5 * (xa[i] + xb[i]) + (h / 8.0) * (fa[i] - fb[i]);
-    dynamics(xm, u1, u2, route_kappa_at(r, xm[0], NULL), fm);
-    for (int i = 0; i < 5; ++i) def[i] = xb[i] - (xa[i] + p->defect_sign * (h / 6.0) * (fa[i] + 4.0 * fm[i] + fb[i]));
-}
+inline double route_kappa_at(const route* r, double s, double* dkds) { return route_kappa(*r, s, dkds, nullptr); }
+inline double route_vmax_at(const route* r, double s) { return route_vmax(*r, s); }
 
 /* TrajectoryOptimizer.cost (:128-170) */
 inline double cost(const route* r, const plan_params* p, int N, const double x0[5], const double* X,
@@ -289,9 +131,6 @@ inline double cost(const route* r, const plan_params* p, int N, const double x0[
 /* ------------------------------------------------------------------------------------------------ */
 /* the stage QP                                                                                       */
 /* ------------------------------------------------------------------------------------------------ */
-enum { ROW_VMIN, ROW_VMAX, ROW_LATP, ROW_LATM, ROW_KMIN, ROW_KMAX, ROW_U1MIN, ROW_U1MAX, ROW_U2MIN, ROW_U2MAX,
-       ROW_S, ROW_STERM };
-
 typedef struct {
     int N, fin;
     double delta;                                         /* Hessian regularisation of this QP (0 unless needed) */
@@ -354,13 +193,13 @@ static int interval_lin(const route* r, const plan_params* p, const double xa[5]
                         double u2, double A[25], double B[15], double c[5], double D1o[25]) {
     const double h = p->dt, sg = p->defect_sign;
     double dka, dkb, dkm, fa[5], fb[5], fm[5], xm[5], Fa[25], Fb[25], Fm[25];
-    const double ka = route_kappa(r, xa[0], &dka, NULL);
-    const double kb = route_kappa(r, xb[0], &dkb, NULL);
-    dynamics(xa, u1, u2, ka, fa);
-    dynamics(xb, u1, u2, kb, fb);
+    const double ka = route_kappa(*r, xa[0], &dka, nullptr);
+    const double kb = route_kappa(*r, xb[0], &dkb, nullptr);
+    dyn(xa, u1, u2, ka, fa);
+    dyn(xb, u1, u2, kb, fb);
     for (int i = 0; i < 5; ++i) xm[i] = 0.5 * (xa[i] + xb[i]) + (h / 8.0) * (fa[i] - fb[i]);
-    const double km = route_kappa(r, xm[0], &dkm, NULL);
-    dynamics(xm, u1, u2, km, fm);
+    const double km = route_kappa(*r, xm[0], &dkm, nullptr);
+    dyn(xm, u1, u2, km, fm);
     double def[5];
     for (int i = 0; i < 5; ++i) def[i] = xb[i] - (xa[i] + sg * (h / 6.0) * (fa[i] + 4.0 * fm[i] + fb[i]));
     dyn_jac(xa, ka, dka, Fa);
@@ -407,13 +246,13 @@ static void interval_hess(const route* r, const plan_params* p, const double xa[
                           double u2, const double y[5], double Haa[25], double Hab[25], double Hbb[25]) {
     const double h = p->dt, f6 = p->defect_sign * h / 6.0;
     double k1a, k2a, k1b, k2b, k1m, k2m, fa[5], fb[5], fm[5], xm[5], Fa[25], Fb[25], Fm[25];
-    const double ka = route_kappa(r, xa[0], &k1a, &k2a);
-    const double kb = route_kappa(r, xb[0], &k1b, &k2b);
-    dynamics(xa, u1, u2, ka, fa);
-    dynamics(xb, u1, u2, kb, fb);
+    const double ka = route_kappa(*r, xa[0], &k1a, &k2a);
+    const double kb = route_kappa(*r, xb[0], &k1b, &k2b);
+    dyn(xa, u1, u2, ka, fa);
+    dyn(xb, u1, u2, kb, fb);
     for (int i = 0; i < 5; ++i) xm[i] = 0.5 * (xa[i] + xb[i]) + (h / 8.0) * (fa[i] - fb[i]);
-    const double km = route_kappa(r, xm[0], &k1m, &k2m);
-    dynamics(xm, u1, u2, km, fm);
+    const double km = route_kappa(*r, xm[0], &k1m, &k2m);
+    dyn(xm, u1, u2, km, fm);
     dyn_jac(xa, ka, k1a, Fa);
     dyn_jac(xb, kb, k1b, Fb);
     dyn_jac(xm, km, k1m, Fm);
@@ -423,11 +262,11 @@ static void interval_hess(const route* r, const plan_params* p, const double xa[
         for (int i = 0; i < 5; ++i) v += Fm[5 * i + j] * y[i];
         yb[j] = v;
     }
-    hess_f(xa, ka, k1a, k2a, y, Wa);
-    hess_f(xb, kb, k1b, k2b, y, Wb);
-    hess_f(xm, km, k1m, k2m, y, Wm);
-    hess_f(xa, ka, k1a, k2a, yb, Va);
-    hess_f(xb, kb, k1b, k2b, yb, Vb);
+    hess_f_scaled(xa, ka, k1a, k2a, y, Wa);
+    hess_f_scaled(xb, kb, k1b, k2b, y, Wb);
+    hess_f_scaled(xm, km, k1m, k2m, y, Wm);
+    hess_f_scaled(xa, ka, k1a, k2a, yb, Va);
+    hess_f_scaled(xb, kb, k1b, k2b, yb, Vb);
     for (int i = 0; i < 5; ++i)
         for (int j = 0; j < 5; ++j) {
             Ma[5 * i + j] = (i == j ? 0.5 : 0.0) + (h / 8.0) * Fa[5 * i + j];
@@ -498,13 +337,16 @@ static void fold_interval(qp_t* Q, int k, const double Haa[25], const double Hab
     }
 }
 
-#define ADDROW(kd, ...)                                                                                    \
+/* row kd of stage k with value gval and the coefficients given, if the stage has it (row_on) */
+#define ADDROW(kd, gval, ...)                                                                              \
     do {                                                                                                   \
-        const double cf_[NZ] = {__VA_ARGS__};                                                              \
-        memcpy(Q->a[k][n], cf_, sizeof(cf_));                                                              \
-        Q->g[k][n] = gv;                                                                                   \
-        Q->kind[k][n] = (kd);                                                                              \
-        ++n;                                                                                               \
+        if (row_on((kd), k, N, fin)) {                                                                     \
+            const double cf_[NZ] = {__VA_ARGS__};                                                          \
+            memcpy(Q->a[k][n], cf_, sizeof(cf_));                                                          \
+            Q->g[k][n] = (gval);                                                                           \
+            Q->kind[k][n] = (kd);                                                                          \
+            ++n;                                                                                           \
+        }                                                                                                  \
     } while (0)
 
 /* the QP at the SQP iterate (Xb, Ub, Sb); vlim: frozen speed limits or NULL; M: multipliers for the exact
@@ -545,48 +387,25 @@ static int build_qp(const route* r, const plan_params* p, int N, const double x0
         const double sl = k < N ? Sb[k] : 0.0, hs = k < N ? 1.0 : 0.0;
         const double kk = x[3], v = x[4];
         int n = 0;
-        double gv;
-        if (!(fin && k == N)) {
-            gv = v + sl - p->v_min;
-            ADDROW(ROW_VMIN, 0, 0, 0, 0, 1.0, 0, 0, hs);                                  /* :251-259 */
-            gv = (vlim ? vlim[k] : route_vmax_at(r, x[0])) - (v + sl);
-            ADDROW(ROW_VMAX, 0, 0, 0, 0, -1.0, 0, 0, -hs);                                /* :263-271 */
-            if (k > 0) {
-                gv = p->a_max - kk * v * v;
-                ADDROW(ROW_LATP, 0, 0, 0, -v * v, -2.0 * kk * v, 0, 0, 0);                /* :277-281 */
-                gv = p->a_max + kk * v * v;
-                ADDROW(ROW_LATM, 0, 0, 0, v * v, 2.0 * kk * v, 0, 0, 0);                  /* :285-289 */
-                if (M) {
-                    /* -lam d2 g over (k, v): g = a_max -+ k v^2 */
-                    const double lp = M->lat[k][0], lm = M->lat[k][1];
-                    Q->H[k][3][4] += 2.0 * v * (lp - lm);
-                    Q->H[k][4][3] += 2.0 * v * (lp - lm);
-                    Q->H[k][4][4] += 2.0 * kk * (lp - lm);
-                }
-            }
+        ADDROW(ROW_VMIN, v + sl - p->v_min, 0, 0, 0, 0, 1.0, 0, 0, hs);                                     /* :251-259 */
+        ADDROW(ROW_VMAX, (vlim ? vlim[k] : route_vmax_at(r, x[0])) - (v + sl), 0, 0, 0, 0, -1.0, 0, 0, -hs);  /* :263-271 */
+        ADDROW(ROW_LATP, p->a_max - kk * v * v, 0, 0, 0, -v * v, -2.0 * kk * v, 0, 0, 0);                   /* :277-281 */
+        ADDROW(ROW_LATM, p->a_max + kk * v * v, 0, 0, 0, v * v, 2.0 * kk * v, 0, 0, 0);                     /* :285-289 */
+        if (M && row_on(ROW_LATP, k, N, fin)) {
+            /* -lam d2 g over (k, v): g = a_max -+ k v^2 */
+            const double lp = M->lat[k][0], lm = M->lat[k][1];
+            Q->H[k][3][4] += 2.0 * v * (lp - lm);
+            Q->H[k][4][3] += 2.0 * v * (lp - lm);
+            Q->H[k][4][4] += 2.0 * kk * (lp - lm);
         }
-        if (k > 0) {
-            gv = kk - p->k_min;
-            ADDROW(ROW_KMIN, 0, 0, 0, 1.0, 0, 0, 0, 0);                                   /* :296-299 */
-            gv = p->k_max - kk;
-            ADDROW(ROW_KMAX, 0, 0, 0, -1.0, 0, 0, 0, 0);                                  /* :303-306 */
-        }
-        if (k < N) {
-            gv = Ub[2 * k] - p->u_min[0];
-            ADDROW(ROW_U1MIN, 0, 0, 0, 0, 0, 1.0, 0, 0);                                  /* :313-316 */
-            gv = p->u_max[0] - Ub[2 * k];
-            ADDROW(ROW_U1MAX, 0, 0, 0, 0, 0, -1.0, 0, 0);                                 /* :320-323 */
-            gv = Ub[2 * k + 1] - p->u_min[1];
-            ADDROW(ROW_U2MIN, 0, 0, 0, 0, 0, 0, 1.0, 0);                                  /* :328-331 */
-            gv = p->u_max[1] - Ub[2 * k + 1];
-            ADDROW(ROW_U2MAX, 0, 0, 0, 0, 0, 0, -1.0, 0);                                 /* :335-338 */
-            gv = Sb[k];
-            ADDROW(ROW_S, 0, 0, 0, 0, 0, 0, 0, 1.0);                                      /* :343-345 */
-        }
-        if (k == N && !fin) {
-            gv = x[0] - s_target / 2.0;
-            ADDROW(ROW_STERM, 1.0, 0, 0, 0, 0, 0, 0, 0);                                  /* :241-244 */
-        }
+        ADDROW(ROW_KMIN, kk - p->k_min, 0, 0, 0, 1.0, 0, 0, 0, 0);                                          /* :296-299 */
+        ADDROW(ROW_KMAX, p->k_max - kk, 0, 0, 0, -1.0, 0, 0, 0, 0);                                         /* :303-306 */
+        ADDROW(ROW_U1MIN, Ub[2 * k] - p->u_min[0], 0, 0, 0, 0, 0, 1.0, 0, 0);                               /* :313-316 */
+        ADDROW(ROW_U1MAX, p->u_max[0] - Ub[2 * k], 0, 0, 0, 0, 0, -1.0, 0, 0);                              /* :320-323 */
+        ADDROW(ROW_U2MIN, Ub[2 * k + 1] - p->u_min[1], 0, 0, 0, 0, 0, 0, 1.0, 0);                           /* :328-331 */
+        ADDROW(ROW_U2MAX, p->u_max[1] - Ub[2 * k + 1], 0, 0, 0, 0, 0, 0, -1.0, 0);                          /* :335-338 */
+        ADDROW(ROW_S, Sb[k], 0, 0, 0, 0, 0, 0, 0, 1.0);                                                     /* :343-345 */
+        ADDROW(ROW_STERM, x[0] - s_target / 2.0, 1.0, 0, 0, 0, 0, 0, 0, 0);                                 /* :241-244 */
         Q->nr[k] = n;
     }
     for (int i = 0; i < 5; ++i) Q->xi0[i] = x0[i] - Xb[i];
@@ -608,36 +427,6 @@ static void stage_hess(const qp_t* Q, int k, const double* W, double H[NZ][NZ]) 
             for (int v = 0; v < NZ; ++v) H[u][v] += W[j] * a[u] * a[v];
         }
     }
-}
-
-/* H (3 x 3, symmetric positive definite) = L D L' with L unit lower triangular, stored as {1/d0, l10, 1/d1,
- * l20, l21, 1/d2}: no square roots, three divisions per factorisation and none in the solves (the GPU kernel's
- * form and rounding).  Fails when a pivot is not positive, the Cholesky condition. */
-static int chol3(const double H[3][3], double L[6]) {
-    const double d0 = H[0][0];
-    if (!(d0 > 0.0)) return -1;
-    L[0] = 1.0 / d0;
-    L[1] = H[1][0] * L[0];
-    const double d1 = H[1][1] - L[1] * H[1][0];
-    if (!(d1 > 0.0)) return -1;
-    L[2] = 1.0 / d1;
-    L[3] = H[2][0] * L[0];
-    const double e21 = H[2][1] - L[3] * H[1][0];
-    L[4] = e21 * L[2];
-    const double d2 = H[2][2] - L[3] * H[2][0] - L[4] * e21;
-    if (!(d2 > 0.0)) return -1;
-    L[5] = 1.0 / d2;
-    return 0;
-}
-
-/* b <- (L D L')^-1 b */
-static void chol3_solve(const double L[6], double b[3]) {
-    const double y0 = b[0];
-    const double y1 = b[1] - L[1] * y0;
-    const double y2 = b[2] - L[3] * y0 - L[4] * y1;
-    b[2] = y2 * L[5];
-    b[1] = y1 * L[2] - L[4] * b[2];
-    b[0] = y0 * L[0] - L[1] * b[1] - L[3] * b[2];
 }
 
 static void solve_core(const qp_t* Q, const fac_t* F, const double gl[][NZ], double dz[][NZ]);
@@ -678,7 +467,7 @@ static int factor(const qp_t* Q, const double W[][NR], fac_t* F) {
                 Hwx[5 * i + j] = v;
             }
         }
-        if (chol3((const double(*)[3])Hww, F->L[k])) return -1;
+        if (!chol3((const double(*)[3])Hww, F->L[k])) return -1;
         for (int j = 0; j < 5; ++j) {
             double col[3] = {-Hwx[j], -Hwx[5 + j], -Hwx[10 + j]};
             chol3_solve(F->L[k], col);
@@ -1134,7 +923,7 @@ static double violation(const route* r, const plan_params* p, int N, const doubl
     double v = 0.0, def[5];
     for (int i = 0; i < 5; ++i) v += fabs(X[i] - x0[i]);
     for (int k = 0; k < N; ++k) {
-        defect(r, p, X + 5 * k, X + 5 * (k + 1), U[2 * k], U[2 * k + 1], def);
+        defect(*r, *p, X + 5 * k, X + 5 * (k + 1), U[2 * k], U[2 * k + 1], def);
         for (int i = 0; i < 5; ++i) v += fabs(def[i]);
     }
     for (int k = 0; k <= N; ++k) {

@@ -1,9 +1,12 @@
 // plan_kernel.h — the planner's device code (one wavefront per chunk, LDS working set); included by plan.hip
 // and, with tools/plan_emu.cpp's definitions of the HIP built-ins, by the host emulation used to debug it
-// under AddressSanitizer.  See plan.hip for the design.
+// under AddressSanitizer.  See plan.hip for the design.  The model itself -- constants, row kinds, route functions,
+// dynamics and derivatives, defect -- is plan_model.h's, shared with the host backend; here are the device's
+// storage, its lane-parallel solver and its way-point searches.
 #pragma once
 #include <cmath>
 #include "../../include/mpcplan.h"
+#include "plan_model.h"
 
 #ifndef PLAN_LDS_DECL
 #define PLAN_LDS_DECL extern __shared__ double lds[]
@@ -19,9 +22,9 @@ __device__ unsigned long long g_plan_prof[16];
 
 namespace {
 
+using namespace plan_model;
+
 constexpr int WAVE = 64;
-constexpr int NZ = 8;             // stage variables: x (s, d, o, k, v), w (u1, u2, S)
-constexpr int NR = 11;            // rows per stage at most
 constexpr int RS = 11;            // row slots per stage in LDS: one per row kind (kind_slot), so every row visit
                                   // has a compile-time slot; a stage's missing kinds leave their slots unused
 constexpr int NH = 36;            // packed symmetric 8x8
@@ -30,28 +33,6 @@ constexpr int NH = 36;            // packed symmetric 8x8
 // every fourth lane on the same bank group: SQ_LDS_BANK_CONFLICT was 39% of the LDS-active cycles)
 constexpr int ZS = NZ + 1;
 constexpr int HSTR = NH + 9;     // a stage's H block: packed H (36), the factorisation's 8 slots (hs_slot), 1 / HT(7, 7)
-constexpr double RHO = 1e8;       // penalty of the active rows in the equality-constrained solve
-constexpr int AL_STEPS = 4;
-constexpr double AL_TOL = 1e-13;   // refinements stop once the multiplier update is at rounding level
-constexpr int POLISH_ROUNDS = 6;
-constexpr int WARM_ROUNDS = 5;      // active-set rounds from the previous QP's classification (oracle qp_solve)
-constexpr double MU_CHECK = 1e-4;   // interior-point checkpoint: a polish is tried once mu and phi are below this ...
-constexpr double CHECK_SEP = 100.0; // ... and every row's s and lambda differ by this factor (no near-tie)
-constexpr int CHECK_ROUNDS = 2;     // polish rounds at the checkpoint (the interior point resumes if they fail)
-constexpr double SHIFT0 = 1.0;
-constexpr double TAU = 0.995;
-constexpr double CYCLE_REL = 1e-6;
-constexpr double DELTA0 = 1e-6;
-constexpr double DELTA_MAX = 1e4;
-constexpr double EXACT_STEP = 0.1;
-constexpr int EXACT_AFTER = 20;      // exact Hessian from this SQP iteration on as well (oracle EXACT_AFTER)
-constexpr double LS_ARMIJO = 1e-4;
-constexpr int LS_STEPS = 12;
-constexpr double LS_FULL = 1e-3;
-constexpr int LS_MEMORY = 4;
-
-enum { ROW_VMIN, ROW_VMAX, ROW_LATP, ROW_LATM, ROW_KMIN, ROW_KMAX, ROW_U1MIN, ROW_U1MAX, ROW_U2MIN, ROW_U2MAX,
-       ROW_S, ROW_STERM };
 
 struct DevRoute {
     const double *s, *cx, *cy, *vmax;
@@ -63,6 +44,9 @@ struct DevRoute {
     const int* grid;
     int T;
     double ginv;
+    // the searches of plan_model.h's route view (lower_bound_g, upper_bound_g)
+    __device__ int lower(double v) const;
+    __device__ int upper(double v) const;
 };
 
 // the grid of DevRoute (host side; T cells of equal length)
@@ -180,7 +164,7 @@ __device__ inline int wsumi(int v) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// route: k_ref_fun (:445-459) and v_max_fun (:470-473)
+// route: the way-point searches under k_ref_fun and v_max_fun (plan_model.h's route_kappa, route_vmax)
 // ------------------------------------------------------------------------------------------------------
 __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 
@@ -210,160 +194,8 @@ __device__ int upper_bound_g(const DevRoute& R, double v) {
     return i;
 }
 
-// kappa(s) with d/ds and d2/ds2 (k2 may be null): s_to_t linear (searchsorted left, clipped to [1, M-1]),
-// spline piece floor(t) clipped to [0, M-2]
-__device__ double route_kappa(const DevRoute& R, double s, double* k1, double* k2) {
-    const int M = R.M;
-    int i = lower_bound_g(R, s);
-    i = i < 1 ? 1 : (i > M - 1 ? M - 1 : i);
-    const double slope = 1.0 / (R.s[i] - R.s[i - 1]);
-    const double t = slope * (s - R.s[i - 1]) + (double)(i - 1);
-    int j = (int)floor(t);
-    j = j < 0 ? 0 : (j > M - 2 ? M - 2 : j);
-    const double tau = t - (double)j;
-    const double* a = R.cx + 4 * j;
-    const double* b = R.cy + 4 * j;
-    const double x1 = (3.0 * a[0] * tau + 2.0 * a[1]) * tau + a[2], x2 = 6.0 * a[0] * tau + 2.0 * a[1], x3 = 6.0 * a[0];
-    const double y1 = (3.0 * b[0] * tau + 2.0 * b[1]) * tau + b[2], y2 = 6.0 * b[0] * tau + 2.0 * b[1], y3 = 6.0 * b[0];
-    const double num = x1 * y2 - y1 * x2;
-    const double q = x1 * x1 + y1 * y1;
-    const double sq = sqrt(q);
-    double den = q * sq + 1e-9;
-    const bool clamp = den < 1e-8;
-    if (clamp) den = 1e-8;
-    const double k = num / den;
-    if (k1) {
-        const double dnum = x1 * y3 - y1 * x3;
-        const double dden = clamp ? 0.0 : 3.0 * sq * (x1 * x2 + y1 * y2);
-        const double kt = (dnum - k * dden) / den;
-        *k1 = kt * slope;
-        if (k2) {
-            const double d2num = x2 * y3 - y2 * x3;
-            const double qd = 2.0 * (x1 * x2 + y1 * y2), qdd = 2.0 * (x2 * x2 + x1 * x3 + y2 * y2 + y1 * y3);
-            const double d2den = (clamp || sq == 0.0) ? 0.0 : 0.75 * qd * qd / sq + 1.5 * sq * qdd;
-            *k2 = (d2num - 2.0 * kt * dden - k * d2den) / den * slope * slope;
-        }
-    }
-    return k;
-}
-
-__device__ double route_vmax(const DevRoute& R, double s) {
-    const int i = upper_bound_g(R, s);
-    return R.vmax[i > 0 ? i - 1 : 0];
-}
-
-// ------------------------------------------------------------------------------------------------------
-// the NLP's functions (trajectory_planning.py:50-89, :128-170, :181-210) and derivatives
-// ------------------------------------------------------------------------------------------------------
-__device__ double guard_den(double den) {
-    if (fabs(den) < 1e-4) den = den > 0.0 ? 1e-4 : (den < 0.0 ? -1e-4 : 1e-4);
-    return den;
-}
-
-__device__ void dyn(const double x[5], double u1, double u2, double kr, double f[5]) {
-    const double den = guard_den(1.0 - x[1] * kr);
-    const double sd = (x[4] * cos(x[2])) / den;
-    f[0] = sd;
-    f[1] = x[4] * sin(x[2]);
-    f[2] = x[4] * x[3] - sd * kr;
-    f[3] = u1;
-    f[4] = u2;
-}
-
-__device__ void dyn_jac(const double x[5], double kr, double dk, double F[25]) {
-    const double d = x[1], o = x[2], k = x[3], v = x[4];
-    const double raw = 1.0 - d * kr;
-    const bool g = fabs(raw) < 1e-4;
-    const double den = guard_den(raw);
-    const double c = cos(o), sn = sin(o);
-    const double sd = v * c / den;
-    double ds[5];
-    ds[0] = g ? 0.0 : v * c * d * dk / (den * den);
-    ds[1] = g ? 0.0 : v * c * kr / (den * den);
-    ds[2] = -v * sn / den;
-    ds[3] = 0.0;
-    ds[4] = c / den;
-#pragma unroll
-    for (int i = 0; i < 25; ++i) F[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        F[j] = ds[j];
-        F[10 + j] = -kr * ds[j];
-    }
-    F[7] = v * c;
-    F[9] = sn;
-    F[10] += -dk * sd;
-    F[13] += v;
-    F[14] += k;
-}
-
-__device__ void hess_f(const double x[5], double kr, double k1, double k2, const double y[5], double W[25]) {
-    const double d = x[1], o = x[2], v = x[4];
-    const double raw = 1.0 - d * kr;
-    const bool gu = fabs(raw) < 1e-4;
-    const double g = 1.0 / guard_den(raw);
-    const double c = cos(o), sn = sin(o);
-    const double gs = gu ? 0.0 : d * k1 * g * g, gd = gu ? 0.0 : kr * g * g;
-    const double gss = gu ? 0.0 : d * k2 * g * g + 2.0 * d * d * k1 * k1 * g * g * g;
-    const double gsd = gu ? 0.0 : k1 * g * g + 2.0 * d * k1 * kr * g * g * g;
-    const double gdd = gu ? 0.0 : 2.0 * kr * kr * g * g * g;
-    const double ds[5] = {v * c * gs, v * c * gd, -v * sn * g, 0.0, c * g};
-    const double sd = v * c * g;
-    const double cs = y[0] - y[2] * kr;
-#pragma unroll
-    for (int i = 0; i < 25; ++i) W[i] = 0.0;
-    W[0] = cs * v * c * gss;
-    W[1] = W[5] = cs * v * c * gsd;
-    W[6] = cs * v * c * gdd;
-    W[2] = W[10] = cs * -v * sn * gs;
-    W[7] = W[11] = cs * -v * sn * gd;
-    W[12] = cs * -v * c * g;
-    W[4] = W[20] = cs * c * gs;
-    W[9] = W[21] = cs * c * gd;
-    W[14] = W[22] = cs * -sn * g;
-    W[12] += -y[1] * v * sn;
-    W[14] += y[1] * c;
-    W[22] += y[1] * c;
-    W[19] += y[2];
-    W[23] += y[2];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        W[j] += -y[2] * k1 * ds[j];
-        W[5 * j] += -y[2] * k1 * ds[j];
-    }
-    W[0] += -y[2] * sd * k2;
-}
-
-__device__ void defect(const DevRoute& R, const plan_params& P, const double xa[5], const double xb[5], double u1,
-                       double u2, double def[5]) {
-    const double h = P.dt;
-    double fa[5], fb[5], fm[5], xm[5];
-    dyn(xa, u1, u2, route_kappa(R, xa[0], nullptr, nullptr), fa);
-    dyn(xb, u1, u2, route_kappa(R, xb[0], nullptr, nullptr), fb);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) xm[i] = 0.5 * (xa[i] + xb[i]) + (h / 8.0) * (fa[i] - fb[i]);
-    dyn(xm, u1, u2, route_kappa(R, xm[0], nullptr, nullptr), fm);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) def[i] = xb[i] - (xa[i] + P.defect_sign * (h / 6.0) * (fa[i] + 4.0 * fm[i] + fb[i]));
-}
-
-// the rows of stage k, in order: [v_min, v_max, (k > 0) lateral +, lateral -] unless the final chunk's last
-// stage; (k > 0) curvature min, max; (k < N) u1 min, max, u2 min, max, slack; the intermediate chunk's
-// terminal row at k = N.  Counted and indexed arithmetically (no per-lane array, which would live in
-// scratch memory).
-__host__ __device__ constexpr int stage_nrows(int k, int N, int fin) {
-    return ((fin && k == N) ? 0 : (k > 0 ? 4 : 2)) + (k > 0 ? 2 : 0) + (k < N ? 5 : 0) + ((k == N && !fin) ? 1 : 0);
-}
-__host__ __device__ constexpr int row_kind(int k, int N, int fin, int j) {
-    const int n0 = (fin && k == N) ? 0 : (k > 0 ? 4 : 2);
-    if (j < n0) return j;                                   // ROW_VMIN, ROW_VMAX, ROW_LATP, ROW_LATM
-    j -= n0;
-    const int n1 = k > 0 ? 2 : 0;
-    if (j < n1) return ROW_KMIN + j;
-    j -= n1;
-    if (k < N) return ROW_U1MIN + j;                        // ROW_U1MIN .. ROW_S
-    return ROW_STERM;
-}
+__device__ inline int DevRoute::lower(double v) const { return lower_bound_g(*this, v); }
+__device__ inline int DevRoute::upper(double v) const { return upper_bound_g(*this, v); }
 
 // Row coefficients over (x_k, w_k) at the SQP iterate's (k, v) of stage k, sparse: every row touches one or
 // two of the 8 stage variables, so instead of a dense 8-vector the loops visit the 12 row kinds in a fully
@@ -371,18 +203,6 @@ __host__ __device__ constexpr int row_kind(int k, int N, int fin, int j) {
 // (for_rows), where each kind, and with it the indices of its nonzero coefficients, is a compile-time
 // constant.  Adding only the nonzero terms, in the same order, gives the dense loops' values (a skipped
 // term is an exact zero).
-// the LDS slot of a row kind: its own, except the intermediate chunk's terminal row (k = N only), which takes
-// the u1-min slot (no stage has both), so a stage's rows fit in NR slots in row order
-__host__ __device__ constexpr int kind_slot(int kind) { return kind == ROW_STERM ? ROW_U1MIN : kind; }
-__host__ __device__ constexpr bool row_on(int kind, int k, int N, int fin) {
-    switch (kind) {
-        case ROW_VMIN: case ROW_VMAX: return !(fin && k == N);
-        case ROW_LATP: case ROW_LATM: return !(fin && k == N) && k > 0;
-        case ROW_KMIN: case ROW_KMAX: return k > 0;
-        case ROW_STERM: return k == N && !fin;
-        default: return k < N;
-    }
-}
 struct RowSp {
     int i0, i1;          // indices of the coefficients (i0 < i1)
     double c0, c1;
@@ -525,37 +345,6 @@ __device__ bool solve5(double M[25], double R[5 * NC]) {
             R[NC * c + j] = v / M[5 * c + c];
         }
     return true;
-}
-
-// H (3 x 3, symmetric positive definite) = L D L' with L unit lower triangular, stored as {1/d0, l10, 1/d1,
-// l20, l21, 1/d2}: no square roots, three divisions per factorisation and none in the solves, which sit on
-// the solves' dependent chains (oracle/plan_oracle.c uses the same form and rounding).  Fails (false) when a
-// pivot is not positive, the Cholesky condition.
-__device__ bool chol3(const double H[3][3], double L[6]) {
-    const double d0 = H[0][0];
-    if (!(d0 > 0.0)) return false;
-    L[0] = 1.0 / d0;
-    L[1] = H[1][0] * L[0];
-    const double d1 = H[1][1] - L[1] * H[1][0];
-    if (!(d1 > 0.0)) return false;
-    L[2] = 1.0 / d1;
-    L[3] = H[2][0] * L[0];
-    const double e21 = H[2][1] - L[3] * H[1][0];
-    L[4] = e21 * L[2];
-    const double d2 = H[2][2] - L[3] * H[2][0] - L[4] * e21;
-    if (!(d2 > 0.0)) return false;
-    L[5] = 1.0 / d2;
-    return true;
-}
-
-// b <- (L D L')^-1 b
-__device__ inline void chol3_solve(const double L[6], double b[3]) {
-    const double y0 = b[0];
-    const double y1 = b[1] - L[1] * y0;
-    const double y2 = b[2] - L[3] * y0 - L[4] * y1;
-    b[2] = y2 * L[5];
-    b[1] = y1 * L[2] - L[4] * b[2];
-    b[0] = y0 * L[0] - L[1] * b[1] - L[3] * b[2];
 }
 
 __host__ __device__ constexpr int hx(int i, int j) {   // packed index of the symmetric 8x8 (i <= j)
@@ -706,7 +495,7 @@ __device__ void interval_hess_fold(Ctx& X, int k, const double xa[5], const doub
         for (int i = 0; i < 5; ++i) v += Fm[5 * i + j] * y[i];
         yb[j] = v;
     }
-    hess_f(xm, km, k1m, k2m, y, Wm);
+    hess_f_folded(xm, km, k1m, k2m, y, Wm);
     {
         double WMa[25], WMb[25];
 #pragma unroll
@@ -742,16 +531,16 @@ __device__ void interval_hess_fold(Ctx& X, int k, const double xa[5], const doub
     }
     {
         double W[25];
-        hess_f(xa, ka, k1a, k2a, y, W);
+        hess_f_folded(xa, ka, k1a, k2a, y, W);
 #pragma unroll
         for (int i = 0; i < 25; ++i) Haa[i] += W[i];
-        hess_f(xa, ka, k1a, k2a, yb, W);
+        hess_f_folded(xa, ka, k1a, k2a, yb, W);
 #pragma unroll
         for (int i = 0; i < 25; ++i) Haa[i] = f6 * (Haa[i] + 4.0 * (h / 8.0) * W[i]);
-        hess_f(xb, kb, k1b, k2b, y, W);
+        hess_f_folded(xb, kb, k1b, k2b, y, W);
 #pragma unroll
         for (int i = 0; i < 25; ++i) Hbb[i] += W[i];
-        hess_f(xb, kb, k1b, k2b, yb, W);
+        hess_f_folded(xb, kb, k1b, k2b, yb, W);
 #pragma unroll
         for (int i = 0; i < 25; ++i) Hbb[i] = f6 * (Hbb[i] - 4.0 * (h / 8.0) * W[i]);
     }

@@ -2,7 +2,8 @@
 solve on the CPU behind the same C ABI (VERDICT r05 "missing" 4: the reference's planner is CPU code,
 trajectory_planning.py:381-387).  Checked here, without a GPU:
   - bit for bit against the planner oracle (oracle/plan_oracle.c, same algorithm and IEEE operation sequence)
-    on a mixed batch of intermediate and final chunks (every output: X, U, S, status, iterations, QPs);
+    on a mixed batch of intermediate and final chunks (every output: X, U, S, status, iterations, QPs), and on a
+    smaller one whose trace shows the exact-Hessian QPs (the host's association of hess_f, csrc/plan_model.h);
   - the route functions (k_ref_fun, its derivative, v_max_fun) against the oracle's;
   - plan_optimize's receding-horizon loop against the package loop driven by the oracle (identical plans);
   - the drop-in's full trajectory on the host backend passes the restated reference_trajectory_check;
@@ -49,6 +50,28 @@ def test_host_backend_equals_oracle_bit_for_bit(env):
         assert np.array_equal(got[k], ref[k]), k
     print("statuses", np.bincount(got["status"], minlength=5).tolist(), "QPs", int(got["sqp"].sum()))
     assert np.isin(got["status"], (0, 4)).mean() >= 0.9
+
+
+def test_exact_hessian_qps_equal_oracle_bit_for_bit(env, capfd, monkeypatch):
+    """The host forms the defects' second derivatives by hess_f_scaled (csrc/plan_model.h), the oracle's association,
+    beside the kernels' hess_f_folded: 16 chunks of every horizon and both kinds, in which the backend's own trace
+    (PLAN_TRACE) shows exact-Hessian QPs taken by chunks that then converge, equal the oracle in every bit."""
+    mpcplan, PO, W = env
+    r = W.plan_route("synth1")
+    x0, st, fin, N = _batch(W, r, n=16)
+    assert set(N.tolist()) == {13, 16, 20, 26} and 0 < fin.sum() < len(fin)
+    monkeypatch.setenv("PLAN_TRACE", "1")
+    pl = mpcplan.Planner(r, mpcplan.default_params(N=int(N.max())), device=-1)
+    got = pl.solve_chunks(x0, st, fin, N)
+    monkeypatch.delenv("PLAN_TRACE")
+    trace = capfd.readouterr().err
+    ref = PO.PlanOracle(r).solve_batch(PO.default_params(N=int(N.max())), x0, st, fin, N=N, num_threads=4)
+    for k in ("X", "U", "S", "status", "iters", "sqp"):
+        assert np.array_equal(got[k], ref[k]), k
+    solved = np.isin(got["status"], (0, 4))
+    # a chunk's QP it is exact once the step before it is <= EXACT_STEP: no solved chunk stops before a second QP
+    assert solved.all() and got["sqp"][solved].min() >= 2
+    assert trace.count(" exact qp ") >= len(N), trace[-2000:]
 
 
 def test_host_route_functions_equal_oracle(env):
