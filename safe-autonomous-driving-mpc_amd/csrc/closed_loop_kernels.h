@@ -136,11 +136,5 @@ __global__ void mpc_pose_kernel(DevTable tab, int n, const double* __restrict__ 
                                 double* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double si = s[i];
-    if (si > tab.smax) si = tab.smax;
-    const int j = seg_t(tab, tab.T, si);
-    const double xr = lin(tab.s, tab.gx, j, si), yr = lin(tab.s, tab.gy, j, si), psi = lin(tab.s, tab.gpsi, j, si);
-    out[3 * (size_t)i] = xr - d[i] * sin(psi);
-    out[3 * (size_t)i + 1] = yr + d[i] * cos(psi);
-    out[3 * (size_t)i + 2] = psi;
+    global_pose(tab, s[i], d[i], out + 3 * (size_t)i);
 }

@@ -6,7 +6,8 @@
 // Gauss-Newton SQP with warm crossovers and its stopping rules) and the same outputs
 // and status codes as the HIP kernels, computed per instance in IEEE double on host threads (batch split
 // over std::thread workers, each with its own scratch).  It is product code: it shares the trajectory table
-// builder (host_table.h) with the device path and nothing with the test oracle.
+// builder (host_table.h), the model (tracker_model.h) and the loop steps (loop_steps.h) with the device path and
+// nothing with the test oracle.
 //
 // Reference functions restated here (medinammartin3/Safe-Autonomous-Driving-MPC):
 //   warm start  trajectory_tracking.py:224-246      predict     :87-114 (dynamics :50-67)
@@ -36,13 +37,6 @@ namespace mpcqp_cpu {
 using mpcqp_host::HostTable;
 
 constexpr int kMaxN = MPC_MAX_N;
-constexpr int kRows = 9;          // soft rows per stage: lane +-d, +-(d + L/2 o), +-(d + L o), 2 obstacle, v >= 0
-constexpr int kBox = 4;           // box rows per control: +u1, -u1, +u2, -u2
-constexpr double kTau = 0.995;    // the device constants (TAU; solve_kernel.h: START_SHIFT, POLISH_*, SQP_*)
-constexpr double kStartShift = 3.0;
-constexpr double kMuCheck = 1e-4;     // interior-point checkpoint (solve_kernel.h: MU_CHECK, CHECK_SEP, CHECK_ROUNDS)
-constexpr double kCheckSep = 100.0;
-constexpr int kCheckRounds = 2;
 // MPC_CHECKPOINT=0 in the environment switches the checkpoint off (A/B; the device kernels read the same flag)
 inline bool checkpoint_on() {
     static const bool on = [] {
@@ -51,70 +45,8 @@ inline bool checkpoint_on() {
     }();
     return on;
 }
-constexpr double kDelta = 1e-11;
-constexpr int kRefine = 2;
-constexpr int kPolishRounds = 6;
-constexpr int kXoRounds = 1;
-constexpr double kCycleRel = 1e-6;
-constexpr int kInfStreak = 5;
-constexpr double kBoxSign[kBox] = {1.0, -1.0, 1.0, -1.0};
-constexpr int kBoxComp[kBox] = {0, 0, 1, 1};
-
-// ---------------------------------------------------------------------------------------------
-// reference signal on the host table (the device lookups' arithmetic: scipy interp1d linear, extrapolate)
-// ---------------------------------------------------------------------------------------------
-struct Ref {
-    const HostTable* h;
-    const double *s, *d, *o, *k, *v, *u1, *u2, *gx, *gy, *gpsi;
-    explicit Ref(const HostTable& t) : h(&t) {
-        const double* b = t.buf.data();
-        const size_t T = (size_t)t.T, tu = (size_t)t.tu;
-        s = b; d = b + T; o = b + 2 * T; k = b + 3 * T; v = b + 4 * T;
-        u1 = b + 5 * T; u2 = u1 + tu;
-        gx = b + 5 * T + 2 * tu; gy = gx + T; gpsi = gy + T;
-    }
-    double lin(const double* y, int i, double x) const {
-        const double slope = (y[i] - y[i - 1]) / (s[i] - s[i - 1]);
-        return slope * (x - s[i - 1]) + y[i - 1];
-    }
-    double slope(const double* y, int i) const { return (y[i] - y[i - 1]) / (s[i] - s[i - 1]); }
-    // get_state (trajectory_loader.py:86-93); slopes of (d, o, k, v) for the Gauss-Newton model, 0 past s_max
-    void state(double x, double out[5], double sl[4] = nullptr) const {
-        if (x >= h->smax) {
-            for (int j = 0; j < 5; ++j) out[j] = h->last[j];
-            if (sl) sl[0] = sl[1] = sl[2] = sl[3] = 0.0;
-            return;
-        }
-        const int i = mpcqp_host::seg_host(*h, h->T, x);
-        out[0] = x;
-        out[1] = lin(d, i, x);
-        out[2] = lin(o, i, x);
-        out[3] = lin(k, i, x);
-        out[4] = lin(v, i, x);
-        if (sl) {
-            sl[0] = slope(d, i);
-            sl[1] = slope(o, i);
-            sl[2] = slope(k, i);
-            sl[3] = slope(v, i);
-        }
-    }
-    // get_control (trajectory_loader.py:95-102)
-    void control(double x, double out[2]) const {
-        if (x >= h->smax) { out[0] = out[1] = 0.0; return; }
-        const int i = mpcqp_host::seg_host(*h, h->tu, x);
-        out[0] = lin(u1, i, x);
-        out[1] = lin(u2, i, x);
-    }
-    // get_global_pose (trajectory_loader.py:104-116)
-    void pose(double x, double dd, double out[3]) const {
-        if (x > h->smax) x = h->smax;
-        const int j = mpcqp_host::seg_host(*h, h->T, x);
-        const double xr = lin(gx, j, x), yr = lin(gy, j, x), psi = lin(gpsi, j, x);
-        out[0] = xr - dd * std::sin(psi);
-        out[1] = yr + dd * std::cos(psi);
-        out[2] = psi;
-    }
-};
+constexpr double kBoxSign[NBOX] = {1.0, -1.0, 1.0, -1.0};
+constexpr int kBoxComp[NBOX] = {0, 0, 1, 1};
 
 // ---------------------------------------------------------------------------------------------
 // one instance: QP(ubar) stage data, interior-point state, Riccati factors, directions
@@ -127,25 +59,25 @@ struct StageQp {
     double a12[kMaxN], a14[kMaxN], a20[kMaxN], a23[kMaxN], a24[kMaxN];   // A_k = I + J'_k (J'(0,4) = dt)
     double Q[kMaxN + 1][5][5], q[kMaxN + 1][5];                // Gauss-Newton state cost, stages 1..N
     double R[2], r[kMaxN][2];                                  // control cost
-    double C[kRows][5];                                        // soft-row coefficients (C x + xi >= b + s)
-    bool on[kRows];
-    double b[kMaxN + 1][kRows];
-    double bb[kMaxN][kBox];                                    // box rows (hard)
+    double C[NROW][5];                                        // soft-row coefficients (C x + xi >= b + s)
+    bool on[NROW];
+    double b[kMaxN + 1][NROW];
+    double bb[kMaxN][NBOX];                                    // box rows (hard)
 };
 struct IpState {
     double du[2 * kMaxN];
-    double s[kMaxN + 1][kRows], l[kMaxN + 1][kRows], xi[kMaxN + 1][kRows], nu[kMaxN + 1][kRows];
-    double sb[kMaxN][kBox], lb[kMaxN][kBox];
+    double s[kMaxN + 1][NROW], l[kMaxN + 1][NROW], xi[kMaxN + 1][NROW], nu[kMaxN + 1][NROW];
+    double sb[kMaxN][NBOX], lb[kMaxN][NBOX];
 };
 struct Factors {
     double K[kMaxN][2][5], Lc[kMaxN][3];                        // feedback, Cholesky factor (l00, l10, l11) of S
     double Qt[kMaxN + 1][5][5], Rt[kMaxN][2];                  // augmented stage Hessians
-    double d[kMaxN + 1][kRows], db[kMaxN][kBox];               // barrier diagonals
+    double d[kMaxN + 1][NROW], db[kMaxN][NBOX];               // barrier diagonals
 };
 struct Direction {
     double du[2 * kMaxN], dX[kMaxN + 1][5];
-    double dl[kMaxN + 1][kRows], ds[kMaxN + 1][kRows], dxi[kMaxN + 1][kRows], dnu[kMaxN + 1][kRows];
-    double dlb[kMaxN][kBox], dsb[kMaxN][kBox];
+    double dl[kMaxN + 1][NROW], ds[kMaxN + 1][NROW], dxi[kMaxN + 1][NROW], dnu[kMaxN + 1][NROW];
+    double dlb[kMaxN][NBOX], dsb[kMaxN][NBOX];
 };
 
 static inline double dot5(const double a[5], const double b[5]) {
@@ -154,7 +86,7 @@ static inline double dot5(const double a[5], const double b[5]) {
 
 class Worker {
 public:
-    Worker(const Ref& ref, const mpc_params& p) : R_(ref), p_(p) {}
+    Worker(const DevTable& ref, const mpc_params& p) : R_(ref), p_(p), K_(model_params(p)) {}
 
     // TrajectoryTracker.solve (trajectory_tracking.py:213-263) for one instance; returns the status code
     int solve(const double x0[5], const double* obs, int nobs, const double* ubar, double* u0, double* U,
@@ -184,7 +116,7 @@ public:
             ninf = status == MPC_INFEASIBLE ? ninf + 1 : 0;
             if (nsqp > 1) {
                 if (step <= p_.sqp_tol) { conv = true; break; }                  // re-linearisation converged
-                if (p_.sqp_tol > 0.0 && ((it >= 2 && back2 <= kCycleRel * step) || ninf >= kInfStreak)) break;
+                if (p_.sqp_tol > 0.0 && ((it >= 2 && back2 <= SQP_CYCLE_REL * step) || ninf >= SQP_INF_STREAK)) break;
             }
         }
         if (U) std::memcpy(U, uo, sizeof(double) * 2 * N);
@@ -195,19 +127,13 @@ public:
         return status;
     }
 
-    // warm start ubar (trajectory_tracking.py:224-246): reference controls along s advanced at the current
-    // speed; a sticky brake once an obstacle is within brake_distance
+    // warm start ubar (trajectory_tracking.py:224-246): loop_steps.h's reference warm start, every stage of it
     void warm_start(const double x0[5], const double* obs, int nobs, double* ub) const {
-        double s = x0[0];
-        bool brake = false;
+        WarmRef w = warm_ref_begin(x0);
         for (int j = 0; j < p_.N; ++j) {
-            for (int i = 0; i < nobs; ++i)
-                if ((obs[2 * i] - s) < p_.brake_distance) brake = true;
-            double ur[2];
-            R_.control(s, ur);
-            ub[2 * j] = ur[0];
-            ub[2 * j + 1] = brake ? p_.brake_accel : ur[1];
-            s += x0[4] * p_.dt;
+            warm_ref_advance(w, j, p_.dt, obs, nobs, p_.brake_distance);
+            warm_ref_control(w, p_.brake_accel, [&](double s, double* ur) { get_control(R_, s, ur); }, ub[2 * j],
+                             ub[2 * j + 1]);
         }
     }
 
@@ -219,22 +145,23 @@ public:
         std::memcpy(X[0], x0, sizeof(x));
         for (int k = 0; k < p_.N; ++k) {
             double st[5];
-            R_.state(x[0], st);
+            get_state(R_, x[0], st);
             plant_step(x, dt, U[2 * k], U[2 * k + 1], st[3]);
             std::memcpy(X[k + 1], x, sizeof(x));
         }
     }
 
 private:
-    const Ref& R_;
+    const DevTable& R_;
     const mpc_params& p_;
+    const KParams K_;        // the model derived from p_ (tracker_model.h)
     StageQp q_;
     IpState S_, Z_, T_, C_;
     Factors F_;
     Direction D_, Da_;
-    unsigned char cls_[kMaxN + 1][kRows], clb_[kMaxN][kBox];      // 0 inactive, 1 active, 2 violated
-    unsigned char flip_[kMaxN + 1][kRows], flipb_[kMaxN][kBox];
-    unsigned char last_cls_[kMaxN + 1][kRows], last_clb_[kMaxN][kBox];   // the SQP's warm crossover
+    unsigned char cls_[kMaxN + 1][NROW], clb_[kMaxN][NBOX];      // 0 inactive, 1 active, 2 violated
+    unsigned char flip_[kMaxN + 1][NROW], flipb_[kMaxN][NBOX];
+    unsigned char last_cls_[kMaxN + 1][NROW], last_clb_[kMaxN][NBOX];   // the SQP's warm crossover
     double xo_du_[2 * kMaxN];   // du of the last cold crossover solve: the unconstrained optimum (interior-point start)
 
     // ---- QP(ubar): Gauss-Newton model of cost/constraints around the nominal rollout
@@ -251,13 +178,14 @@ private:
         for (int k = 0; k < N; ++k) {
             const double* x = Q.Xb[k];
             double st[5], sl[4];
-            R_.state(x[0], st, sl);
-            const double dk = gn ? sl[2] : 0.0;
-            Q.a12[k] = dt * x[4];
-            Q.a14[k] = dt * x[2];
-            Q.a20[k] = dt * (-x[4] * dk);
-            Q.a23[k] = dt * x[4];
-            Q.a24[k] = dt * (x[3] - st[3]);
+            get_state(R_, x[0], st, sl);
+            double a[5];
+            stage_A(x, dt, st[3], gn ? sl[2] : 0.0, a);
+            Q.a12[k] = a[0];
+            Q.a14[k] = a[1];
+            Q.a20[k] = a[2];
+            Q.a23[k] = a[3];
+            Q.a24[k] = a[4];
         }
         const double w[3] = {p_.w_d, p_.w_o, p_.w_v};
         const int comp[3] = {1, 2, 4};
@@ -266,7 +194,7 @@ private:
         for (int k = 1; k <= N; ++k) {
             const double* x = Q.Xb[k];
             double st[5], sl[4];
-            R_.state(x[0], st, sl);
+            get_state(R_, x[0], st, sl);
             const double ref[3] = {st[1], st[2], st[4]};
             const double dref[3] = {gn ? sl[0] : 0.0, gn ? sl[1] : 0.0, gn ? sl[3] : 0.0};
             for (int j = 0; j < 3; ++j) {
@@ -287,38 +215,17 @@ private:
             Q.r[k][0] = Q.R[0] * ub[2 * k];
             Q.r[k][1] = Q.R[1] * ub[2 * k + 1];
         }
-        const double L = p_.wheelbase, h = p_.wheelbase / 2.0, tg = p_.max_time_2_obs;
-        const double sl = p_.lane_width / 2.0 - p_.vehicle_radius - p_.safe_lane_margin;   // :169
-        const double C[kRows][5] = {{0, 1, 0, 0, 0}, {0, -1, 0, 0, 0}, {0, 1, h, 0, 0},   {0, -1, -h, 0, 0},
-                                    {0, 1, L, 0, 0}, {0, -1, -L, 0, 0}, {-1, 0, 0, 0, 0}, {-1, 0, 0, 0, -tg},
-                                    {0, 0, 0, 0, 1}};
-        std::memcpy(Q.C, C, sizeof(C));
-        for (int j = 0; j < kRows; ++j) Q.on[j] = (j != 6 && j != 7) || Q.obs;
-        for (int k = 1; k <= N; ++k) {
-            const double* x = Q.Xb[k];
-            const double pv0 = x[1], pv1 = x[1] + h * x[2], pv2 = x[1] + L * x[2];
-            Q.b[k][0] = -sl - pv0;
-            Q.b[k][1] = -(sl - pv0);
-            Q.b[k][2] = -sl - pv1;
-            Q.b[k][3] = -(sl - pv1);
-            Q.b[k][4] = -sl - pv2;
-            Q.b[k][5] = -(sl - pv2);
-            Q.b[k][6] = Q.b[k][7] = 0.0;
-            if (Q.obs) {
-                // the obstacle rows of :194-204 for every obstacle collapse to the nearest predicted one
-                double shat = INFINITY;
-                for (int i = 0; i < nobs; ++i) shat = std::min(shat, obs[2 * i] + obs[2 * i + 1] * (k * dt));
-                Q.b[k][6] = -(shat - p_.obstacle_safety_distance - x[0]);
-                Q.b[k][7] = -(shat - x[0] - tg * x[4]);
-            }
-            Q.b[k][8] = -x[4];
+        // the rows and boxes: tracker_model.h's coefficients (with a zero k entry) and values
+        for (int j = 0; j < NROW; ++j) {
+            double c[4];
+            row_coef(j, K_.L / 2.0, K_.L, K_.tgap, c);
+            const double c5[5] = {c[0], c[1], c[2], 0.0, c[3]};
+            std::memcpy(Q.C[j], c5, sizeof(c5));
+            Q.on[j] = row_exists(j, Q.obs);
         }
-        for (int k = 0; k < N; ++k) {
-            Q.bb[k][0] = p_.u_min[0] - ub[2 * k];
-            Q.bb[k][1] = -(p_.u_max[0] - ub[2 * k]);
-            Q.bb[k][2] = p_.u_min[1] - ub[2 * k + 1];
-            Q.bb[k][3] = -(p_.u_max[1] - ub[2 * k + 1]);
-        }
+        for (int k = 1; k <= N; ++k)
+            row_values(K_, Q.Xb[k], nearest_obstacle(obs, nobs, k, dt), Q.obs, Q.b[k]);
+        for (int k = 0; k < N; ++k) box_values(K_, ub[2 * k], ub[2 * k + 1], Q.bb[k]);
     }
 
     // ---- linear model pieces: x_{k+1} = A_k x_k + B u_k, B = dt e3 e1' + dt e4 e2'
@@ -445,7 +352,7 @@ private:
         const StageQp& Q = q_;
         for (int k = 1; k <= Q.N; ++k) {
             std::memcpy(F_.Qt[k], Q.Q[k], sizeof(F_.Qt[k]));
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!Q.on[j]) continue;
                 const double d = S_.s[k][j] / S_.l[k][j] + S_.xi[k][j] / S_.nu[k][j];
                 F_.d[k][j] = d;
@@ -457,7 +364,7 @@ private:
         for (int t = 0; t < Q.N; ++t) {
             F_.Rt[t][0] = Q.R[0];
             F_.Rt[t][1] = Q.R[1];
-            for (int j = 0; j < kBox; ++j) {
+            for (int j = 0; j < NBOX; ++j) {
                 const double d = S_.sb[t][j] / S_.lb[t][j];
                 F_.db[t][j] = d;
                 F_.Rt[t][kBoxComp[j]] += 1.0 / d;
@@ -468,15 +375,15 @@ private:
 
     // Newton direction for complementarity targets r4 (s lam), r5 (xi nu), r4b (box), residuals rp/rpb/rx and
     // the dual residual pieces y (stages) / z (controls), eliminated row-wise onto the Riccati system
-    void newton(const double (*rp)[kRows], const double (*rpb)[kBox], const double (*rx)[kRows],
-                const double (*y)[5], const double (*z)[2], const double (*r4)[kRows], const double (*r5)[kRows],
-                const double (*r4b)[kBox], Direction& D) {
+    void newton(const double (*rp)[NROW], const double (*rpb)[NBOX], const double (*rx)[NROW],
+                const double (*y)[5], const double (*z)[2], const double (*r4)[NROW], const double (*r5)[NROW],
+                const double (*r4b)[NBOX], Direction& D) {
         const StageQp& Q = q_;
         const int N = Q.N;
-        double qh[kMaxN + 1][5], gh[kMaxN][2], rh[kMaxN + 1][kRows], rhb[kMaxN][kBox];
+        double qh[kMaxN + 1][5], gh[kMaxN][2], rh[kMaxN + 1][NROW], rhb[kMaxN][NBOX];
         for (int k = 1; k <= N; ++k) {
             for (int a = 0; a < 5; ++a) qh[k][a] = -y[k][a];
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!Q.on[j]) continue;
                 const double v = -rp[k][j] - r4[k][j] / S_.l[k][j] + (r5[k][j] + S_.xi[k][j] * rx[k][j]) / S_.nu[k][j];
                 rh[k][j] = v;
@@ -487,7 +394,7 @@ private:
         for (int t = 0; t < N; ++t) {
             gh[t][0] = -z[t][0];
             gh[t][1] = -z[t][1];
-            for (int j = 0; j < kBox; ++j) {
+            for (int j = 0; j < NBOX; ++j) {
                 const double v = -rpb[t][j] - r4b[t][j] / S_.lb[t][j];
                 rhb[t][j] = v;
                 gh[t][kBoxComp[j]] += kBoxSign[j] * v / F_.db[t][j];
@@ -495,7 +402,7 @@ private:
         }
         riccati_solve(qh, gh, D);
         for (int k = 1; k <= N; ++k)
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!Q.on[j]) continue;
                 const double dl = (rh[k][j] - dot5(Q.C[j], D.dX[k])) / F_.d[k][j];
                 D.dl[k][j] = dl;
@@ -505,7 +412,7 @@ private:
                 D.dxi[k][j] = -(r5[k][j] + S_.xi[k][j] * dn) / S_.nu[k][j];
             }
         for (int t = 0; t < N; ++t)
-            for (int j = 0; j < kBox; ++j) {
+            for (int j = 0; j < NBOX; ++j) {
                 const double dl = (rhb[t][j] - kBoxSign[j] * D.du[2 * t + kBoxComp[j]]) / F_.db[t][j];
                 D.dlb[t][j] = dl;
                 D.dsb[t][j] = -(r4b[t][j] + S_.sb[t][j] * dl) / S_.lb[t][j];
@@ -517,7 +424,7 @@ private:
         double a = 1.0;
         auto ratio = [&a](double v, double dv) { if (dv < 0.0 && -v / dv < a) a = -v / dv; };
         for (int k = 1; k <= q_.N; ++k)
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!q_.on[j]) continue;
                 ratio(S_.s[k][j], D.ds[k][j]);
                 ratio(S_.l[k][j], D.dl[k][j]);
@@ -525,7 +432,7 @@ private:
                 ratio(S_.nu[k][j], D.dnu[k][j]);
             }
         for (int t = 0; t < q_.N; ++t)
-            for (int j = 0; j < kBox; ++j) {
+            for (int j = 0; j < NBOX; ++j) {
                 ratio(S_.sb[t][j], D.dsb[t][j]);
                 ratio(S_.lb[t][j], D.dlb[t][j]);
             }
@@ -535,13 +442,13 @@ private:
     double comp_after(const Direction& D, double a) const {
         double c = 0.0;
         for (int k = 1; k <= q_.N; ++k)
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!q_.on[j]) continue;
                 c += (S_.s[k][j] + a * D.ds[k][j]) * (S_.l[k][j] + a * D.dl[k][j]) +
                      (S_.xi[k][j] + a * D.dxi[k][j]) * (S_.nu[k][j] + a * D.dnu[k][j]);
             }
         for (int t = 0; t < q_.N; ++t)
-            for (int j = 0; j < kBox; ++j) c += (S_.sb[t][j] + a * D.dsb[t][j]) * (S_.lb[t][j] + a * D.dlb[t][j]);
+            for (int j = 0; j < NBOX; ++j) c += (S_.sb[t][j] + a * D.dsb[t][j]) * (S_.lb[t][j] + a * D.dlb[t][j]);
         return c;
     }
 
@@ -555,7 +462,7 @@ private:
         const int N = Q.N;
         const double rho = Q.rho;
         for (int k = 1; k <= N; ++k)
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 unsigned char c = 0;
                 if (Q.on[j] && from != 1) {
                     if (from == 2) c = last_cls_[k][j];
@@ -565,7 +472,7 @@ private:
                 cls_[k][j] = c;
             }
         for (int t = 0; t < N; ++t)
-            for (int j = 0; j < kBox; ++j)
+            for (int j = 0; j < NBOX; ++j)
                 clb_[t][j] = from == 1 ? 0 : (from == 2 ? last_clb_[t][j] : (X.lb[t][j] > X.sb[t][j]));
         bool accepted = false;
         double Xs[kMaxN + 1][5];
@@ -574,77 +481,77 @@ private:
             std::memcpy(&W, &X, sizeof(W));
             for (int k = 1; k <= N; ++k) {
                 std::memcpy(F_.Qt[k], Q.Q[k], sizeof(F_.Qt[k]));
-                for (int j = 0; j < kRows; ++j)
+                for (int j = 0; j < NROW; ++j)
                     if (Q.on[j] && cls_[k][j] == 1) {
                         for (int a = 0; a < 5; ++a)
-                            for (int c = 0; c < 5; ++c) F_.Qt[k][a][c] += Q.C[j][a] * Q.C[j][c] / kDelta;
+                            for (int c = 0; c < 5; ++c) F_.Qt[k][a][c] += Q.C[j][a] * Q.C[j][c] / POLISH_DELTA;
                         if (!(X.l[k][j] > 0.0)) W.l[k][j] = 0.0;
                     }
             }
             for (int t = 0; t < N; ++t) {
                 F_.Rt[t][0] = Q.R[0];
                 F_.Rt[t][1] = Q.R[1];
-                for (int j = 0; j < kBox; ++j)
-                    if (clb_[t][j]) F_.Rt[t][kBoxComp[j]] += 1.0 / kDelta;
+                for (int j = 0; j < NBOX; ++j)
+                    if (clb_[t][j]) F_.Rt[t][kBoxComp[j]] += 1.0 / POLISH_DELTA;
             }
             riccati_factor();
             // from the all-inactive classification (the crossover) the first solve is the unconstrained LQR's exact
             // optimum: one solve, nothing to refine (oracle polish_from, kernel MODE_XO)
-            const int nref = from == 1 ? 1 : kRefine;
+            const int nref = from == 1 ? 1 : POLISH_REFINE;
             for (int r = 0; r <= nref; ++r) {
                 rollout(W.du, Xs);
-                double qh[kMaxN + 1][5], gh[kMaxN][2], r2[kMaxN + 1][kRows], r2b[kMaxN][kBox];
+                double qh[kMaxN + 1][5], gh[kMaxN][2], r2[kMaxN + 1][NROW], r2b[kMaxN][NBOX];
                 for (int k = 1; k <= N; ++k) {
                     for (int a = 0; a < 5; ++a) {
                         double acc = Q.q[k][a];
                         for (int c = 0; c < 5; ++c) acc += Q.Q[k][a][c] * Xs[k][c];
                         qh[k][a] = -acc;
                     }
-                    for (int j = 0; j < kRows; ++j) {
+                    for (int j = 0; j < NROW; ++j) {
                         if (!Q.on[j] || cls_[k][j] == 0) continue;
                         const double lam = cls_[k][j] == 2 ? rho : W.l[k][j];
                         for (int a = 0; a < 5; ++a) qh[k][a] += lam * Q.C[j][a];
                         if (cls_[k][j] == 1) {
                             r2[k][j] = Q.b[k][j] - dot5(Q.C[j], Xs[k]);
-                            for (int a = 0; a < 5; ++a) qh[k][a] += Q.C[j][a] * r2[k][j] / kDelta;
+                            for (int a = 0; a < 5; ++a) qh[k][a] += Q.C[j][a] * r2[k][j] / POLISH_DELTA;
                         }
                     }
                 }
                 for (int t = 0; t < N; ++t) {
                     gh[t][0] = -(Q.R[0] * W.du[2 * t] + Q.r[t][0]);
                     gh[t][1] = -(Q.R[1] * W.du[2 * t + 1] + Q.r[t][1]);
-                    for (int j = 0; j < kBox; ++j) {
+                    for (int j = 0; j < NBOX; ++j) {
                         if (!clb_[t][j]) continue;
                         const double sg = kBoxSign[j];
                         gh[t][kBoxComp[j]] += sg * W.lb[t][j];
                         r2b[t][j] = Q.bb[t][j] - sg * W.du[2 * t + kBoxComp[j]];
-                        gh[t][kBoxComp[j]] += sg * r2b[t][j] / kDelta;
+                        gh[t][kBoxComp[j]] += sg * r2b[t][j] / POLISH_DELTA;
                     }
                 }
                 if (r == nref) break;
                 riccati_solve(qh, gh, D_);
                 for (int i = 0; i < 2 * N; ++i) W.du[i] += D_.du[i];
                 for (int k = 1; k <= N; ++k)
-                    for (int j = 0; j < kRows; ++j)
-                        if (Q.on[j] && cls_[k][j] == 1) W.l[k][j] += (r2[k][j] - dot5(Q.C[j], D_.dX[k])) / kDelta;
+                    for (int j = 0; j < NROW; ++j)
+                        if (Q.on[j] && cls_[k][j] == 1) W.l[k][j] += (r2[k][j] - dot5(Q.C[j], D_.dX[k])) / POLISH_DELTA;
                 for (int t = 0; t < N; ++t)
-                    for (int j = 0; j < kBox; ++j)
-                        if (clb_[t][j]) W.lb[t][j] += (r2b[t][j] - kBoxSign[j] * D_.du[2 * t + kBoxComp[j]]) / kDelta;
+                    for (int j = 0; j < NBOX; ++j)
+                        if (clb_[t][j]) W.lb[t][j] += (r2b[t][j] - kBoxSign[j] * D_.du[2 * t + kBoxComp[j]]) / POLISH_DELTA;
             }
             // the crossover's solve is the unconstrained optimum of QP(ubar): kept for the interior-point start
             if (from == 1 && round == 0) std::memcpy(xo_du_, W.du, sizeof(double) * 2 * N);
             // KKT consistency of the solved point
             double lmax = 1.0;
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j)
+                for (int j = 0; j < NROW; ++j)
                     if (Q.on[j] && cls_[k][j] == 1) lmax = std::max(lmax, std::fabs(W.l[k][j]));
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j)
+                for (int j = 0; j < NBOX; ++j)
                     if (clb_[t][j]) lmax = std::max(lmax, std::fabs(W.lb[t][j]));
             int nviol = 0;
             bool offending = false;
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     flip_[k][j] = 0;
                     if (!Q.on[j]) continue;
                     const double bsc = 1.0 + std::fabs(Q.b[k][j]);
@@ -663,7 +570,7 @@ private:
                     offending = offending || bad;
                 }
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j) {
+                for (int j = 0; j < NBOX; ++j) {
                     const double bsc = 1.0 + std::fabs(Q.bb[t][j]);
                     const double r = kBoxSign[j] * W.du[2 * t + kBoxComp[j]] - Q.bb[t][j];
                     const bool bad = clb_[t][j] ? (W.lb[t][j] < -1e-9 * lmax || std::fabs(r) > 1e-7 * bsc)
@@ -681,10 +588,10 @@ private:
                 break;
             }
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j)
+                for (int j = 0; j < NROW; ++j)
                     if (flip_[k][j]) cls_[k][j] = cls_[k][j] == 1 ? (W.l[k][j] > rho ? 2 : 0) : 1;
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j)
+                for (int j = 0; j < NBOX; ++j)
                     if (flipb_[t][j]) clb_[t][j] = !clb_[t][j];
         }
         std::memcpy(last_cls_, cls_, sizeof(last_cls_));
@@ -702,14 +609,14 @@ private:
         if (p_.polish >= 2) {
             std::memset(&Z_, 0, sizeof(Z_));
             bool inf = false;
-            if (active_set(Z_, warm ? 2 : 1, kXoRounds, inf)) {
+            if (active_set(Z_, warm ? 2 : 1, XO_ROUNDS, inf)) {
                 std::memcpy(S_.du, Z_.du, sizeof(double) * 2 * N);
                 return inf ? MPC_INFEASIBLE : MPC_OK;
             }
         }
         int nsoft = 0;
-        for (int j = 0; j < kRows; ++j) nsoft += Q.on[j];
-        const double Mtot = (double)(2 * nsoft * N + kBox * N);
+        for (int j = 0; j < NROW; ++j) nsoft += Q.on[j];
+        const double Mtot = (double)(2 * nsoft * N + NBOX * N);
         // start centred at the unconstrained optimum of QP(ubar) (one factorisation and solve without rows), or
         // at du = 0 when the soft rows are less violated there:
         // slack max(r, 0) + shift, elastic slack max(-r, 0) + shift for the row value r there, the multiplier
@@ -739,7 +646,7 @@ private:
             // primal point: the unconstrained optimum, or du = 0 (ubar) when the soft rows are less violated there
             double v_unc = 0.0, v_bar = 0.0;
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     if (!Q.on[j]) continue;
                     const double r = dot5(Q.C[j], X[k]) - Q.b[k][j];
                     v_unc += r < 0.0 ? -r : 0.0;
@@ -752,10 +659,10 @@ private:
         }
         double bscale = 0.0, rowc = 0.0;
         for (int k = 1; k <= N; ++k)
-            for (int j = 0; j < kRows; ++j) {
+            for (int j = 0; j < NROW; ++j) {
                 if (!Q.on[j]) continue;
                 const double r = dot5(Q.C[j], X[k]) - Q.b[k][j];
-                const double sv = (r > 0.0 ? r : 0.0) + kStartShift, xi = (r < 0.0 ? -r : 0.0) + kStartShift;
+                const double sv = (r > 0.0 ? r : 0.0) + START_SHIFT, xi = (r < 0.0 ? -r : 0.0) + START_SHIFT;
                 S_.s[k][j] = sv;
                 S_.xi[k][j] = xi;
                 S_.l[k][j] = rho * xi / (sv + xi);
@@ -765,7 +672,7 @@ private:
             }
         const double mrow = rowc / (double)(nsoft * N);
         for (int t = 0; t < N; ++t)
-            for (int j = 0; j < kBox; ++j) {
+            for (int j = 0; j < NBOX; ++j) {
                 const double v = kBoxSign[j] * S_.du[2 * t + kBoxComp[j]] - Q.bb[t][j];
                 S_.sb[t][j] = v > 1.0 ? v : 1.0;
                 S_.lb[t][j] = mrow / S_.sb[t][j];
@@ -773,8 +680,8 @@ private:
             }
         double y[kMaxN + 1][5], yc[kMaxN + 1][5], ya[kMaxN + 1][5];
         double z[kMaxN][2], zc[kMaxN][2], za[kMaxN][2];
-        double rp[kMaxN + 1][kRows], rx[kMaxN + 1][kRows], rpb[kMaxN][kBox];
-        double r4[kMaxN + 1][kRows], r5[kMaxN + 1][kRows], r4b[kMaxN][kBox];
+        double rp[kMaxN + 1][NROW], rx[kMaxN + 1][NROW], rpb[kMaxN][NBOX];
+        double r4[kMaxN + 1][NROW], r5[kMaxN + 1][NROW], r4b[kMaxN][NBOX];
         int status = MPC_MAX_ITER, it = 0, stall = 0;
         bool checked = false;
         for (it = 0; it < p_.max_iter; ++it) {
@@ -787,7 +694,7 @@ private:
                     yc[k][a] = acc;
                     ya[k][a] = 0.0;
                 }
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     if (!Q.on[j]) continue;
                     for (int a = 0; a < 5; ++a) ya[k][a] -= S_.l[k][j] * Q.C[j][a];
                     rp[k][j] = dot5(Q.C[j], X[k]) + S_.xi[k][j] - S_.s[k][j] - Q.b[k][j];
@@ -805,7 +712,7 @@ private:
                 za[t][1] = -S_.lb[t][2] + S_.lb[t][3];
                 z[t][0] = zc[t][0] + za[t][0];
                 z[t][1] = zc[t][1] + za[t][1];
-                for (int j = 0; j < kBox; ++j) {
+                for (int j = 0; j < NBOX; ++j) {
                     rpb[t][j] = kBoxSign[j] * S_.du[2 * t + kBoxComp[j]] - S_.sb[t][j] - Q.bb[t][j];
                     rpmax = std::max(rpmax, std::fabs(rpb[t][j]));
                     comp += S_.sb[t][j] * S_.lb[t][j];
@@ -828,25 +735,25 @@ private:
                 status = rdmax <= 1e4 * p_.tol * (1.0 + sd) ? MPC_OK : MPC_NUMERICAL;
                 break;
             }
-            // checkpoint (once per QP): no near-tie between any row's slack and multiplier at mu <= kMuCheck ->
-            // kCheckRounds polish rounds from the iterate's classification; certified = the exact optimum, else
+            // checkpoint (once per QP): no near-tie between any row's slack and multiplier at mu <= MU_CHECK ->
+            // CHECK_ROUNDS polish rounds from the iterate's classification; certified = the exact optimum, else
             // the interior point continues from the unchanged iterate
-            if (p_.polish && !checked && mu <= kMuCheck && checkpoint_on()) {
+            if (p_.polish && !checked && mu <= MU_CHECK && checkpoint_on()) {
                 bool tie = false;
                 for (int k = 1; k <= N && !tie; ++k)
-                    for (int j = 0; j < kRows; ++j) {
+                    for (int j = 0; j < NROW; ++j) {
                         if (!Q.on[j]) continue;
                         const double s = S_.s[k][j], l = S_.l[k][j], x = S_.xi[k][j], n = S_.nu[k][j];
-                        if (!(s > kCheckSep * l || l > kCheckSep * s) || !(x > kCheckSep * n || n > kCheckSep * x)) tie = true;
+                        if (!(s > CHECK_SEP * l || l > CHECK_SEP * s) || !(x > CHECK_SEP * n || n > CHECK_SEP * x)) tie = true;
                     }
                 for (int t = 0; t < N && !tie; ++t)
-                    for (int j = 0; j < kBox; ++j)
-                        if (!(S_.sb[t][j] > kCheckSep * S_.lb[t][j] || S_.lb[t][j] > kCheckSep * S_.sb[t][j])) tie = true;
+                    for (int j = 0; j < NBOX; ++j)
+                        if (!(S_.sb[t][j] > CHECK_SEP * S_.lb[t][j] || S_.lb[t][j] > CHECK_SEP * S_.sb[t][j])) tie = true;
                 if (!tie) {
                     checked = true;
                     std::memcpy(&C_, &S_, sizeof(C_));
                     bool inf = false;
-                    if (active_set(C_, 0, kCheckRounds, inf)) {
+                    if (active_set(C_, 0, CHECK_ROUNDS, inf)) {
                         std::memcpy(S_.du, C_.du, sizeof(double) * 2 * N);
                         iters = it;
                         return inf ? MPC_INFEASIBLE : MPC_OK;
@@ -856,39 +763,39 @@ private:
             factor();
             // predictor (affine scaling)
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     r4[k][j] = S_.s[k][j] * S_.l[k][j];
                     r5[k][j] = S_.xi[k][j] * S_.nu[k][j];
                 }
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j) r4b[t][j] = S_.sb[t][j] * S_.lb[t][j];
+                for (int j = 0; j < NBOX; ++j) r4b[t][j] = S_.sb[t][j] * S_.lb[t][j];
             newton(rp, rpb, rx, y, z, r4, r5, r4b, Da_);
             const double aa = max_step(Da_);
             double sig = comp_after(Da_, aa) / Mtot / mu;
             sig = sig * sig * sig;
             // Mehrotra corrector
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     r4[k][j] = S_.s[k][j] * S_.l[k][j] + Da_.ds[k][j] * Da_.dl[k][j] - sig * mu;
                     r5[k][j] = S_.xi[k][j] * S_.nu[k][j] + Da_.dxi[k][j] * Da_.dnu[k][j] - sig * mu;
                 }
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j)
+                for (int j = 0; j < NBOX; ++j)
                     r4b[t][j] = S_.sb[t][j] * S_.lb[t][j] + Da_.dsb[t][j] * Da_.dlb[t][j] - sig * mu;
             newton(rp, rpb, rx, y, z, r4, r5, r4b, D_);
-            double a = std::min(1.0, kTau * max_step(D_));
+            double a = std::min(1.0, TAU * max_step(D_));
             double cnew = comp_after(D_, a);
             if (cnew > comp) {
                 // safeguard: the second-order term made it worse; take the plain centred direction
                 for (int k = 1; k <= N; ++k)
-                    for (int j = 0; j < kRows; ++j) {
+                    for (int j = 0; j < NROW; ++j) {
                         r4[k][j] = S_.s[k][j] * S_.l[k][j] - sig * mu;
                         r5[k][j] = S_.xi[k][j] * S_.nu[k][j] - sig * mu;
                     }
                 for (int t = 0; t < N; ++t)
-                    for (int j = 0; j < kBox; ++j) r4b[t][j] = S_.sb[t][j] * S_.lb[t][j] - sig * mu;
+                    for (int j = 0; j < NBOX; ++j) r4b[t][j] = S_.sb[t][j] * S_.lb[t][j] - sig * mu;
                 newton(rp, rpb, rx, y, z, r4, r5, r4b, D_);
-                a = std::min(1.0, kTau * max_step(D_));
+                a = std::min(1.0, TAU * max_step(D_));
                 cnew = comp_after(D_, a);
             }
             // breakdown guard: a step whose complementarity or control direction is not finite is not taken
@@ -898,7 +805,7 @@ private:
             stall = (mu < 1e-6 && cnew > 0.9 * comp) ? stall + 1 : 0;     // late-phase no-progress counter
             for (int i = 0; i < 2 * N; ++i) S_.du[i] += a * D_.du[i];
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j) {
+                for (int j = 0; j < NROW; ++j) {
                     if (!Q.on[j]) continue;
                     S_.s[k][j] += a * D_.ds[k][j];
                     S_.l[k][j] += a * D_.dl[k][j];
@@ -906,7 +813,7 @@ private:
                     S_.nu[k][j] += a * D_.dnu[k][j];
                 }
             for (int t = 0; t < N; ++t)
-                for (int j = 0; j < kBox; ++j) {
+                for (int j = 0; j < NBOX; ++j) {
                     S_.sb[t][j] += a * D_.dsb[t][j];
                     S_.lb[t][j] += a * D_.dlb[t][j];
                 }
@@ -920,11 +827,11 @@ private:
             }
         if (status == MPC_OK)
             for (int k = 1; k <= N; ++k)
-                for (int j = 0; j < kRows; ++j)
+                for (int j = 0; j < NROW; ++j)
                     if (Q.on[j] && S_.xi[k][j] > 1e-6 * (1.0 + std::fabs(Q.b[k][j]))) status = MPC_INFEASIBLE;
         if (p_.polish) {
             bool inf = false;
-            if (active_set(S_, 0, kPolishRounds, inf)) status = inf ? MPC_INFEASIBLE : MPC_OK;
+            if (active_set(S_, 0, POLISH_ROUNDS, inf)) status = inf ? MPC_INFEASIBLE : MPC_OK;
         }
         return status;
     }
@@ -948,116 +855,40 @@ inline void noise_draw(unsigned long long seed, int n, const long long* ego, con
     }
 }
 
-// mpc_evaluate_batch for one instance (include/mpcqp.h): the operation order of mpc_evaluate_kernel
-// (evaluate_kernel.h), stage by stage, so every output equals the device's bit for bit.  X is the rollout
-// predict(x0, U) [N+1][5]; mo the slab width (0 without obstacles), rw the row width 7 + params.max_obs;
+// mpc_evaluate_batch for one instance (include/mpcqp.h): tracker_model.h's steps of a control and of a stage, which
+// mpc_evaluate_kernel (evaluate_kernel.h) runs a lane each, folded here one after the other, so every output
+// equals the device's bit for bit.  X is the rollout predict(x0, U) [N+1][5]; rw the row width 7 + params.max_obs;
 // summary [MPC_EV_NQ], terms [5] and rows [N][rw] may be null.
-inline void evaluate_nmin(double& m, bool& nan, double r) {
-    if (!nan) {
-        if (r != r) nan = true;
-        else if (r < m) m = r;
-    }
-}
-inline void evaluate_one(const Ref& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
+inline void evaluate_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
                          int rw, const double* U, double* summary, double* terms, double* rows) {
     const int N = p.N;
-    const double inf = __builtin_inf(), qnan = __builtin_nan("");
-    const double sl = p.lane_width / 2.0 - p.vehicle_radius - p.safe_lane_margin;   // trajectory_tracking.py:169
-    const double osd = p.obstacle_safety_distance, tgap = p.max_time_2_obs, L = p.wheelbase;
+    const KParams P = model_params(p);
     double ct[kMaxN][5], part[kMaxN];
-    // group summary: np.argmin takes the first NaN row if there is one, else the first minimum
-    double gmin = inf, fl = inf, fo = inf, fv = inf, bx = 0.0, cnt = 0.0;
-    bool gnan = false, flnan = false, fonan = false, fvnan = false, bxnan = false;
+    EvRun run = ev_run_begin();
+    // np.argmin takes the first NaN row if there is one, else the first minimum
+    double gmin = INFINITY, cnt = 0.0;
+    bool gnan = false;
     int astage = 0, akind = 0;
-    for (int k = 0; k < N; ++k) {
-        const double u1 = U[2 * k], u2 = U[2 * k + 1];
-        ct[k][3] = p.w_u1 * (u1 * u1);
-        ct[k][4] = p.w_u2 * (u2 * u2);
-        const double e[4] = {p.u_min[0] - u1, u1 - p.u_max[0], p.u_min[1] - u2, u2 - p.u_max[1]};
-        for (int a = 0; a < 4; ++a) {
-            if (e[a] != e[a]) bxnan = true;
-            else if (e[a] > bx) bx = e[a];
-        }
-    }
+    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], ct[k], run);
     for (int j = 1; j <= N; ++j) {
         double st[5];
-        R.state(X[j][0], st);
-        const double s = X[j][0], d = X[j][1], o = X[j][2], v = X[j][4];
-        const double ed = d - st[1], eo = o - st[2], ev = v - st[4];
-        ct[j - 1][0] = p.w_d * (ed * ed);
-        ct[j - 1][1] = p.w_o * (eo * eo);
-        ct[j - 1][2] = p.w_v * (ev * ev);
-        double smin = inf, p1 = 0.0;
-        bool snan = false;
-        int skind = 0, nneg = 0;
-        double* ro = rows ? rows + (size_t)(j - 1) * rw : nullptr;
-        auto visit = [&](double r, int kind) {
-            if (!snan && (r != r || r < smin)) {
-                smin = r;
-                skind = kind;
-                snan = r != r;
-            }
-            p1 = p1 + (r != r ? r : (r < 0.0 ? -r : 0.0));
-            nneg += r < 0.0 ? 1 : 0;
-            if (ro) ro[kind] = r;
-        };
-        const double vf = d + (L / 2.0) * o, vl = d + L * o;
-        const double g[6] = {sl - d, d + sl, sl - vf, vf + sl, sl - vl, vl + sl};
-        for (int a = 0; a < 6; ++a) {
-            visit(g[a], a);
-            evaluate_nmin(fl, flnan, g[a]);
-        }
-        if (nobs > 0) {
-            const double tk = (double)j * p.dt;
-            const double vt = v * tgap;
-            const double safe = vt > osd ? vt : osd;             // the reference's max(osd, v * tgap)
-            for (int i = 0; i < nobs; ++i) {
-                const double sop = obs[2 * i] + obs[2 * i + 1] * tk;
-                const double r = (sop - s) - safe;
-                visit(r, 7 + i);
-                evaluate_nmin(fo, fonan, r);
-            }
-        }
-        if (ro)
-            for (int i = 7 + nobs; i < rw; ++i) ro[i] = qnan;
-        visit(v, 6);
-        evaluate_nmin(fv, fvnan, v);
-        part[j - 1] = p1;
-        cnt += (double)nneg;
-        if (!gnan && (astage == 0 || snan || smin < gmin)) {
-            gmin = smin;
-            gnan = snan;
+        get_state(R, X[j][0], st);
+        EvStage S = ev_stage_begin();
+        ev_stage(P, j, X[j], st, obs, nobs, rw, ct[j - 1], rows ? rows + (size_t)(j - 1) * rw : nullptr, S, run);
+        part[j - 1] = S.p1;
+        cnt += (double)S.nneg;
+        if (!gnan && (astage == 0 || S.snan || S.smin < gmin)) {
+            gmin = S.smin;
+            gnan = S.snan;
             astage = j;
-            akind = skind;
+            akind = S.skind;
         }
     }
-    double cost = 0.0, t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, l1 = 0.0;
-    for (int j = 0; j < N; ++j) {
-        for (int a = 0; a < 3; ++a) {
-            cost = cost + ct[j][a];
-            t[a] = t[a] + ct[j][a];
-        }
-        l1 = l1 + part[j];
-    }
-    for (int j = 0; j < N; ++j)
-        for (int a = 3; a < 5; ++a) {
-            cost = cost + ct[j][a];
-            t[a] = t[a] + ct[j][a];
-        }
-    if (summary) {
-        summary[MPC_EVQ_COST] = cost;
-        summary[MPC_EVQ_MIN_ROW] = gnan ? qnan : gmin;
-        summary[MPC_EVQ_ARGMIN_STAGE] = (double)astage;
-        summary[MPC_EVQ_ARGMIN_KIND] = (double)akind;
-        summary[MPC_EVQ_L1] = l1;
-        summary[MPC_EVQ_N_NEG] = cnt;
-        summary[MPC_EVQ_MIN_LANE] = flnan ? qnan : fl + 0.0;
-        summary[MPC_EVQ_MIN_OBS] = (fonan || nobs == 0) ? qnan : fo + 0.0;
-        summary[MPC_EVQ_MIN_V] = fvnan ? qnan : fv + 0.0;
-        summary[MPC_EVQ_BOX] = bxnan ? qnan : bx + 0.0;
-    }
-    if (terms)
-        for (int a = 0; a < 5; ++a) terms[a] = t[a];
+    const EvSums Z = ev_sums(N, &ct[0][0], part);
+    if (summary)
+        ev_summary(summary, Z, gnan ? (double)NAN : gmin, astage, akind, cnt, run.fl, run.fo, run.fv, run.bx,
+                   ev_flags(run, gnan), nobs);
+    if (terms) std::memcpy(terms, Z.t, sizeof(Z.t));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1105,11 +936,11 @@ struct LoopEgos {
     // The plant step x + dt f(x, ua, k_ref(s)) (:403-406) of ego b with the applied control ua, then perturb(x)
     // on the new state; the kept history rows and the plant-side quantities (u: the commanded control)
     template <typename Perturb>
-    void plant(const Ref& ref, double dt, int b, int step, const double* u, const double* ua, int status,
+    void plant(const DevTable& ref, double dt, int b, int step, const double* u, const double* ua, int status,
                Perturb perturb) {
         double* xb = x.data() + 5 * (size_t)b;
         double st[5];
-        ref.state(xb[0], st);
+        get_state(ref, xb[0], st);
         plant_step(xb, dt, ua[0], ua[1], st[3]);
         perturb(xb);
         if (slot[b] >= 0) {
@@ -1161,10 +992,10 @@ inline int script_step(const mpc_actor* sc, int A, double dt, double s, double v
 
 struct Backend {
     HostTable table;
-    std::unique_ptr<Ref> ref;
+    const DevTable ref;      // the table seen by tracker_model.h's lookups
     int threads = 0;
 
-    explicit Backend(HostTable&& t) : table(std::move(t)), ref(new Ref(table)) {
+    explicit Backend(HostTable&& t) : table(std::move(t)), ref(table.view()) {
         const char* e = std::getenv("MPC_CPU_THREADS");
         threads = e ? std::atoi(e) : 0;
         if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
@@ -1179,7 +1010,7 @@ struct Backend {
         auto run = [&]() {
             std::unique_ptr<Worker> w;
             try {
-                w.reset(new Worker(*ref, p));
+                w.reset(new Worker(ref, p));
             } catch (...) {
                 return;
             }
@@ -1233,7 +1064,7 @@ struct Backend {
             w.predict(x0 + 5 * (size_t)b, Ub, X);
             if (Xpred) std::memcpy(Xpred + (size_t)b * 5 * (N + 1), X, sizeof(double) * 5 * (N + 1));
             if (summary || terms || rows)
-                evaluate_one(*ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
+                evaluate_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
                              summary ? summary + (size_t)b * MPC_EV_NQ : nullptr,
                              terms ? terms + 5 * (size_t)b : nullptr,
                              rows ? rows + (size_t)b * N * rw : nullptr);
@@ -1243,15 +1074,15 @@ struct Backend {
     void lookup(int n, const double* s, double* st, double* ct) const {
         for (int i = 0; i < n; ++i) {
             double o[5], c[2];
-            ref->state(s[i], o);
-            ref->control(s[i], c);
+            get_state(ref, s[i], o);
+            get_control(ref, s[i], c);
             if (st) std::memcpy(st + 5 * (size_t)i, o, sizeof(o));
             if (ct) std::memcpy(ct + 2 * (size_t)i, c, sizeof(c));
         }
     }
 
     void pose(int n, const double* s, const double* d, double* out) const {
-        for (int i = 0; i < n; ++i) ref->pose(s[i], d[i], out + 3 * (size_t)i);
+        for (int i = 0; i < n; ++i) global_pose(ref, s[i], d[i], out + 3 * (size_t)i);
     }
 
     // The loop of every closed-loop member, step-synchronous like the device loop.  Per step: the list of the
@@ -1365,7 +1196,7 @@ struct Backend {
                      return n;
                  },
                  [&](int step, int b, const double* u, int status) {
-                     E.plant(*ref, p.dt, b, step, u, u, status, [](double*) {});
+                     E.plant(ref, p.dt, b, step, u, u, status, [](double*) {});
                  });
         E.finish(n_steps);
         return MPC_SUCCESS;
@@ -1513,7 +1344,7 @@ struct Backend {
                      for (int k = 0; k < 2; ++k)
                          ua[k] = apply_actuation(u[k], Z.act_sigma[k], at, MPC_NZ_CH_ACT + k, p.u_min[k], p.u_max[k],
                                                  clamped);
-                     E.plant(*ref, p.dt, b, step, u, ua, status, [&](double* xb) {
+                     E.plant(ref, p.dt, b, step, u, ua, status, [&](double* xb) {
                          for (int j = 0; j < 5; ++j)
                              xb[j] = noise_add(xb[j], Z.proc_sigma[j], at, MPC_NZ_CH_PROC + j, p.dt);
                      });
@@ -1559,7 +1390,7 @@ struct Backend {
                          const int src = reset ? -1 : warm_source(k, N, a.warm->tail);
                          if (walk) warm_ref_advance(w, k, p.dt, oa, nobs, p.brake_distance);
                          if (src < 0) {
-                             warm_ref_control(w, p.brake_accel, [&](double s, double* ur) { ref->control(s, ur); },
+                             warm_ref_control(w, p.brake_accel, [&](double s, double* ur) { get_control(ref, s, ur); },
                                               ub[2 * k], ub[2 * k + 1]);
                          } else {
                              ub[2 * k] = clamp_control(kp[2 * src], p.u_min[0], p.u_max[0]);

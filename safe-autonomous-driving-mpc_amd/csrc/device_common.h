@@ -1,47 +1,14 @@
 // device_common.h -- shared device definitions of the tracking-MPC solver (included by mpcqp.hip through the
-// kernel headers): the device table and kernel parameters, the reference-signal lookups, the per-instance LDS
-// layout, the row helpers, the fast reciprocals, the cross-lane (DPP / permlane) helpers and lane groups, the
-// nominal rollout and the fences of the stage pipelines.
+// kernel headers): the per-instance LDS layout, the row helpers, the fast reciprocals, the cross-lane (DPP /
+// permlane) helpers and lane groups, the nominal rollout and the fences of the stage pipelines.  The table, the
+// kernel parameters, the reference-signal lookups, the solver's constants and the row coefficients are
+// tracker_model.h's, shared with the host backend.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "tracker_model.h"
+
 #define WAVE 64
-#define NROW 9
-#define NBOX 4
-#define TAU 0.995
-
-// ------------------------------------------------------------------------------------------
-// device table + kernel parameters
-// ------------------------------------------------------------------------------------------
-struct DevTable {
-    const double* s;   // [T]  (strict-monotone fixed, trajectory_loader.py:26-30)
-    const double* d;
-    const double* o;
-    const double* k;
-    const double* v;
-    const double* u1;  // [Tu]
-    const double* u2;
-    const double* gx;  // [T]  global pose of the reference line (trajectory_loader.py:32-62)
-    const double* gy;
-    const double* gpsi;
-    int T, Tu;
-    double smax;
-    double last[5];    // X_ref[-1] verbatim (trajectory_loader.py:90-91)
-    const int* bidx;   // [nb + 1] bucket index of s: bidx[g] = lower_bound(s, s0 + g h)
-    int nb;
-    double s0, ibh;    // s[0], 1 / h
-};
-
-struct KParams {
-    int N, max_obs, linearization, sqp_iters, max_iter, polish;
-    double dt, u_min0, u_min1, u_max0, u_max1;
-    double w_d, w_o, w_v, w_u1, w_u2;
-    double osd, tgap, L, sl, brake_distance, brake_accel;
-    double tol, tol_mu, rho, sqp_tol;
-    double mu_check;   // interior-point checkpoint threshold (MU_CHECK; -1 = off, MPC_CHECKPOINT=0)
-    int dbg;           // diagnostics only (MPC_DBG, default 0): 1 = the crossover kernel defers without the
-                       // work-list atomic (timing probe; the interior-point launch then sees an empty list)
-};
 
 // ------------------------------------------------------------------------------------------
 // wave helpers
@@ -62,66 +29,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 __device__ __forceinline__ void wave_sync() { __syncthreads(); }
-
-// ------------------------------------------------------------------------------------------
-// reference signal: scipy interp1d 'linear' + extrapolate (scipy _interpolate.py:457-483)
-// ------------------------------------------------------------------------------------------
-// interval of v in the table's s column (n <= T: a prefix of it), i.e. scipy's searchsorted
-// (lower bound) clamped to [1, n - 1].  v's bucket g brackets the lower bound: it lies in
-// [bidx[g - 1], bidx[g + 2]] (one bucket of slack either side for the rounding of g), so a binary search
-// over that window returns the full binary search's answer exactly.  With 4 buckets per table interval
-// the window holds ~1 knot (~2 dependent L2 loads instead of log2 T; every instance looks up ~4 N times),
-// and a table with clustered knots costs log2 of the knots in the window, never a linear walk.
-// Host restatement: mpcqp_host::seg_host (host_table.h).
-__device__ __forceinline__ int seg_t(const DevTable& t, int n, double v) {
-    double gf = (v - t.s0) * t.ibh;
-    gf = gf > 0.0 ? gf : 0.0;                       // also maps NaN to bucket 0
-    const int g = gf < (double)(t.nb - 1) ? (int)gf : t.nb - 1;
-    int lo = t.bidx[g > 0 ? g - 1 : 0];
-    int hi = g + 2 <= t.nb ? t.bidx[g + 2] : t.T;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (t.s[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    lo = lo < n ? lo : n;
-    lo = lo < 1 ? 1 : lo;
-    lo = lo > n - 1 ? n - 1 : lo;
-    return lo;
-}
-__device__ __forceinline__ double lin(const double* x, const double* y, int i, double v) {
-    double slope = (y[i] - y[i - 1]) / (x[i] - x[i - 1]);
-    return slope * (v - x[i - 1]) + y[i - 1];
-}
-__device__ __forceinline__ double slope_at(const double* x, const double* y, int i) {
-    return (y[i] - y[i - 1]) / (x[i] - x[i - 1]);
-}
-// get_state (trajectory_loader.py:86-93): out[5]; slopes (d,o,k,v) for Gauss-Newton (0 past s_max)
-__device__ void get_state(const DevTable& t, double s, double* out, double* sl) {
-    if (s >= t.smax) {
-        for (int j = 0; j < 5; ++j) out[j] = t.last[j];
-        if (sl) sl[0] = sl[1] = sl[2] = sl[3] = 0.0;
-        return;
-    }
-    int i = seg_t(t, t.T, s);
-    out[0] = s;
-    out[1] = lin(t.s, t.d, i, s);
-    out[2] = lin(t.s, t.o, i, s);
-    out[3] = lin(t.s, t.k, i, s);
-    out[4] = lin(t.s, t.v, i, s);
-    if (sl) {
-        sl[0] = slope_at(t.s, t.d, i);
-        sl[1] = slope_at(t.s, t.o, i);
-        sl[2] = slope_at(t.s, t.k, i);
-        sl[3] = slope_at(t.s, t.v, i);
-    }
-}
-// get_control (trajectory_loader.py:95-102)
-__device__ void get_control(const DevTable& t, double s, double* out) {
-    if (s >= t.smax) { out[0] = 0.0; out[1] = 0.0; return; }
-    int i = seg_t(t, t.Tu, s);
-    out[0] = lin(t.s, t.u1, i, s);
-    out[1] = lin(t.s, t.u2, i, s);
-}
 
 // ------------------------------------------------------------------------------------------
 // per-instance LDS layout (doubles); stage arrays indexed by stage k = 0..N
@@ -221,21 +128,6 @@ __host__ __device__ __forceinline__ int p4(int a, int b) {
 // state index (0..4: s,d,o,k,v) of reduced index (0..3: s,d,o,v)
 __device__ __forceinline__ int st4(int a) { return a == 3 ? 4 : a; }
 
-// soft row coefficient vectors over (s,d,o,v) (the oracle's C[][] without the k entry)
-__device__ __forceinline__ void row_coef(int j, double h, double L, double T, double c[4]) {
-    c[0] = c[1] = c[2] = c[3] = 0.0;
-    switch (j) {
-        case 0: c[1] = 1.0; break;
-        case 1: c[1] = -1.0; break;
-        case 2: c[1] = 1.0; c[2] = h; break;
-        case 3: c[1] = -1.0; c[2] = -h; break;
-        case 4: c[1] = 1.0; c[2] = L; break;
-        case 5: c[1] = -1.0; c[2] = -L; break;
-        case 6: c[0] = -1.0; break;
-        case 7: c[0] = -1.0; c[3] = -T; break;
-        default: c[3] = 1.0; break;
-    }
-}
 __device__ __forceinline__ double bsign(int j) { return (j & 1) ? -1.0 : 1.0; }   // box rows +u1,-u1,+u2,-u2
 __device__ __forceinline__ double dot4(const double c[4], const double x[4]) {
     return fma(c[0], x[0], fma(c[1], x[1], fma(c[2], x[2], c[3] * x[3])));

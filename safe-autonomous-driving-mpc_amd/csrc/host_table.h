@@ -6,7 +6,7 @@
 //                              (medinammartin3/Safe-Autonomous-Driving-MPC trajectory_loader.py:13-24)
 //   build_host_table           the strict-monotone s fix (trajectory_loader.py:26-30), the interp1d columns
 //                              (:64-84, u over s[:min(T, Tu)]), the global reference line (:32-62) and the
-//                              bucket index of the s column used by the device lookups (seg_t)
+//                              bucket index of the s column used by the lookups (tracker_model.h, seg_t)
 #ifndef MPCQP_HOST_TABLE_H
 #define MPCQP_HOST_TABLE_H
 
@@ -15,6 +15,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "tracker_model.h"
 
 namespace mpcqp_host {
 
@@ -218,6 +220,26 @@ struct HostTable {
     double smax = 0.0, s0 = 0.0, ibh = 0.0;
     double last[5] = {0, 0, 0, 0, 0};
     size_t off_bidx = 0;      // offset of the bucket index, in doubles
+
+    // the table over `base`, a copy of buf anywhere (the device's) or buf itself: what the lookups of
+    // tracker_model.h read
+    DevTable view(const double* base) const {
+        DevTable t;
+        const size_t n = (size_t)T;
+        t.s = base; t.d = base + n; t.o = base + 2 * n; t.k = base + 3 * n; t.v = base + 4 * n;
+        t.u1 = base + 5 * n; t.u2 = t.u1 + tu;
+        t.gx = t.u2 + tu; t.gy = t.gx + n; t.gpsi = t.gy + n;
+        t.T = T;
+        t.Tu = tu;
+        t.smax = smax;
+        for (int j = 0; j < 5; ++j) t.last[j] = last[j];
+        t.bidx = reinterpret_cast<const int*>(base + off_bidx);
+        t.nb = nb;
+        t.s0 = s0;
+        t.ibh = ibh;
+        return t;
+    }
+    DevTable view() const { return view(buf.data()); }
 };
 
 inline bool build_host_table(const double* X, int T, const double* U, int Tu, HostTable& h) {
@@ -272,25 +294,9 @@ inline bool build_host_table(const double* X, int T, const double* U, int Tu, Ho
     return true;
 }
 
-// host restatement of the device interval search (seg_t in device_common.h): scipy's searchsorted lower bound
-// of v in s[0..T), found by binary search inside the buckets around v's, clamped to [1, n - 1]
-inline int seg_host(const HostTable& h, int n, double v) {
-    const double* s = h.buf.data();
-    const int* bidx = reinterpret_cast<const int*>(h.buf.data() + h.off_bidx);
-    double gf = (v - h.s0) * h.ibh;
-    gf = gf > 0.0 ? gf : 0.0;
-    const int g = gf < (double)(h.nb - 1) ? (int)gf : h.nb - 1;
-    int lo = bidx[g > 0 ? g - 1 : 0];
-    int hi = g + 2 <= h.nb ? bidx[g + 2] : h.T;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    lo = lo < n ? lo : n;
-    lo = lo < 1 ? 1 : lo;
-    lo = lo > n - 1 ? n - 1 : lo;
-    return lo;
-}
+// the interval search on a HostTable: tracker_model.h's seg_t over its view (no arithmetic of its own; kept under
+// this name for drivers written against it)
+inline int seg_host(const HostTable& h, int n, double v) { return seg_t(h.view(), n, v); }
 
 }  // namespace mpcqp_host
 

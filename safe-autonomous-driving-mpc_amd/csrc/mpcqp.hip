@@ -17,7 +17,8 @@
 // the reference's numpy arithmetic; the solver uses explicit fma() where it wants fusion.
 //
 // This file is the library's one translation unit.  The device code lives in the headers it includes:
-//   device_common.h        table, parameters, lookups, LDS layout, cross-lane helpers, rollout, fences
+//   tracker_model.h        table, parameters, lookups, constants, row model, evaluator steps (shared with the host)
+//   device_common.h        LDS layout, cross-lane helpers, rollout, fences
 //   riccati_lanes.h        the lane-distributed Riccati recursions (inline-asm DPP chains)
 //   solve_kernel.h         mpc_solve_kernel and mpc_lookup_kernel
 //   closed_loop_kernels.h  closed-loop FSM / plant / compaction kernels, pose kernel
@@ -188,28 +189,9 @@ static int check_params(const mpc_params* p) {
     return MPC_SUCCESS;
 }
 
+// the kernels' parameters: the model's (tracker_model.h) and the environment's switches
 static KParams kparams(const mpc_params* p) {
-    KParams k;
-    k.N = p->N;
-    k.max_obs = p->max_obs;
-    k.linearization = p->linearization;
-    k.sqp_iters = p->sqp_iters;
-    k.max_iter = p->max_iter;
-    k.dt = p->dt;
-    k.u_min0 = p->u_min[0]; k.u_min1 = p->u_min[1];
-    k.u_max0 = p->u_max[0]; k.u_max1 = p->u_max[1];
-    k.w_d = p->w_d; k.w_o = p->w_o; k.w_v = p->w_v; k.w_u1 = p->w_u1; k.w_u2 = p->w_u2;
-    k.osd = p->obstacle_safety_distance;
-    k.tgap = p->max_time_2_obs;
-    k.L = p->wheelbase;
-    k.sl = p->lane_width / 2.0 - p->vehicle_radius - p->safe_lane_margin;   // trajectory_tracking.py:169
-    k.brake_distance = p->brake_distance;
-    k.brake_accel = p->brake_accel;
-    k.tol = p->tol;
-    k.tol_mu = p->tol_mu;
-    k.rho = p->elastic_rho;
-    k.polish = p->polish;
-    k.sqp_tol = p->sqp_tol;
+    KParams k = model_params(*p);
     const char* dbg = std::getenv("MPC_DBG");
     k.dbg = dbg ? std::atoi(dbg) : 0;
     k.mu_check = mpcqp_cpu::checkpoint_on() ? MU_CHECK : -1.0;
@@ -248,7 +230,6 @@ extern "C" int mpc_create(const double* X, int T, const double* U, int Tu, const
     mpcqp_host::HostTable ht;      // monotone s fix, interp columns, global line, bucket index (host_table.h)
     if (!mpcqp_host::build_host_table(X, T, U, Tu, ht)) return fail(MPC_E_ARG, "bad trajectory table");
     const std::vector<double>& h = ht.buf;
-    const int tu = ht.tu;
     mpc_ctx* c = (mpc_ctx*)std::calloc(1, sizeof(mpc_ctx));
     if (!c) return fail(MPC_E_ALLOC, "calloc");
     c->device = device;
@@ -272,24 +253,7 @@ extern "C" int mpc_create(const double* X, int T, const double* U, int Tu, const
         std::free(c);
         return fail(MPC_E_DEVICE, "hipMemcpy table");
     }
-    c->tab.s = c->table_buf;
-    c->tab.d = c->table_buf + T;
-    c->tab.o = c->table_buf + 2 * T;
-    c->tab.k = c->table_buf + 3 * T;
-    c->tab.v = c->table_buf + 4 * T;
-    c->tab.u1 = c->table_buf + 5 * T;
-    c->tab.u2 = c->table_buf + 5 * T + tu;
-    c->tab.gx = c->table_buf + 5 * T + 2 * tu;
-    c->tab.gy = c->tab.gx + T;
-    c->tab.gpsi = c->tab.gy + T;
-    c->tab.T = T;
-    c->tab.Tu = tu;
-    c->tab.smax = ht.smax;
-    c->tab.bidx = reinterpret_cast<const int*>(c->table_buf + ht.off_bidx);
-    c->tab.nb = ht.nb;
-    c->tab.s0 = ht.s0;
-    c->tab.ibh = ht.ibh;
-    for (int j = 0; j < 5; ++j) c->tab.last[j] = ht.last[j];
+    c->tab = ht.view(c->table_buf);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         hipFree(c->table_buf);
         std::free(c);

@@ -1,5 +1,5 @@
 // solve_kernel.h -- the solver kernel mpc_solve_kernel<GL, OBS, MODE, NT> (setup, crossover, interior point,
-// polish, outputs), its algorithm constants and launch modes, and the table lookup kernel.
+// polish, outputs), its launch modes, and the table lookup kernel.  Its constants are tracker_model.h's.
 #pragma once
 #include "../../include/mpcqp.h"
 #include "riccati_lanes.h"
@@ -25,22 +25,6 @@ __device__ unsigned long long g_prof[16];
 #define PROF(i)
 #define PROF_END
 #endif
-
-#define POLISH_DELTA 1e-11
-#define POLISH_REFINE 2
-#define POLISH_ROUNDS 6
-#define XO_ROUNDS 1            // rounds of the crossover attempt before the interior point
-// SQP stopping rules besides convergence (oracle orc_solve): a 2-cycle (the QP returns the point of two QPs
-// back, |U_k - U_k-2| <= SQP_CYCLE_REL |U_k - U_k-1|), and SQP_INF_STREAK elastic QPs in a row
-#define SQP_CYCLE_REL 1e-6
-#define SQP_INF_STREAK 5
-#define START_SHIFT 3.0     // interior-point start: slack and elastic slack beyond the row value (oracle pdip)
-// interior-point checkpoint (oracle pdip): once mu <= MU_CHECK and every row's slack and
-// multiplier are CHECK_SEP apart, CHECK_ROUNDS polish rounds try the iterate's classification; a certified point
-// is the QP's exact optimum, otherwise the interior point continues from the unchanged iterate (once per QP)
-#define MU_CHECK 1e-4
-#define CHECK_SEP 100.0
-#define CHECK_ROUNDS 2
 
 // ------------------------------------------------------------------------------------------
 // the solver kernel.  A 64-lane wavefront carries G = 64 / GL MPC instances, one per aligned group
@@ -142,7 +126,7 @@ mpc_solve_kernel(DevTable tab, KParams Pr, int B, const double* __restrict__ x0g
     double cf[NR][4];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        rowon[j] = (rid<OBS>(j) != 6 && rid<OBS>(j) != 7) || has_obs;
+        rowon[j] = row_exists(rid<OBS>(j), has_obs);
         ron[j] = live && rowon[j];
         row_coef(rid<OBS>(j), hL, Pr.L, Pr.tgap, cf[j]);
     }
@@ -166,7 +150,9 @@ mpc_solve_kernel(DevTable tab, KParams Pr, int B, const double* __restrict__ x0g
             S.ub[2 * gl + 1] = ubarg[(size_t)b * 2 * N + 2 * gl + 1];
         } else {
             // warm start, trajectory_tracking.py:224-246: s_curr advanced by repeated addition,
-            // sticky brake flag over steps 0..gl
+            // sticky brake flag over steps 0..gl.  The kernel's own text of loop_steps.h's warm_ref_begin /
+            // warm_ref_advance / warm_ref_control (which the host backend and the carry kernel walk): through
+            // them every instantiation's register allocation moved
             double s_curr = x0[0], v_curr = x0[4];
             bool brake = false;
             for (int j = 0; j <= gl; ++j) {
@@ -183,7 +169,7 @@ mpc_solve_kernel(DevTable tab, KParams Pr, int B, const double* __restrict__ x0g
     wave_sync();
 
     int nsoft = 0;
-    for (int jj = 0; jj < NROW; ++jj) nsoft += ((jj != 6 && jj != 7) || has_obs) ? 1 : 0;
+    for (int jj = 0; jj < NROW; ++jj) nsoft += row_exists(jj, has_obs) ? 1 : 0;
     const double Mtot = (double)(2 * nsoft * N + NBOX * N);
     const double R0 = 2.0 * Pr.w_u1, R1 = 2.0 * Pr.w_u2;
 
@@ -220,6 +206,10 @@ mpc_solve_kernel(DevTable tab, KParams Pr, int B, const double* __restrict__ x0g
             slk[0] = l2.x; slk[1] = l2.y; slk[2] = l3.x; slk[3] = l3.y;
         }
         // ---- K2: stage data of QP(ubar) ----------------------------------------------------
+        // The A5 / AC coefficients, the row values v[] and the box values bb[] below are the kernel's own text of
+        // tracker_model.h's stage_A, nearest_obstacle + row_values and box_values, which the host backend calls:
+        // this kernel sits at 512 registers, and through the shared functions (each of the four parts alone)
+        // no instantiation came out instruction-identical.  Change them together
         const bool gn = Pr.linearization != 0;
         if (gl < N) {
             const double* x = S.Xr + 5 * gl;

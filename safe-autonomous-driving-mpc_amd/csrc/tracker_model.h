@@ -1,0 +1,371 @@
+// tracker_model.h -- the tracker's model, stated once for its kernels (solve_kernel.h, evaluate_kernel.h, the
+// closed-loop kernels) and for its host backend (cpu_backend.h): the view of the reference-signal table and the
+// lookups on it, the solver's constants, the model derived from mpc_params (lane bound, which rows exist, the row
+// coefficients, the row and box values of a stage, the A_k coefficients) and the evaluator's steps.  Both sides keep
+// their own storage, loops, lane mapping and reductions and hand single values in.  One exception: mpc_solve_kernel
+// keeps its own text of stage_A, nearest_obstacle, row_values and box_values (and of loop_steps.h's warm start) in
+// its K1 / K2 blocks, because its register allocation moves with any other form of them; the comments there say so.
+// What may be written here: single rounded FP64 operations, integer arithmetic, fabs and comparisons (sin / cos for
+// the pose).  The build has -ffp-contract=off, so the device pass, the host pass and a plain C++ compiler form the
+// same operation sequence.  oracle/mpc_oracle.c shares nothing with this file: it is the independent reference.
+#pragma once
+#include "../../include/mpcqp.h"
+#include <math.h>
+
+#ifdef __HIPCC__
+#define TRACKER_MODEL __host__ __device__
+#define TRACKER_MODEL_INLINE __host__ __device__ __forceinline__
+#define TRACKER_UNROLL _Pragma("unroll")
+#else
+#define TRACKER_MODEL inline
+#define TRACKER_MODEL_INLINE inline
+#define TRACKER_UNROLL
+#endif
+
+// ------------------------------------------------------------------------------------------
+// the solver's constants
+// ------------------------------------------------------------------------------------------
+constexpr int NROW = 9;               // soft rows per stage: lane +-d, +-(d + L/2 o), +-(d + L o), 2 obstacle, v >= 0
+constexpr int NBOX = 4;               // box rows per control: +u1, -u1, +u2, -u2
+constexpr double TAU = 0.995;         // fraction of the step to the boundary
+constexpr double POLISH_DELTA = 1e-11;
+constexpr int POLISH_REFINE = 2;
+constexpr int POLISH_ROUNDS = 6;
+constexpr int XO_ROUNDS = 1;          // rounds of the crossover attempt before the interior point
+// SQP stopping rules besides convergence (oracle orc_solve): a 2-cycle (the QP returns the point of two QPs
+// back, |U_k - U_k-2| <= SQP_CYCLE_REL |U_k - U_k-1|), and SQP_INF_STREAK elastic QPs in a row
+constexpr double SQP_CYCLE_REL = 1e-6;
+constexpr int SQP_INF_STREAK = 5;
+constexpr double START_SHIFT = 3.0;   // interior-point start: slack and elastic slack beyond the row value (oracle pdip)
+// interior-point checkpoint (oracle pdip): once mu <= MU_CHECK and every row's slack and
+// multiplier are CHECK_SEP apart, CHECK_ROUNDS polish rounds try the iterate's classification; a certified point
+// is the QP's exact optimum, otherwise the interior point continues from the unchanged iterate (once per QP)
+constexpr double MU_CHECK = 1e-4;
+constexpr double CHECK_SEP = 100.0;
+constexpr int CHECK_ROUNDS = 2;
+
+// ------------------------------------------------------------------------------------------
+// the reference-signal table: one buffer of doubles (host_table.h builds it), seen through column pointers.  The
+// device context points them into its device copy, HostTable::view() into the host buffer
+// ------------------------------------------------------------------------------------------
+struct DevTable {
+    const double* s;   // [T]  (strict-monotone fixed, trajectory_loader.py:26-30)
+    const double* d;
+    const double* o;
+    const double* k;
+    const double* v;
+    const double* u1;  // [Tu]
+    const double* u2;
+    const double* gx;  // [T]  global pose of the reference line (trajectory_loader.py:32-62)
+    const double* gy;
+    const double* gpsi;
+    int T, Tu;
+    double smax;
+    double last[5];    // X_ref[-1] verbatim (trajectory_loader.py:90-91)
+    const int* bidx;   // [nb + 1] bucket index of s: bidx[g] = lower_bound(s, s0 + g h)
+    int nb;
+    double s0, ibh;    // s[0], 1 / h
+};
+
+// scipy interp1d 'linear' + extrapolate (scipy _interpolate.py:457-483).
+// Interval of v in the table's s column (n <= T: a prefix of it), i.e. scipy's searchsorted
+// (lower bound) clamped to [1, n - 1].  v's bucket g brackets the lower bound: it lies in
+// [bidx[g - 1], bidx[g + 2]] (one bucket of slack either side for the rounding of g), so a binary search
+// over that window returns the full binary search's answer exactly.  With 4 buckets per table interval
+// the window holds ~1 knot (~2 dependent L2 loads instead of log2 T; every instance looks up ~4 N times),
+// and a table with clustered knots costs log2 of the knots in the window, never a linear walk.
+TRACKER_MODEL_INLINE int seg_t(const DevTable& t, int n, double v) {
+    double gf = (v - t.s0) * t.ibh;
+    gf = gf > 0.0 ? gf : 0.0;                       // also maps NaN to bucket 0
+    const int g = gf < (double)(t.nb - 1) ? (int)gf : t.nb - 1;
+    int lo = t.bidx[g > 0 ? g - 1 : 0];
+    int hi = g + 2 <= t.nb ? t.bidx[g + 2] : t.T;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t.s[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    lo = lo < n ? lo : n;
+    lo = lo < 1 ? 1 : lo;
+    lo = lo > n - 1 ? n - 1 : lo;
+    return lo;
+}
+TRACKER_MODEL_INLINE double lin(const double* x, const double* y, int i, double v) {
+    double slope = (y[i] - y[i - 1]) / (x[i] - x[i - 1]);
+    return slope * (v - x[i - 1]) + y[i - 1];
+}
+TRACKER_MODEL_INLINE double slope_at(const double* x, const double* y, int i) {
+    return (y[i] - y[i - 1]) / (x[i] - x[i - 1]);
+}
+// get_state (trajectory_loader.py:86-93): out[5]; slopes (d,o,k,v) for Gauss-Newton (0 past s_max)
+TRACKER_MODEL static void get_state(const DevTable& t, double s, double* out, double* sl = nullptr) {
+    if (s >= t.smax) {
+        for (int j = 0; j < 5; ++j) out[j] = t.last[j];
+        if (sl) sl[0] = sl[1] = sl[2] = sl[3] = 0.0;
+        return;
+    }
+    int i = seg_t(t, t.T, s);
+    out[0] = s;
+    out[1] = lin(t.s, t.d, i, s);
+    out[2] = lin(t.s, t.o, i, s);
+    out[3] = lin(t.s, t.k, i, s);
+    out[4] = lin(t.s, t.v, i, s);
+    if (sl) {
+        sl[0] = slope_at(t.s, t.d, i);
+        sl[1] = slope_at(t.s, t.o, i);
+        sl[2] = slope_at(t.s, t.k, i);
+        sl[3] = slope_at(t.s, t.v, i);
+    }
+}
+// get_control (trajectory_loader.py:95-102)
+TRACKER_MODEL static void get_control(const DevTable& t, double s, double* out) {
+    if (s >= t.smax) { out[0] = 0.0; out[1] = 0.0; return; }
+    int i = seg_t(t, t.Tu, s);
+    out[0] = lin(t.s, t.u1, i, s);
+    out[1] = lin(t.s, t.u2, i, s);
+}
+// get_global_pose (trajectory_loader.py:104-116): out[3] = (x, y, psi) of the point d beside the line at s
+TRACKER_MODEL_INLINE void global_pose(const DevTable& t, double s, double d, double* out) {
+    if (s > t.smax) s = t.smax;
+    const int j = seg_t(t, t.T, s);
+    const double xr = lin(t.s, t.gx, j, s), yr = lin(t.s, t.gy, j, s), psi = lin(t.s, t.gpsi, j, s);
+    out[0] = xr - d * sin(psi);
+    out[1] = yr + d * cos(psi);
+    out[2] = psi;
+}
+
+// ------------------------------------------------------------------------------------------
+// the model derived from mpc_params
+// ------------------------------------------------------------------------------------------
+// what the kernels are handed; mu_check and dbg are the device context's (the environment's)
+struct KParams {
+    int N, max_obs, linearization, sqp_iters, max_iter, polish;
+    double dt, u_min0, u_min1, u_max0, u_max1;
+    double w_d, w_o, w_v, w_u1, w_u2;
+    double osd, tgap, L, sl, brake_distance, brake_accel;
+    double tol, tol_mu, rho, sqp_tol;
+    double mu_check;   // interior-point checkpoint threshold (MU_CHECK; -1 = off, MPC_CHECKPOINT=0)
+    int dbg;           // diagnostics only (MPC_DBG, default 0): 1 = the crossover kernel defers without the
+                       // work-list atomic (timing probe; the interior-point launch then sees an empty list)
+};
+// the lane rows' bound (trajectory_tracking.py:169)
+inline double lane_bound(const mpc_params& p) { return p.lane_width / 2.0 - p.vehicle_radius - p.safe_lane_margin; }
+inline KParams model_params(const mpc_params& p) {
+    KParams k;
+    k.N = p.N;
+    k.max_obs = p.max_obs;
+    k.linearization = p.linearization;
+    k.sqp_iters = p.sqp_iters;
+    k.max_iter = p.max_iter;
+    k.polish = p.polish;
+    k.dt = p.dt;
+    k.u_min0 = p.u_min[0]; k.u_min1 = p.u_min[1];
+    k.u_max0 = p.u_max[0]; k.u_max1 = p.u_max[1];
+    k.w_d = p.w_d; k.w_o = p.w_o; k.w_v = p.w_v; k.w_u1 = p.w_u1; k.w_u2 = p.w_u2;
+    k.osd = p.obstacle_safety_distance;
+    k.tgap = p.max_time_2_obs;
+    k.L = p.wheelbase;
+    k.sl = lane_bound(p);
+    k.brake_distance = p.brake_distance;
+    k.brake_accel = p.brake_accel;
+    k.tol = p.tol;
+    k.tol_mu = p.tol_mu;
+    k.rho = p.elastic_rho;
+    k.sqp_tol = p.sqp_tol;
+    k.mu_check = MU_CHECK;
+    k.dbg = 0;
+    return k;
+}
+
+// soft row j exists for an instance: the obstacle rows (6, 7) need obstacles
+TRACKER_MODEL_INLINE constexpr bool row_exists(int j, bool has_obs) { return (j != 6 && j != 7) || has_obs; }
+
+// soft row coefficient vectors over (s,d,o,v) (the oracle's C[][] without the k entry):
+// h = L / 2, T the time gap
+TRACKER_MODEL_INLINE void row_coef(int j, double h, double L, double T, double c[4]) {
+    c[0] = c[1] = c[2] = c[3] = 0.0;
+    switch (j) {
+        case 0: c[1] = 1.0; break;
+        case 1: c[1] = -1.0; break;
+        case 2: c[1] = 1.0; c[2] = h; break;
+        case 3: c[1] = -1.0; c[2] = -h; break;
+        case 4: c[1] = 1.0; c[2] = L; break;
+        case 5: c[1] = -1.0; c[2] = -L; break;
+        case 6: c[0] = -1.0; break;
+        case 7: c[0] = -1.0; c[3] = -T; break;
+        default: c[3] = 1.0; break;
+    }
+}
+
+// the position of the nearest obstacle predicted at stage k: the obstacle rows of :194-204 for every obstacle
+// collapse to it (infinity without obstacles)
+TRACKER_MODEL_INLINE double nearest_obstacle(const double* obs, int nobs, int k, double dt) {
+    double shat = INFINITY;
+    for (int i = 0; i < nobs; ++i) {
+        const double sp = obs[2 * i] + obs[2 * i + 1] * (k * dt);
+        shat = sp < shat ? sp : shat;
+    }
+    return shat;
+}
+// the row values v[NROW] (by row id) of a stage at its nominal state x, shat its nearest_obstacle
+TRACKER_MODEL_INLINE void row_values(const KParams& P, const double* x, double shat, bool has_obs, double* v) {
+    const double sl = P.sl;
+    const double pv0 = x[1], pv1 = x[1] + (P.L / 2.0) * x[2], pv2 = x[1] + P.L * x[2];
+    v[0] = -sl - pv0;
+    v[1] = -(sl - pv0);
+    v[2] = -sl - pv1;
+    v[3] = -(sl - pv1);
+    v[4] = -sl - pv2;
+    v[5] = -(sl - pv2);
+    v[6] = has_obs ? -(shat - P.osd - x[0]) : 0.0;
+    v[7] = has_obs ? -(shat - x[0] - P.tgap * x[4]) : 0.0;
+    v[8] = -x[4];
+}
+// the box values bb[NBOX] of a control at its linearisation point (ub1, ub2)
+TRACKER_MODEL_INLINE void box_values(const KParams& P, double ub1, double ub2, double* bb) {
+    bb[0] = P.u_min0 - ub1;
+    bb[1] = -(P.u_max0 - ub1);
+    bb[2] = P.u_min1 - ub2;
+    bb[3] = -(P.u_max1 - ub2);
+}
+// the coefficients (a12, a14, a20, a23, a24) of A_k = I + J'_k (J'(0,4) = dt) at the nominal state x: kref the
+// reference curvature at x[0], dk its slope (0 without the Gauss-Newton term)
+TRACKER_MODEL_INLINE void stage_A(const double* x, double dt, double kref, double dk, double* a) {
+    a[0] = dt * x[4];
+    a[1] = dt * x[2];
+    a[2] = dt * (-x[4] * dk);
+    a[3] = dt * x[4];
+    a[4] = dt * (x[3] - kref);
+}
+
+// ------------------------------------------------------------------------------------------
+// the evaluator (mpc_evaluate_batch, include/mpcqp.h): the steps of one control and of one stage, and the sums
+// ------------------------------------------------------------------------------------------
+enum { EV_NAN_ROW = 1, EV_NAN_LANE = 2, EV_NAN_OBS = 4, EV_NAN_V = 8, EV_NAN_BOX = 16 };
+
+// The running minima of the three row families, the running box excess, and which of them met a NaN: a lane's on
+// the device (reduced over the group afterwards), the whole instance's on the host
+struct EvRun {
+    double fl, fo, fv, bx;
+    bool flnan, fonan, fvnan, bxnan;
+};
+TRACKER_MODEL_INLINE EvRun ev_run_begin() { return EvRun{INFINITY, INFINITY, INFINITY, 0.0, false, false, false, false}; }
+// the EV_NAN_* bits of a run and of a stage's (or any stage's) NaN row
+TRACKER_MODEL_INLINE int ev_flags(const EvRun& R, bool snan) {
+    return (snan ? EV_NAN_ROW : 0) | (R.flnan ? EV_NAN_LANE : 0) | (R.fonan ? EV_NAN_OBS : 0) |
+           (R.fvnan ? EV_NAN_V : 0) | (R.bxnan ? EV_NAN_BOX : 0);
+}
+
+// NaN-propagating running minimum (numpy's min): once a NaN was seen it stays
+TRACKER_MODEL_INLINE void ev_nmin(double& m, bool& nan, double r) {
+    if (!nan) {
+        if (r != r) nan = true;
+        else if (r < m) m = r;
+    }
+}
+
+// control (u1, u2): its two cost terms to ct[3], ct[4], and the excess over the bounds handed to SLSQP (:249-252)
+TRACKER_MODEL_INLINE void ev_control(const KParams& P, double u1, double u2, double* ct, EvRun& R) {
+    ct[3] = P.w_u1 * (u1 * u1);
+    ct[4] = P.w_u2 * (u2 * u2);
+    const double e[4] = {P.u_min0 - u1, u1 - P.u_max0, P.u_min1 - u2, u2 - P.u_max1};
+    TRACKER_UNROLL
+    for (int a = 0; a < 4; ++a) {
+        if (e[a] != e[a]) R.bxnan = true;
+        else if (e[a] > R.bx) R.bx = e[a];
+    }
+}
+
+// what one stage leaves: its minimal row (the first NaN if there is one, else the first minimum: np.argmin) and
+// that row's kind, its L1 violation and its count of negative rows
+struct EvStage {
+    double smin, p1;
+    bool snan;
+    int skind, nneg;
+};
+TRACKER_MODEL_INLINE EvStage ev_stage_begin() { return EvStage{INFINITY, 0.0, false, 0, 0}; }
+// Stage j at the rolled-out state x with st the reference state at x[0]: its three cost terms to ct[0..2], and
+// its rows visited in the reference's order (the six lane rows, the obstacles, v), each stored to ro (row width
+// rw, NaN past the obstacles; ro may be null); S starts from ev_stage_begin()
+TRACKER_MODEL_INLINE void ev_stage(const KParams& P, int j, const double* x, const double* st, const double* obs,
+                                   int nobs, int rw, double* ct, double* ro, EvStage& S, EvRun& R) {
+    const double s = x[0], d = x[1], o = x[2], v = x[4];
+    const double ed = d - st[1], eo = o - st[2], ev = v - st[4];
+    ct[0] = P.w_d * (ed * ed);
+    ct[1] = P.w_o * (eo * eo);
+    ct[2] = P.w_v * (ev * ev);
+    auto visit = [&](double r, int kind) {
+        if (!S.snan && (r != r || r < S.smin)) {
+            S.smin = r;
+            S.skind = kind;
+            S.snan = r != r;
+        }
+        S.p1 = S.p1 + (r != r ? r : (r < 0.0 ? -r : 0.0));
+        S.nneg += r < 0.0 ? 1 : 0;
+        if (ro) ro[kind] = r;
+    };
+    const double sl = P.sl;
+    const double vf = d + (P.L / 2.0) * o, vl = d + P.L * o;
+    const double g[6] = {sl - d, d + sl, sl - vf, vf + sl, sl - vl, vl + sl};
+    TRACKER_UNROLL
+    for (int a = 0; a < 6; ++a) {
+        visit(g[a], a);
+        ev_nmin(R.fl, R.flnan, g[a]);
+    }
+    if (nobs > 0) {
+        const double tk = (double)j * P.dt;
+        const double vt = v * P.tgap;
+        const double safe = vt > P.osd ? vt : P.osd;       // the reference's max(osd, v * tgap)
+        for (int i = 0; i < nobs; ++i) {
+            const double sop = obs[2 * i] + obs[2 * i + 1] * tk;
+            const double r = (sop - s) - safe;
+            visit(r, 7 + i);
+            ev_nmin(R.fo, R.fonan, r);
+        }
+    }
+    if (ro)
+        for (int i = 7 + nobs; i < rw; ++i) ro[i] = NAN;
+    visit(v, 6);
+    ev_nmin(R.fv, R.fvnan, v);
+}
+
+// The sums whose bits must not depend on who adds them, from ct [N][5] (the cost terms d, o, v of stage j + 1 and
+// u1, u2 of control j) and part [N] (the stages' L1 violations): the reference's running cost over stages 1..N
+// (d, o, v), then controls 0..N-1 (u1, u2), one sum; its five shares t; the L1 violation
+struct EvSums {
+    double cost, t[5], l1;
+};
+TRACKER_MODEL_INLINE EvSums ev_sums(int N, const double* ct, const double* part) {
+    EvSums Z = {0.0, {0.0, 0.0, 0.0, 0.0, 0.0}, 0.0};
+    for (int j = 0; j < N; ++j) {
+        TRACKER_UNROLL
+        for (int a = 0; a < 3; ++a) {
+            Z.cost = Z.cost + ct[5 * j + a];
+            Z.t[a] = Z.t[a] + ct[5 * j + a];
+        }
+        Z.l1 = Z.l1 + part[j];
+    }
+    for (int j = 0; j < N; ++j) {
+        TRACKER_UNROLL
+        for (int a = 3; a < 5; ++a) {
+            Z.cost = Z.cost + ct[5 * j + a];
+            Z.t[a] = Z.t[a] + ct[5 * j + a];
+        }
+    }
+    return Z;
+}
+// The summary row o [MPC_EV_NQ]: min_row is NaN if a row was, cnt the negative rows, (fl, fo, fv, bx) the instance's
+// minima and box excess, flags its EV_NAN_* bits
+TRACKER_MODEL_INLINE void ev_summary(double* o, const EvSums& Z, double min_row, int astage, int akind, double cnt,
+                                     double fl, double fo, double fv, double bx, int flags, int nobs) {
+    o[MPC_EVQ_COST] = Z.cost;
+    o[MPC_EVQ_MIN_ROW] = min_row;
+    o[MPC_EVQ_ARGMIN_STAGE] = (double)astage;
+    o[MPC_EVQ_ARGMIN_KIND] = (double)akind;
+    o[MPC_EVQ_L1] = Z.l1;
+    o[MPC_EVQ_N_NEG] = cnt;
+    // + 0.0: a minimum of -0.0 and 0.0 comes out as 0.0 whichever the reduction met first
+    o[MPC_EVQ_MIN_LANE] = (flags & EV_NAN_LANE) ? NAN : fl + 0.0;
+    o[MPC_EVQ_MIN_OBS] = ((flags & EV_NAN_OBS) || nobs == 0) ? NAN : fo + 0.0;
+    o[MPC_EVQ_MIN_V] = (flags & EV_NAN_V) ? NAN : fv + 0.0;
+    o[MPC_EVQ_BOX] = (flags & EV_NAN_BOX) ? NAN : bx + 0.0;
+}

@@ -3,7 +3,7 @@
 // malformed / duplicate-key / deeply nested corpus.
 //
 // For every file: parse it; on success build the device table on the host and check the bucketed
-// interval search (seg_host, the restatement of the device's seg_t) against std::lower_bound at every
+// interval search (seg_t of csrc/tracker_model.h, the one the kernels run) against std::lower_bound at every
 // knot, one ulp either side, midpoints and random points.  Prints one line per file:
 //   OK <T> <Tu> <sum of X> <sum of U> <search mismatches>      or      ERR <message>
 #include <algorithm>
@@ -30,13 +30,14 @@ static int check_search(const mpcqp_host::HostTable& h) {
     probe.push_back(NAN);
     probe.push_back(-1e300);
     probe.push_back(1e300);
+    const DevTable t = h.view();
     int bad = 0;
     for (int n : {h.T, h.tu}) {
         for (double v : probe) {
             int lb = (int)(std::lower_bound(s, s + h.T, v) - s);   // numpy searchsorted 'left'
             if (v != v) lb = 0;                                     // NaN: both treat it as before s[0]
             lb = std::min(std::max(std::min(lb, n), 1), n - 1);
-            if (lb != mpcqp_host::seg_host(h, n, v)) ++bad;
+            if (lb != seg_t(t, n, v)) ++bad;
         }
     }
     return bad;

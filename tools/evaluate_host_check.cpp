@@ -103,7 +103,7 @@ int main(int argc, char** argv) {
                             ++bad;
                     }
                     // the rollout is Worker::predict's; the summary agrees with the rows
-                    mpcqp_cpu::Worker w(*be.ref, p);
+                    mpcqp_cpu::Worker w(be.ref, p);
                     for (int b = 0; b < B; ++b) {
                         double Xp[mpcqp_cpu::kMaxN + 1][5];
                         w.predict(&x0[5 * (size_t)b], &u[(size_t)b * 2 * N], Xp);

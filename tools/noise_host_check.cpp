@@ -108,7 +108,7 @@ int main(int argc, char** argv) {
     std::vector<double> x0(5 * (size_t)B, 0.0);
     for (int b = 0; b < B; ++b) {
         double st[5];
-        be.ref->state(start[b], st);
+        get_state(be.ref, start[b], st);
         x0[5 * b] = start[b]; x0[5 * b + 1] = 0.01 * (b % 3); x0[5 * b + 3] = st[3]; x0[5 * b + 4] = 6.0 + 0.5 * (b % 4);
     }
     const int A = 2;
