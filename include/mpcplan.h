@@ -129,7 +129,8 @@ int plan_chunks_per_cu(plan_ctx* c, int Nmax, int* out);
  *   max_chunks          chunks per plan at most (the reference has no cap); also the slot count below
  *   avg[nav]            avg[i] = mean(vmax[i:]) over the route's speed-limit array (:507, np.mean, which
  *                       the caller computes so that N matches the host loop bit for bit)
- *   Nmax                bounds every chunk's N = ceil(size / avg[int(s / 5)] * 2 / 0.3) (:507-515)
+ *   Nmax                bounds every chunk's N = ceil(size / avg[int(s / 5)] * 2 / dt) (:507-515; dt is the
+ *                       params' dt: the reference's loop divides by the dt it gives the optimizer, :514-517)
  * Outputs per plan b and chunk slot n < max_chunks (slot = b * max_chunks + n): X[slot][Nmax+1][5],
  * U[slot][Nmax][2], S[slot][Nmax] (the chunk's whole plan, rows past its N zero), N[slot], is_final[slot],
  * status[slot], iters[slot], sqp[slot]; nchunks[b] = chunks run, or -(n + 1) when chunk n's N falls outside

@@ -12,9 +12,22 @@ import time
 import numpy as np
 from scipy.optimize import minimize
 
-W_Y, W_S, W_U, W_SL = 10.0, 10.0, 0.1, 100.0
-U_MIN, U_MAX = np.array([-0.6, -5.0]), np.array([0.6, 4.0])
-K_MIN, K_MAX, A_MAX = -0.8, 0.8, 6.0
+
+class Params:
+    """The model parameters of the chunk NLP: TrajectoryOptimizer.__init__'s weights and bounds (:14-47), the
+    constant v_min_fun of optimize_full_trajectory (:476-477), and defect_sign, the sign in front of Simpson's sum
+    (+1: the forward rule of the committed trajectories, see include/mpcplan.h; -1: the committed source's :205).
+    The defaults are the reference's values; dt is Chunk's own argument."""
+
+    def __init__(self, w_y=10.0, w_s=10.0, w_u=0.1, w_slack=100.0, u_min=(-0.6, -5.0), u_max=(0.6, 4.0), k_min=-0.8,
+                 k_max=0.8, a_max=6.0, v_min=0.0, defect_sign=1.0):
+        self.w_y, self.w_s, self.w_u, self.w_slack = float(w_y), float(w_s), float(w_u), float(w_slack)
+        self.u_min, self.u_max = np.array(u_min, float), np.array(u_max, float)
+        self.k_min, self.k_max, self.a_max = float(k_min), float(k_max), float(a_max)
+        self.v_min, self.defect_sign = float(v_min), float(defect_sign)
+
+
+DEFAULT = Params()
 
 
 def dkappa(route, s):
@@ -69,8 +82,9 @@ def dyn_jac(x, u, kr, dkr):
 
 
 class Chunk:
-    def __init__(self, route, N, dt, x0, s_target, final):
+    def __init__(self, route, N, dt, x0, s_target, final, params=None):
         self.r, self.N, self.dt, self.x0, self.st, self.final = route, N, dt, np.asarray(x0, float), s_target, final
+        self.p = DEFAULT if params is None else params
         self.nz = 5 * (N + 1) + 3 * N
 
     def unpack(self, z):
@@ -79,11 +93,12 @@ class Chunk:
 
     def cost(self, z):
         X, U, S = self.unpack(z)
+        p = self.p
         den = max(1, self.r.s_total - self.x0[0])
         c = 0.0
         for k in range(self.N):
-            c += W_Y * (X[k, 1] ** 2 + X[k, 2] ** 2) + W_S * ((self.r.s_total - X[k, 0]) / den) ** 2 + \
-                W_U * (U[k] @ U[k]) + W_SL * S[k] ** 2
+            c += p.w_y * (X[k, 1] ** 2 + X[k, 2] ** 2) + p.w_s * ((self.r.s_total - X[k, 0]) / den) ** 2 + \
+                p.w_u * (U[k] @ U[k]) + p.w_slack * S[k] ** 2
         return c
 
     def defect(self, X, U, k):
@@ -91,7 +106,8 @@ class Chunk:
         f0, f1 = dyn(x0, u, self.r.k_ref_fun(x0[0])), dyn(x1, u, self.r.k_ref_fun(x1[0]))
         xm = 0.5 * (x0 + x1) + h / 8 * (f0 - f1)
         fm = dyn(xm, u, self.r.k_ref_fun(xm[0]))
-        return x1 - (x0 + h / 6 * (f0 + 4 * fm + f1))     # forward HS (the committed trajectories' rule)
+        # defect_sign +1: forward HS (the committed trajectories' rule); -1: the source's x_k - dt/6 (...) (:205)
+        return x1 - (x0 + self.p.defect_sign * (h / 6) * (f0 + 4 * fm + f1))
 
     def defect_jac(self, X, U, k):
         h, x0, x1, u = self.dt, X[k], X[k + 1], U[k]
@@ -102,9 +118,10 @@ class Chunk:
         xm = 0.5 * (x0 + x1) + h / 8 * (f0 - f1)
         Fm, _ = dyn_jac(xm, u, kap(xm[0]), dkappa(self.r, xm[0]))
         I = np.eye(5)
-        D0 = -I - h / 6 * (F0 + 4 * Fm @ (0.5 * I + h / 8 * F0))
-        D1 = I - h / 6 * (4 * Fm @ (0.5 * I - h / 8 * F1) + F1)
-        Du = -h * G
+        sg = self.p.defect_sign
+        D0 = -I - sg * (h / 6) * (F0 + 4 * Fm @ (0.5 * I + h / 8 * F0))
+        D1 = I - sg * (h / 6) * (4 * Fm @ (0.5 * I - h / 8 * F1) + F1)
+        Du = -sg * h * G
         return D0, D1, Du
 
     # constraint functions in the reference's sense (>= 0 / == 0), forward defect
@@ -117,17 +134,17 @@ class Chunk:
 
     def ineq(self, z):
         X, U, S = self.unpack(z)
-        N, out = self.N, []
+        N, out, p = self.N, [], self.p
         if not self.final:
             out.append(X[N, 0] - self.st / 2)
         for k in range(N + 1):
             sl = S[k] if k < N else 0.0
-            out += [X[k, 4] + sl - 0.0, self.r.v_max_fun(X[k, 0]) - (X[k, 4] + sl),
-                    A_MAX - X[k, 3] * X[k, 4] ** 2, A_MAX + X[k, 3] * X[k, 4] ** 2]
+            out += [X[k, 4] + sl - p.v_min, self.r.v_max_fun(X[k, 0]) - (X[k, 4] + sl),
+                    p.a_max - X[k, 3] * X[k, 4] ** 2, p.a_max + X[k, 3] * X[k, 4] ** 2]
         for k in range(N + 1):
-            out += [X[k, 3] - K_MIN, K_MAX - X[k, 3]]
+            out += [X[k, 3] - p.k_min, p.k_max - X[k, 3]]
         for k in range(N):
-            out += [U[k, 0] - U_MIN[0], U_MAX[0] - U[k, 0], U[k, 1] - U_MIN[1], U_MAX[1] - U[k, 1], S[k]]
+            out += [U[k, 0] - p.u_min[0], p.u_max[0] - U[k, 0], U[k, 1] - p.u_min[1], p.u_max[1] - U[k, 1], S[k]]
         return np.array(out)
 
     def ineq_jac(self, z):
@@ -168,19 +185,20 @@ class Chunk:
         N, nz = self.N, self.nz
         X, U, S = self.unpack(z)
         den = max(1, self.r.s_total - self.x0[0])
+        p = self.p
         H = np.zeros(nz)
         g = np.zeros(nz)
         for k in range(N):
-            H[5 * k + 0] = 2 * W_S / den ** 2
-            g[5 * k + 0] = -2 * W_S * (self.r.s_total - X[k, 0]) / den ** 2
-            H[5 * k + 1] = H[5 * k + 2] = 2 * W_Y
-            g[5 * k + 1], g[5 * k + 2] = 2 * W_Y * X[k, 1], 2 * W_Y * X[k, 2]
+            H[5 * k + 0] = 2 * p.w_s / den ** 2
+            g[5 * k + 0] = -2 * p.w_s * (self.r.s_total - X[k, 0]) / den ** 2
+            H[5 * k + 1] = H[5 * k + 2] = 2 * p.w_y
+            g[5 * k + 1], g[5 * k + 2] = 2 * p.w_y * X[k, 1], 2 * p.w_y * X[k, 2]
             iu = 5 * (N + 1) + 2 * k
-            H[iu] = H[iu + 1] = 2 * W_U
-            g[iu], g[iu + 1] = 2 * W_U * U[k, 0], 2 * W_U * U[k, 1]
+            H[iu] = H[iu + 1] = 2 * p.w_u
+            g[iu], g[iu + 1] = 2 * p.w_u * U[k, 0], 2 * p.w_u * U[k, 1]
             isl = 5 * (N + 1) + 2 * N + k
-            H[isl] = 2 * W_SL
-            g[isl] = 2 * W_SL * S[k]
+            H[isl] = 2 * p.w_slack
+            g[isl] = 2 * p.w_slack * S[k]
         return H, g
 
     def z_init(self):
@@ -209,19 +227,20 @@ class Chunk:
         N, nz = self.N, self.nz
         X, U, S = self.unpack(z)
         den = max(1, self.r.s_total - self.x0[0])
+        p = self.p
         H = np.zeros(nz)
         g = np.zeros(nz)
         for k in range(N):
-            H[5 * k + 0] = 2 * W_S / den ** 2
-            g[5 * k + 0] = -2 * W_S * (self.r.s_total - X[k, 0]) / den ** 2
-            H[5 * k + 1] = H[5 * k + 2] = 2 * W_Y
-            g[5 * k + 1], g[5 * k + 2] = 2 * W_Y * X[k, 1], 2 * W_Y * X[k, 2]
+            H[5 * k + 0] = 2 * p.w_s / den ** 2
+            g[5 * k + 0] = -2 * p.w_s * (self.r.s_total - X[k, 0]) / den ** 2
+            H[5 * k + 1] = H[5 * k + 2] = 2 * p.w_y
+            g[5 * k + 1], g[5 * k + 2] = 2 * p.w_y * X[k, 1], 2 * p.w_y * X[k, 2]
             iu = 5 * (N + 1) + 2 * k
-            H[iu] = H[iu + 1] = 2 * W_U
-            g[iu], g[iu + 1] = 2 * W_U * U[k, 0], 2 * W_U * U[k, 1]
+            H[iu] = H[iu + 1] = 2 * p.w_u
+            g[iu], g[iu + 1] = 2 * p.w_u * U[k, 0], 2 * p.w_u * U[k, 1]
             isl = 5 * (N + 1) + 2 * N + k
-            H[isl] = 2 * W_SL
-            g[isl] = 2 * W_SL * S[k]
+            H[isl] = 2 * p.w_slack
+            g[isl] = 2 * p.w_slack * S[k]
         A, b = [], []
         for k in range(N):
             D0, D1, Du = self.defect_jac(X, U, k)

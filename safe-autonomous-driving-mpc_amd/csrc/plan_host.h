@@ -1159,7 +1159,7 @@ inline void optimize(const route* r, const plan_params* p0, int B, int Nmax, con
                 if (!(si < (double)nav)) { err = true; break; }
                 int idx = si <= -(double)nav ? 0 : (int)si;
                 if (idx < 0) idx += nav;
-                const double hz = ceil(size / avg[idx] * 2.0 / 0.3);
+                const double hz = ceil(size / avg[idx] * 2.0 / p0->dt);      // the optimizer's dt (see plan_loop_kernel)
                 if (!(hz >= 1.0 && hz <= (double)Nmax)) { err = true; break; }
                 const int Nc = (int)hz;
                 p.N = Nc;

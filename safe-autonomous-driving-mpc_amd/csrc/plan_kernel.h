@@ -1971,8 +1971,10 @@ __global__ void __launch_bounds__(WAVE) plan_chunk_kernel(KArgs a) {
 // b runs plan b's chunks one after another from starts[b], with no barrier across plans (a launch over B plans
 // lasts as long as the slowest plan's chain of chunks, not the sum over rounds of each round's slowest chunk).
 // Chunk n of plan b: remaining = s_total - s; final when remaining < 2 max_chunk_size (size = remaining, else
-// max_chunk_size); N = ceil(size / avg[int(s / 5)] * 2 / 0.3) with avg[i] = mean(vmax[i:]) (the reference's
-// np.mean over the speed-limit array, :507, computed by the caller); the chunk's plan, horizon, final flag and
+// max_chunk_size); N = ceil(size / avg[int(s / 5)] * 2 / P.dt) with avg[i] = mean(vmax[i:]) (the reference's
+// np.mean over the speed-limit array, :507, computed by the caller).  The divisor is the optimizer's dt, not a
+// literal: the reference's loop has one local, dt = 0.3 (:514), which it divides the horizon by (:515) and hands
+// to the chunk's TrajectoryOptimizer (:517), so N dt covers the horizon at any dt.  The chunk's plan, horizon, final flag and
 // status go to slot (b, n); the next start is X[N/2] (the reference's commit of the first int(N/2)
 // intervals, :523-541) or X[N] after a final chunk.  The loop ends when remaining <= 0.1 or after
 // max_chunks chunks; nchunks[b] = chunks run, or -(n + 1) when chunk n's horizon is outside [1, Nmax] (or
@@ -2016,7 +2018,7 @@ __global__ void __launch_bounds__(WAVE) plan_loop_kernel(LArgs a) {
         if (!(si < (double)a.nav)) { err = true; break; }
         int idx = si <= -(double)a.nav ? 0 : (int)si;
         if (idx < 0) idx += a.nav;
-        const double hz = ceil(size / a.avg[idx] * 2.0 / 0.3);
+        const double hz = ceil(size / a.avg[idx] * 2.0 / a.P.dt);
         if (!(hz >= 1.0 && hz <= (double)Nm)) { err = true; break; }
         X.N = (int)hz;
         X.fin = fin;

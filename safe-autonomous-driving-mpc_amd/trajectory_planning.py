@@ -334,6 +334,14 @@ def _commit(pieces, X, U, S, n, fin):
     return pieces[-1][0][-1]
 
 
+def _loop_dt(opt):
+    """The chunk loop's dt.  The reference's loop has one local, dt = 0.3 (:514): it divides the horizon by it
+    (N = ceil(horizon / dt), :515) and hands it to the chunk's TrajectoryOptimizer (:517), so the horizon rule's
+    0.3 is the optimizer's dt and N dt covers the horizon.  An optimizer given to the batch loop with another dt
+    gets that dt in both places; without one it is the reference's 0.3."""
+    return 0.3 if opt.dt is None else float(opt.dt)
+
+
 def _device_loop(route, starts, max_chunk_size, max_chunks, device, pieces, statuses, horizons, opt, seg=64,
                  timing=None):
     """optimize_full_trajectory_batch's chunk loop as plan_optimize_device launches: every plan advances on its
@@ -347,9 +355,10 @@ def _device_loop(route, starts, max_chunk_size, max_chunks, device, pieces, stat
     s_total = route.s_total
     vm = np.asarray(route.vmax, np.float64)
     avg = np.array([float(np.mean(vm[i:])) for i in range(vm.size)])     # route.avg_speed_from(5 i), :507
-    nb = int(np.max(np.ceil(2.0 * max_chunk_size / avg * 2.0 / 0.3)))
+    dt = _loop_dt(opt)
+    nb = int(np.max(np.ceil(2.0 * max_chunk_size / avg * 2.0 / dt)))
     Nmax = min(max(nb, 1), mpcplan.PLAN_MAX_N)
-    opt.N, opt.dt = Nmax, 0.3
+    opt.N, opt.dt = Nmax, dt
     pl = mpcplan.Planner(route, opt.params(0.0), device=device)
     cur = np.asarray(starts, np.float64).copy()
     used = np.zeros(cur.shape[0], int)
@@ -398,8 +407,8 @@ def _device_loop(route, starts, max_chunk_size, max_chunks, device, pieces, stat
         pl.close()
 
 
-def optimize_full_trajectory_batch(route, starts, max_chunk_size=20, max_chunks=10000, device=0, solve_chunks=None,
-                                   device_loop=True):
+def optimize_full_trajectory_batch(route, starts, max_chunk_size=20, max_chunks=10000, device=None, solve_chunks=None,
+                                   device_loop=True, optimizer=None):
     """The chunk loop of optimize_full_trajectory (trajectory_planning.py:491-548) for B plans on one route at
     once, from B start states (e.g. a fleet re-planning from where each vehicle is): every round solves the
     current chunk of each unfinished plan in one batched call, each chunk with its own horizon (the
@@ -411,7 +420,11 @@ def optimize_full_trajectory_batch(route, starts, max_chunk_size=20, max_chunks=
     -> dict(X, U, S, status) replaces the GPU batch (tests drive this loop with the CPU oracle).
     device_loop (GPU, the default): the whole loop runs on the device (plan_optimize_device), each plan on its
     own wavefront with no barrier across plans; False: one batched chunk launch per round, the host loop
-    below.  Both give the same plans bit for bit (the same chunk solver on the same chunk inputs)."""
+    below.  Both give the same plans bit for bit (the same chunk solver on the same chunk inputs).
+    device: 0 when neither it nor an optimizer is given.
+    optimizer: a TrajectoryOptimizer whose weights, bounds and dt the loop takes instead of the reference's
+    (_loop_dt: its dt is the horizon rule's divisor too); the loop runs on its device, and a `device` argument that
+    names another one raises ValueError."""
     from sanity_checks import plan_check_summary
     if isinstance(route, dict):
         import routes
@@ -426,7 +439,11 @@ def optimize_full_trajectory_batch(route, starts, max_chunk_size=20, max_chunks=
     statuses = [[] for _ in range(B)]
     horizons = [[] for _ in range(B)]
     done = np.zeros(B, bool)
-    opt = TrajectoryOptimizer(device=device)
+    if optimizer is not None and device is not None and int(device) != int(optimizer.device):
+        raise ValueError(f"device = {device} but the optimizer's device is {optimizer.device}")
+    opt = TrajectoryOptimizer(device=0 if device is None else device) if optimizer is None else optimizer
+    device = opt.device
+    dt = _loop_dt(opt)
     pl = None
     if solve_chunks is None and device_loop:
         _device_loop(route, starts, max_chunk_size, max_chunks, device, pieces, statuses, horizons, opt,
@@ -441,13 +458,13 @@ def optimize_full_trajectory_batch(route, starts, max_chunk_size=20, max_chunks=
         fin = (rem < max_chunk_size * 2).astype(np.int32)
         size = np.where(fin == 1, rem, max_chunk_size)
         st = cur[act, 0] + size
-        N = np.array([int(np.ceil(size[i] / route.avg_speed_from(cur[b, 0]) * 2.0 / 0.3))
+        N = np.array([int(np.ceil(size[i] / route.avg_speed_from(cur[b, 0]) * 2.0 / dt))
                       for i, b in enumerate(act)], np.int32)
         if N.max() > mpcplan.PLAN_MAX_N:
             raise ValueError(f"chunk horizon N={N.max()} exceeds PLAN_MAX_N={mpcplan.PLAN_MAX_N}")
         if solve_chunks is None:
             if pl is None:
-                opt.N, opt.dt = int(N.max()), 0.3
+                opt.N, opt.dt = int(N.max()), dt
                 pl = mpcplan.Planner(route, opt.params(0.0), device=device)
             r = pl.solve_chunks(cur[act], st, fin, N)
         else:

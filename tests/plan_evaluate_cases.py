@@ -71,6 +71,7 @@ def ref_rows(ch, z):
 
 
 def _acceptable(ch, X, U, rows):
+    """The acceptance rule of the module docstring, at the chunk's own dt."""
     r = np.sort(rows[~np.isnan(rows)])
     if np.abs(r).min() < 1e-6 or r[1] - r[0] < 1e-6:
         return False
@@ -81,18 +82,20 @@ def _acceptable(ch, X, U, rows):
             import plan_ref as PR
             f0 = PR.dyn(X[k], U[k], ch.r.k_ref_fun(X[k, 0]))
             f1 = PR.dyn(X[k + 1], U[k], ch.r.k_ref_fun(X[k + 1, 0]))
-            pts.append(0.5 * (X[k] + X[k + 1]) + DT / 8 * (f0 - f1))
+            pts.append(0.5 * (X[k] + X[k + 1]) + ch.dt / 8 * (f0 - f1))
         for x in pts:
             if np.abs(way - x[0]).min() < 1e-6 or abs(1.0 - x[1] * ch.r.k_ref_fun(x[0])) < 1e-3:
                 return False
     return True
 
 
-def _make(route, N, final, rng):
+def _make(route, N, final, rng, dt=DT, params=None):
+    """One case; dt and params (plan_ref.Params, None: the defaults) state the NLP it is evaluated under
+    (tests/plan_params_cases.py regenerates the cases under its parameter sets)."""
     import plan_ref as PR
     redraws = 0
     while True:
-        D = N * DT * route.avg_speed_from(0.5 * route.s_total) / 2.0
+        D = N * dt * route.avg_speed_from(0.5 * route.s_total) / 2.0
         if final:
             s0, target = route.s_total - D, route.s_total
             vcap = min(route.v_max_fun(s0), np.sqrt(2.0 * 2.5 * D))
@@ -101,7 +104,7 @@ def _make(route, N, final, rng):
             target = s0 + D
             vcap = route.v_max_fun(s0)
         x0 = np.array([s0, rng.normal(0, 0.05), rng.normal(0, 0.01), route.k_ref_fun(s0), rng.uniform(0.2, 0.9) * vcap])
-        ch = PR.Chunk(route, N, DT, x0, target, bool(final))
+        ch = PR.Chunk(route, N, dt, x0, target, bool(final), params)
         X, U, S = ch.unpack(ch.z_init())
         X = X + rng.normal(0, 0.05, X.shape)
         U = U + rng.normal(0, 0.3, U.shape)
