@@ -36,7 +36,8 @@ extern "C" {
  * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
  *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
  *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device,
- *    mpc_closed_loop_traced and mpc_closed_loop_warm / mpc_default_warm. */
+ *    mpc_closed_loop_traced, mpc_closed_loop_warm / mpc_default_warm and mpc_gradient_batch /
+ *    mpc_gradient_batch_device. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -192,6 +193,56 @@ int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const double* obs, c
 int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                               const double* U, double* Xpred, double* summary, double* terms, double* rows,
                               void* stream);
+
+/* Batched gradients of what mpc_evaluate_batch computes, at ANY control sequence U: the gradient of
+ * TrajectoryTracker.cost(U, x0) in U and in x0, and J' lam for the rows of constraints(x0, obstacles) weighted by
+ * lam, by one reverse (adjoint) sweep each over the rollout predict(x0, U) -- exact, where the reference's SLSQP
+ * differences 2N + 1 rollouts.  The function differentiated is the evaluator's: the table is piecewise linear and
+ * its slope at s is that of the interval the lookup selects (the left one at a knot, 0 for s >= s_max); the safe
+ * distance max(obstacle_safety_distance, v * max_time_2_obs) has slope max_time_2_obs in v only where
+ * v * max_time_2_obs > obstacle_safety_distance (the reference's max).  The solver knobs (linearization too) are
+ * ignored.  No version step: detect it by the presence of its symbol.
+ *   x0, obs, n_obs, U   mpc_evaluate_batch's contract exactly
+ *   lam [B][N][7 + max_obs] or NULL   row weights in the layout of `rows`; columns >= 7 + n_obs[b] are never read
+ *                       (a `rows`-shaped array with NaN there is fine)
+ * outputs (any may be NULL; all NULL is allowed and launches nothing; jtl without lam is MPC_E_ARG):
+ *   grad    [B][N][2]   d cost / d u_k, k = 0..N-1
+ *   jtl     [B][N][2]   sum over stages and rows of lam * d g / d u_k (J' lam)
+ *   gx0     [B][5]      d cost / d x0
+ *   costate [B][N][5]   p_1..p_N of the cost: p_k = d cost / d x_k with the later stages folded in
+ *   summary [B][MPC_GR_NQ]   the MPC_GRQ_* columns below
+ * With x_k = (s, d, o, k, v) the rollout, e_d = d - d_ref(s) (e_o, e_v alike) and d_ref' the table slope at s:
+ *   q_k  (k = 1..N)  = (-((2 w_d e_d d_ref' + 2 w_o e_o o_ref') + 2 w_v e_v v_ref'), 2 w_d e_d, 2 w_o e_o, 0,
+ *                      2 w_v e_v) with 2 w_d e_d = (2 w_d) * e_d
+ *   p_N = q_N;  p_k = q_k + A_k' p_k+1 for k = N-1..1, each component one addition q_k[i] + (A_k' p_k+1)[i];
+ *   A_k' p = (p_s + a20 p_o, p_d, p_o + a12 p_d, p_k + a23 p_o, ((p_v + dt p_s) + a14 p_d) + a24 p_o) with
+ *        a12 = dt v, a14 = dt o, a20 = dt (-v k_ref'), a23 = dt v, a24 = dt (k - k_ref) at x_k
+ *   grad[k] = ((2 w_u1) u1_k + dt p_k+1[3], (2 w_u2) u2_k + dt p_k+1[4]);   gx0 = A_0' p_1
+ *   the row side repeats the sweep with q_k replaced by c_k = sum_r lam[k][r] grad_x g_k,r: per component one
+ *        running sum from 0 over the rows in the reference's order (the six lane rows, the obstacles, v) that skips
+ *        the rows whose coefficient in that component is structurally zero, adding lam * coefficient (lam itself
+ *        where the coefficient is +-1); jtl[k] = dt (p'_k+1[3], p'_k+1[4])
+ * The results do not depend on the backend, the lane-group width or B; a NaN in one instance's inputs stays in
+ * that instance.  In the summary a NaN enters a maximum or minimum and stays (numpy's rule).
+ * Misuse is MPC_E_ARG with a message; B == 0 succeeds. */
+#define MPC_GRQ_COST 0           /* the same bits as MPC_EVQ_COST                                              */
+#define MPC_GRQ_GRAD_INF 1       /* max |grad|                                                                 */
+#define MPC_GRQ_LAG_INF 2        /* max |grad - jtl|; equals GRAD_INF when lam is NULL                         */
+#define MPC_GRQ_PG_INF 3         /* max over components of |clamp(u - r, u_min, u_max) - u| with r = grad - jtl:
+                                    the projected-gradient measure for the bounds handed to SLSQP              */
+#define MPC_GRQ_COMPL 4          /* max |lam * g| over the rows read; NaN without lam                          */
+#define MPC_GRQ_MIN_LAM 5        /* min lam over the rows read; NaN without lam                                */
+#define MPC_GR_NQ 6
+int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs, const double* U,
+                       const double* lam, double* grad, double* jtl, double* gx0, double* costate, double* summary);
+/* Same, with device pointers, launched asynchronously on `stream`: one kernel, no host synchronisation, no
+ * allocation, graph-capturable.  The double arrays must be 8-byte aligned (MPC_E_ARG otherwise).  The call shares
+ * no state with the solver, so it may overlap a solve on another stream of the same context.  On a host context
+ * (device = -1) the pointers are host memory and the call is synchronous; every output equals the device's bit for
+ * bit. */
+int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                              const double* U, const double* lam, double* grad, double* jtl, double* gx0,
+                              double* costate, double* summary, void* stream);
 
 /* Reference-signal service on the device table: TrajectoryLoader.get_state / get_control
  * (trajectory_loader.py:86-102), batched. Host buffers, synchronous.  out_state [n][5], out_control [n][2]. */

@@ -891,6 +891,44 @@ inline void evaluate_one(const DevTable& R, const mpc_params& p, const double (*
     if (terms) std::memcpy(terms, Z.t, sizeof(Z.t));
 }
 
+// mpc_gradient_batch for one instance (include/mpcqp.h): tracker_model.h's steps of a stage, of the reverse sweep
+// and of a control, which mpc_gradient_kernel (gradient_kernel.h) runs a lane each, folded here one after the
+// other, so every output equals the device's bit for bit.  X is the rollout predict(x0, U) [N+1][5]; lam [N][rw]
+// (rw = 7 + params.max_obs), grad [N][2], jtl [N][2], gx0 [5], costate [N][5] and summary [MPC_GR_NQ] may be null.
+inline void gradient_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
+                         int rw, const double* U, const double* lam, double* grad, double* jtl, double* gx0,
+                         double* costate, double* summary) {
+    const int N = p.N;
+    const KParams P = model_params(p);
+    double ct[kMaxN][5], part[kMaxN], A[kMaxN][5], q[kMaxN][5], c[kMaxN][5];
+    EvRun run = ev_run_begin();
+    GrRun G = gr_run_begin();
+    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], ct[k], run);
+    for (int j = 0; j <= N; ++j) {
+        double st[5], sl[4];
+        get_state(R, X[j][0], st, sl);
+        if (j < N) stage_A(X[j], P.dt, st[3], sl[2], A[j]);
+        if (j >= 1) {
+            EvStage S = ev_stage_begin();
+            ev_stage(P, j, X[j], st, obs, nobs, rw, ct[j - 1], nullptr, S, run);
+            gr_stage(P, j, X[j], st, sl, obs, nobs, lam ? lam + (size_t)(j - 1) * rw : nullptr, q[j - 1], c[j - 1], G);
+            part[j - 1] = 0.0;
+        }
+    }
+    double g0[5], g0r[5];
+    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0);
+    if (lam) gr_sweep(N, P.dt, &A[0][0], &c[0][0], g0r);
+    for (int k = 0; k < N; ++k) {
+        double g[2], jt[2];
+        gr_control(P, U[2 * k], U[2 * k + 1], q[k], lam ? c[k] : nullptr, g, jt, G);
+        if (grad) std::memcpy(grad + 2 * k, g, sizeof(g));
+        if (jtl) std::memcpy(jtl + 2 * k, jt, sizeof(jt));
+    }
+    if (gx0) std::memcpy(gx0, g0, sizeof(g0));
+    if (costate) std::memcpy(costate, q, sizeof(double) * 5 * N);
+    if (summary) gr_summary(summary, ev_sums(N, &ct[0][0], part).cost, G, lam != nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------
 // shared pieces of the closed-loop members of Backend
 // ---------------------------------------------------------------------------------------------
@@ -1068,6 +1106,25 @@ struct Backend {
                              summary ? summary + (size_t)b * MPC_EV_NQ : nullptr,
                              terms ? terms + 5 * (size_t)b : nullptr,
                              rows ? rows + (size_t)b * N * rw : nullptr);
+        });
+    }
+
+    // mpc_gradient_batch on host buffers (the device entry's argument contract); lam is [B][N][7 + p.max_obs]
+    void gradient_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                        const double* U, const double* lam, double* grad, double* jtl, double* gx0, double* costate,
+                        double* summary) const {
+        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
+        parallel(p, B, [&](Worker& w, int b) {
+            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
+            no = no < 0 ? 0 : (no > mo ? mo : no);
+            double X[kMaxN + 1][5];
+            const double* Ub = U + (size_t)b * 2 * N;
+            w.predict(x0 + 5 * (size_t)b, Ub, X);
+            gradient_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
+                         lam ? lam + (size_t)b * N * rw : nullptr, grad ? grad + (size_t)b * 2 * N : nullptr,
+                         jtl ? jtl + (size_t)b * 2 * N : nullptr, gx0 ? gx0 + 5 * (size_t)b : nullptr,
+                         costate ? costate + (size_t)b * 5 * N : nullptr,
+                         summary ? summary + (size_t)b * MPC_GR_NQ : nullptr);
         });
     }
 

@@ -17,7 +17,7 @@
 // the reference's numpy arithmetic; the solver uses explicit fma() where it wants fusion.
 //
 // This file is the library's one translation unit.  The device code lives in the headers it includes:
-//   tracker_model.h        table, parameters, lookups, constants, row model, evaluator steps (shared with the host)
+//   tracker_model.h        table, parameters, lookups, constants, row model, evaluator and gradient steps (shared with the host)
 //   device_common.h        LDS layout, cross-lane helpers, rollout, fences
 //   riccati_lanes.h        the lane-distributed Riccati recursions (inline-asm DPP chains)
 //   solve_kernel.h         mpc_solve_kernel and mpc_lookup_kernel
@@ -29,6 +29,7 @@
 //   trace_kernels.h        the plan traces' gap and history kernels (the solver's U / Xpred of every step)
 //   warm_kernels.h         the warm starts' carry and keep kernels (the previous plan as the next ubar)
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
+//   gradient_kernel.h      the batched gradients of that cost and of those rows (reverse sweeps)
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points; the driver the closed-loop entries share is closed_loop_host.h) and, last, the comm
 // layer (comm.h).
@@ -56,6 +57,7 @@
 #include "trace_kernels.h"
 #include "warm_kernels.h"
 #include "evaluate_kernel.h"
+#include "gradient_kernel.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -104,7 +106,8 @@ struct mpc_ctx {
     int *nobs, *status, *iters;
     double *ls, *lst, *lct;
     size_t cap_lookup;
-    // mpc_evaluate_batch's output staging (summary, terms, rows), grown on demand
+    // mpc_evaluate_batch's output staging (summary, terms, rows) and mpc_gradient_batch's staging (lam and its
+    // outputs), grown on demand
     double* ev;
     size_t cap_ev;      // doubles
     hipStream_t stream;
@@ -605,6 +608,107 @@ extern "C" int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const dou
     if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, sizeof(double) * n_sum, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     if (terms) HIPCHK(hipMemcpyAsync(terms, d_terms, sizeof(double) * n_terms, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     if (rows) HIPCHK(hipMemcpyAsync(rows, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
+    return MPC_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------
+// batched gradients (gradient_kernel.h)
+// ------------------------------------------------------------------------------------------
+// the argument checks both entries share (after ctx, B and the B == 0 return)
+static int gradient_args(mpc_ctx* c, const double* x0, const double* obs, const double* U, const double* lam,
+                         const double* jtl) {
+    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
+    if (!U) return fail(MPC_E_ARG, "U is NULL (the gradient needs the control sequence to differentiate at)");
+    if (obs && c->p.max_obs == 0)
+        return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
+    if (jtl && !lam) return fail(MPC_E_ARG, "jtl asked for but lam is NULL (J' lam needs the row weights)");
+    return check_params(&c->p);
+}
+
+extern "C" int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                         const double* U, const double* lam, double* grad, double* jtl, double* gx0,
+                                         double* costate, double* summary, void* stream) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(MPC_E_ARG, "B < 0");
+    if (B == 0) return MPC_SUCCESS;
+    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
+    int rc = gradient_args(c, x0, obs, U, lam, jtl);
+    if (rc) return rc;
+    if (((uintptr_t)x0 | (uintptr_t)obs | (uintptr_t)U | (uintptr_t)lam | (uintptr_t)grad | (uintptr_t)jtl |
+         (uintptr_t)gx0 | (uintptr_t)costate | (uintptr_t)summary) & 7)
+        return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->gradient_batch(c->p, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary);
+        });
+    KParams kp = kparams(&c->p);
+    const int rw = 7 + c->p.max_obs;       // lam keeps the context's slab width without obstacles too
+    if (!obs) kp.max_obs = 0;
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const int GL = kp.N + 1 <= 16 ? 16 : (kp.N + 1 <= 32 ? 32 : 64);     // launch_solve's rule
+    const dim3 grid((B + WAVE / GL - 1) / (WAVE / GL));
+    hipStream_t st = (hipStream_t)stream;
+#define MPC_GR_LAUNCH(GLV, OBSV)                                                                              \
+    hipLaunchKernelGGL((mpc_gradient_kernel<GLV, OBSV>), grid, dim3(WAVE), 0, st, c->tab, kp, B, rw, x0, obs, \
+                       obs ? n_obs : nullptr, U, lam, grad, jtl, gx0, costate, summary)
+    if (GL == 16) { if (obs) MPC_GR_LAUNCH(16, true); else MPC_GR_LAUNCH(16, false); }
+    else if (GL == 32) { if (obs) MPC_GR_LAUNCH(32, true); else MPC_GR_LAUNCH(32, false); }
+    else { if (obs) MPC_GR_LAUNCH(64, true); else MPC_GR_LAUNCH(64, false); }
+#undef MPC_GR_LAUNCH
+    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                  const double* U, const double* lam, double* grad, double* jtl, double* gx0,
+                                  double* costate, double* summary) {
+    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(MPC_E_ARG, "B < 0");
+    if (B == 0) return MPC_SUCCESS;
+    int rc = gradient_args(c, x0, obs, U, lam, jtl);
+    if (rc) return rc;
+    const int N = c->p.N, mo = c->p.max_obs, rw = 7 + mo;
+    if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->gradient_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, U, lam, grad, jtl, gx0, costate,
+                                   summary);
+        });
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    rc = ensure_staging(c, B, N, mo);
+    if (rc) return rc;
+    const size_t n_lam = lam ? (size_t)B * N * rw : 0, n_u = (size_t)B * N * 2, n_x0 = (size_t)B * 5,
+                 n_cos = (size_t)B * N * 5, n_sum = (size_t)B * MPC_GR_NQ;
+    const size_t need = n_lam + 2 * n_u + n_x0 + n_cos + n_sum;
+    if (need > c->cap_ev) {
+        c->cap_ev = 0;
+        if (grow(&c->ev, need)) return fail(MPC_E_ALLOC, "hipMalloc gradient staging");
+        c->cap_ev = need;
+    }
+    double *d_lam = c->ev, *d_grad = d_lam + n_lam, *d_jtl = d_grad + n_u, *d_gx0 = d_jtl + n_u,
+           *d_cos = d_gx0 + n_x0, *d_sum = d_cos + n_cos;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    const bool use_obs = obs != nullptr;
+    if (use_obs) {
+        HIPCHK(hipMemcpyAsync(c->obs, obs, sizeof(double) * 2 * mo * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+        if (n_obs) HIPCHK(hipMemcpyAsync(c->nobs, n_obs, sizeof(int) * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    }
+    HIPCHK(hipMemcpyAsync(c->ub, U, sizeof(double) * n_u, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    if (lam) HIPCHK(hipMemcpyAsync(d_lam, lam, sizeof(double) * n_lam, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
+    rc = mpc_gradient_batch_device(c, B, c->x0, use_obs ? c->obs : nullptr, use_obs && n_obs ? c->nobs : nullptr,
+                                   c->ub, lam ? d_lam : nullptr, grad ? d_grad : nullptr, jtl ? d_jtl : nullptr,
+                                   gx0 ? d_gx0 : nullptr, costate ? d_cos : nullptr, summary ? d_sum : nullptr,
+                                   (void*)s);
+    if (rc) return rc;
+    if (grad) HIPCHK(hipMemcpyAsync(grad, d_grad, sizeof(double) * n_u, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (jtl) HIPCHK(hipMemcpyAsync(jtl, d_jtl, sizeof(double) * n_u, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (gx0) HIPCHK(hipMemcpyAsync(gx0, d_gx0, sizeof(double) * n_x0, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (costate)
+        HIPCHK(hipMemcpyAsync(costate, d_cos, sizeof(double) * n_cos, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
+    if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, sizeof(double) * n_sum, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
     HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
     return MPC_SUCCESS;
 }

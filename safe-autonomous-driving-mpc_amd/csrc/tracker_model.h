@@ -1,8 +1,9 @@
-// tracker_model.h -- the tracker's model, stated once for its kernels (solve_kernel.h, evaluate_kernel.h, the
-// closed-loop kernels) and for its host backend (cpu_backend.h): the view of the reference-signal table and the
-// lookups on it, the solver's constants, the model derived from mpc_params (lane bound, which rows exist, the row
-// coefficients, the row and box values of a stage, the A_k coefficients) and the evaluator's steps.  Both sides keep
-// their own storage, loops, lane mapping and reductions and hand single values in.  One exception: mpc_solve_kernel
+// tracker_model.h -- the tracker's model, stated once for its kernels (solve_kernel.h, evaluate_kernel.h,
+// gradient_kernel.h, the closed-loop kernels) and for its host backend (cpu_backend.h): the view of the
+// reference-signal table and the lookups on it, the solver's constants, the model derived from mpc_params (lane
+// bound, which rows exist, the row coefficients, the row and box values of a stage, the A_k coefficients), the
+// evaluator's steps and the gradient's steps.  Both sides keep their own storage, loops, lane mapping and
+// reductions and hand single values in.  One exception: mpc_solve_kernel
 // keeps its own text of stage_A, nearest_obstacle, row_values and box_values (and of loop_steps.h's warm start) in
 // its K1 / K2 blocks, because its register allocation moves with any other form of them; the comments there say so.
 // What may be written here: single rounded FP64 operations, integer arithmetic, fabs and comparisons (sin / cos for
@@ -368,4 +369,127 @@ TRACKER_MODEL_INLINE void ev_summary(double* o, const EvSums& Z, double min_row,
     o[MPC_EVQ_MIN_OBS] = ((flags & EV_NAN_OBS) || nobs == 0) ? NAN : fo + 0.0;
     o[MPC_EVQ_MIN_V] = (flags & EV_NAN_V) ? NAN : fv + 0.0;
     o[MPC_EVQ_BOX] = (flags & EV_NAN_BOX) ? NAN : bx + 0.0;
+}
+
+// ------------------------------------------------------------------------------------------
+// the gradient (mpc_gradient_batch, include/mpcqp.h): the derivative of what the evaluator computes, by one reverse
+// (adjoint) sweep over the rollout for the cost and one for the rows weighted by lam.  The table is piecewise linear:
+// its slope at s is get_state's sl[] (the interval seg_t selects, so the left one at a knot; 0 past s_max)
+// ------------------------------------------------------------------------------------------
+// m <- max / min(m, a) with numpy's NaN rule (loop_steps.h's keep_max / keep_min): a NaN enters and stays
+TRACKER_MODEL_INLINE void gr_nmax(double& m, double a) {
+    if (a > m || a != a) m = a;
+}
+TRACKER_MODEL_INLINE void gr_nmin(double& m, double a) {
+    if (a < m || a != a) m = a;
+}
+// The running extremes of the summary: a lane's on the device (reduced over the group afterwards), the whole
+// instance's on the host.  The maxima are of absolute values, so they start from 0
+struct GrRun {
+    double ginf, linf, pginf, compl_, minlam;
+};
+TRACKER_MODEL_INLINE GrRun gr_run_begin() { return GrRun{0.0, 0.0, 0.0, 0.0, INFINITY}; }
+
+// Stage j at the rolled-out state x, with st the reference state at x[0] and sl its slopes (d', o', k', v'):
+//   q[5]  the gradient of the stage's cost terms in (s, d, o, k, v)
+//   c[5]  sum_r lam[r] grad_x g_r over the stage's rows in the reference's order (the six lane rows, the obstacles,
+//         v), each component one running sum from 0 that skips the rows whose coefficient in it is structurally 0;
+//         lam is the stage's slice in the `rows` layout (0..5 lane, 6 v, 7 + i obstacle i), columns >= 7 + nobs are
+//         not read.  Zero when lam is null
+// and into R the complementarity |lam_r g_r| and lam_r of every row read.  The row values are ev_stage's expressions
+TRACKER_MODEL_INLINE void gr_stage(const KParams& P, int j, const double* x, const double* st, const double* sl,
+                                   const double* obs, int nobs, const double* lam, double* q, double* c, GrRun& R) {
+    const double s = x[0], d = x[1], o = x[2], v = x[4];
+    const double gd = (2.0 * P.w_d) * (d - st[1]);
+    const double go = (2.0 * P.w_o) * (o - st[2]);
+    const double gv = (2.0 * P.w_v) * (v - st[4]);
+    q[0] = -((gd * sl[0] + go * sl[1]) + gv * sl[3]);
+    q[1] = gd;
+    q[2] = go;
+    q[3] = 0.0;
+    q[4] = gv;
+    c[0] = c[1] = c[2] = c[3] = c[4] = 0.0;
+    if (!lam) return;
+    auto visit = [&](double l, double g) {
+        gr_nmax(R.compl_, fabs(l * g));
+        gr_nmin(R.minlam, l);
+    };
+    const double bl = P.sl, h = P.L / 2.0;
+    const double vf = d + h * o, vl = d + P.L * o;
+    const double g[6] = {bl - d, d + bl, bl - vf, vf + bl, bl - vl, vl + bl};
+    const double go_[3] = {0.0, h, P.L};              // |dg/do| of the row pairs; dg/dd = -1, +1 within a pair
+    TRACKER_UNROLL
+    for (int a = 0; a < 6; ++a) {
+        const double l = lam[a];
+        c[1] = (a & 1) ? c[1] + l : c[1] - l;
+        if (a >= 2) c[2] = (a & 1) ? c[2] + l * go_[a >> 1] : c[2] - l * go_[a >> 1];
+        visit(l, g[a]);
+    }
+    if (nobs > 0) {
+        const double tk = (double)j * P.dt;
+        const double vt = v * P.tgap;
+        const bool gap = vt > P.osd;                   // the reference's max(osd, v * tgap) follows v
+        const double safe = gap ? vt : P.osd;
+        for (int i = 0; i < nobs; ++i) {
+            const double l = lam[7 + i];
+            const double sop = obs[2 * i] + obs[2 * i + 1] * tk;
+            c[0] = c[0] - l;
+            if (gap) c[4] = c[4] - l * P.tgap;
+            visit(l, (sop - s) - safe);
+        }
+    }
+    c[4] = c[4] + lam[6];
+    visit(lam[6], v);
+}
+
+// y = A' p with a = stage_A's (a12, a14, a20, a23, a24)
+TRACKER_MODEL_INLINE void gr_AT(const double* a, double dt, const double* p, double* y) {
+    y[0] = p[0] + a[2] * p[2];
+    y[1] = p[1];
+    y[2] = p[2] + a[0] * p[1];
+    y[3] = p[3] + a[3] * p[2];
+    y[4] = ((p[4] + dt * p[0]) + a[1] * p[1]) + a[4] * p[2];
+}
+// The reverse sweep, in place: z [N][5] holds the stage terms of stages 1..N and returns the costates p_1..p_N
+// (p_N = z_N; p_k = z_k + A_k' p_k+1 for k = N-1..1); A [N][5] holds stage_A at x_0..x_N-1; g0 = A_0' p_1
+TRACKER_MODEL_INLINE void gr_sweep(int N, double dt, const double* A, double* z, double* g0) {
+    double y[5];
+    for (int k = N - 1; k >= 1; --k) {
+        gr_AT(A + 5 * k, dt, z + 5 * k, y);
+        TRACKER_UNROLL
+        for (int a = 0; a < 5; ++a) z[5 * (k - 1) + a] = z[5 * (k - 1) + a] + y[a];
+    }
+    gr_AT(A, dt, z, y);
+    TRACKER_UNROLL
+    for (int a = 0; a < 5; ++a) g0[a] = y[a];
+}
+// Control k = (u1, u2) with p = p_k+1 of the cost and pr = p'_k+1 of the rows (null without lam): its gradient g[2],
+// its J' lam jt[2] (zero without lam), and into R |g|, |g - jt| and the projected-gradient measure
+// |clamp(u - (g - jt), u_min, u_max) - u| for the bounds handed to SLSQP
+TRACKER_MODEL_INLINE void gr_control(const KParams& P, double u1, double u2, const double* p, const double* pr,
+                                     double* g, double* jt, GrRun& R) {
+    g[0] = (2.0 * P.w_u1) * u1 + P.dt * p[3];
+    g[1] = (2.0 * P.w_u2) * u2 + P.dt * p[4];
+    jt[0] = pr ? P.dt * pr[3] : 0.0;
+    jt[1] = pr ? P.dt * pr[4] : 0.0;
+    const double u[2] = {u1, u2}, lo[2] = {P.u_min0, P.u_min1}, hi[2] = {P.u_max0, P.u_max1};
+    TRACKER_UNROLL
+    for (int a = 0; a < 2; ++a) {
+        const double r = pr ? g[a] - jt[a] : g[a];
+        const double t = u[a] - r;
+        const double cl = t < lo[a] ? lo[a] : (t > hi[a] ? hi[a] : t);     // a NaN passes through
+        gr_nmax(R.ginf, fabs(g[a]));
+        gr_nmax(R.linf, fabs(r));
+        gr_nmax(R.pginf, fabs(cl - u[a]));
+    }
+}
+// The summary row o [MPC_GR_NQ] from the instance's extremes; + 0.0: a minimum of -0.0 and 0.0 comes out as 0.0
+// whichever the reduction met first
+TRACKER_MODEL_INLINE void gr_summary(double* o, double cost, const GrRun& R, bool has_lam) {
+    o[MPC_GRQ_COST] = cost;
+    o[MPC_GRQ_GRAD_INF] = R.ginf;
+    o[MPC_GRQ_LAG_INF] = R.linf;
+    o[MPC_GRQ_PG_INF] = R.pginf;
+    o[MPC_GRQ_COMPL] = has_lam ? R.compl_ : NAN;
+    o[MPC_GRQ_MIN_LAM] = has_lam ? R.minlam + 0.0 : NAN;
 }

@@ -72,7 +72,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_gradient_batch", "mpc_gradient_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -116,6 +116,10 @@ EVQ_COST, EVQ_MIN_ROW, EVQ_ARGMIN_STAGE, EVQ_ARGMIN_KIND, EVQ_L1, EVQ_N_NEG = 0,
 EVQ_MIN_LANE, EVQ_MIN_OBS, EVQ_MIN_V, EVQ_BOX = 6, 7, 8, 9
 EV_NQ = 10
 EVQ_FIELDS = ("cost", "min_row", "argmin_stage", "argmin_kind", "l1", "n_neg", "min_lane", "min_obs", "min_v", "box")
+# mpc_gradient_batch: the columns of its per-instance summary (MPC_GRQ_*)
+GRQ_COST, GRQ_GRAD_INF, GRQ_LAG_INF, GRQ_PG_INF, GRQ_COMPL, GRQ_MIN_LAM = 0, 1, 2, 3, 4, 5
+GR_NQ = 6
+GRQ_FIELDS = ("cost", "grad_inf", "lag_inf", "pg_inf", "compl", "min_lam")
 
 _lib = None
 
@@ -140,6 +144,10 @@ def lib():
     L.mpc_evaluate_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]
     L.mpc_evaluate_batch_device.restype = C.c_int
     L.mpc_evaluate_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+    L.mpc_gradient_batch.restype = C.c_int
+    L.mpc_gradient_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.mpc_gradient_batch_device.restype = C.c_int
+    L.mpc_gradient_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
     L.mpc_lookup.restype = C.c_int
     L.mpc_lookup.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.mpc_set_params.restype = C.c_int
@@ -421,6 +429,48 @@ class Solver:
         """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr(); 0 / None = NULL)."""
         _check(lib().mpc_evaluate_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, X_ptr, summary_ptr,
                                                terms_ptr, rows_ptr, C.c_void_p(stream)), "mpc_evaluate_batch_device")
+
+    def gradient_batch(self, x0, U, obs=None, n_obs=None, lam=None, costate=False):
+        """mpc_gradient_batch: the gradients of what evaluate_batch computes at ANY control sequences U [B,N,2] from
+        x0 [B,5] (obs, n_obs as in evaluate_batch).  lam [B,N,7+max_obs] or None: row weights in the layout of
+        evaluate_batch's rows (columns past n_obs are not read).  Returns dict(grad [B,N,2] = d cost / d U,
+        gx0 [B,5] = d cost / d x0, summary [B,6] (columns GRQ_FIELDS: cost, max |grad|, max |grad - jtl|, the
+        projected-gradient measure, max |lam g|, min lam)) and, with lam, jtl [B,N,2] = J' lam of the constraint
+        rows; with costate=True, costate [B,N,5] = p_1..p_N of the cost."""
+        p = self.params
+        N, mo = p.N, p.max_obs
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        if U is None:
+            raise ValueError("U is required: the control sequences to differentiate at")
+        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
+        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
+            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
+        if obs is not None and mo > 0:
+            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
+            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
+        else:
+            obs, n_obs = None, None
+        if lam is not None:
+            lam = np.ascontiguousarray(lam, np.float64).reshape(B, N, 7 + mo)
+        grad = np.empty((B, N, 2)); gx0 = np.empty((B, 5)); summary = np.empty((B, GR_NQ))
+        jtl = np.empty((B, N, 2)) if lam is not None else None
+        P = np.empty((B, N, 5)) if costate else None
+        _check(lib().mpc_gradient_batch(self.h, B, _p(x0), _p(obs), _pi(n_obs), _p(U), _p(lam), _p(grad), _p(jtl),
+                                        _p(gx0), _p(P), _p(summary)), "mpc_gradient_batch")
+        out = dict(grad=grad, gx0=gx0, summary=summary)
+        if lam is not None:
+            out["jtl"] = jtl
+        if costate:
+            out["costate"] = P
+        return out
+
+    def gradient_batch_device(self, B, x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, grad_ptr, jtl_ptr, gx0_ptr,
+                              costate_ptr, summary_ptr, stream=0):
+        """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr(); 0 / None = NULL)."""
+        _check(lib().mpc_gradient_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, grad_ptr,
+                                               jtl_ptr, gx0_ptr, costate_ptr, summary_ptr, C.c_void_p(stream)),
+               "mpc_gradient_batch_device")
 
     def closed_loop(self, x_init, fsm=None, max_steps=1000, s_stop=None, s_max=None):
         """Batched run_simulation (trajectory_tracking.py:377-443) on the device.
