@@ -57,7 +57,7 @@ def restate(traj, x0, U, obs, lam, dtype, m=None):
     """cost, d cost / d U [N,2], d cost / d x0 [5], J' lam [N,2] and the rows [N,7+M] of one instance, written from
     the reference's dynamics / predict / cost / constraints: every state carries its dense Jacobian in (U, x0)
     through the Euler steps; the table's values and slopes come from the trajectory arrays by np.searchsorted.
-    obs [M,2]; lam [N,7+M] in the layout of `rows`."""
+    obs [M,2]; lam [N,7+M] in the layout of `rows`.  Also X [N+1,5], the rollout."""
     T = dtype
     m = default_model() if m is None else m
     c = {k: T(v) for k, v in m.items()}
@@ -76,6 +76,7 @@ def restate(traj, x0, U, obs, lam, dtype, m=None):
         return slope * (s - sv[i - 1]) + tab[i - 1], slope
 
     x = np.asarray(x0).astype(T)
+    Xs = [x]
     J = np.zeros((5, nv), T)
     J[:, 2 * N:] = np.eye(5, dtype=T)
     cost, gc, jt = T(0), np.zeros(nv, T), np.zeros(nv, T)
@@ -92,6 +93,7 @@ def restate(traj, x0, U, obs, lam, dtype, m=None):
         Jd[4, 2 * k + 1] = 1
         x = x + c["dt"] * xd
         J = J + c["dt"] * Jd
+        Xs.append(x)
         s, d, o, _, v = x
         ref, sl = look(s)
         for w, a in ((c["w_d"], 1), (c["w_o"], 2), (c["w_v"], 4)):
@@ -115,7 +117,8 @@ def restate(traj, x0, U, obs, lam, dtype, m=None):
         cost = cost + c["w_u1"] * U[k, 0] ** 2 + c["w_u2"] * U[k, 1] ** 2
         gc[2 * k] += 2 * c["w_u1"] * U[k, 0]
         gc[2 * k + 1] += 2 * c["w_u2"] * U[k, 1]
-    return dict(cost=cost, grad=gc[:2 * N].reshape(N, 2), gx0=gc[2 * N:], jtl=jt[:2 * N].reshape(N, 2), rows=rows)
+    return dict(cost=cost, grad=gc[:2 * N].reshape(N, 2), gx0=gc[2 * N:], jtl=jt[:2 * N].reshape(N, 2), rows=rows,
+                X=np.array(Xs))
 
 
 def rel_err(a, ref):
@@ -244,15 +247,21 @@ def smooth_case(ti, Xpred, m):
     return bool((knot > KNOT_MARGIN).all() and (kink > KNOT_MARGIN).all())
 
 
-def check_finite_differences(env):
+def check_finite_differences(env, groups=None, m=None, what="", **kw):
     """(cost(U + hV) - cost(U - hV)) / 2h against grad . V, and per row family the same for one row of the evaluator's
-    `rows` against jtl . V with lam the unit vector of that row, for FD_DIRS random unit directions per case."""
-    m = default_model()
-    used, trajs, with8 = 0, set(), 0
+    `rows` against jtl . V with lam the unit vector of that row, for FD_DIRS random unit directions per case: on the
+    60 golden cases under the default parameters, or on the `groups` (in gradient_golden's format) recorded under the
+    model m, through contexts with the mpc_params fields kw.  Returns (cases used, cases, trajectories, cases used
+    with 8 obstacles); the default run asserts its own counts."""
+    default = groups is None
+    groups = gradient_golden(env) if default else groups
+    m = default_model() if m is None else m
+    used, total, trajs, with8 = 0, 0, set(), 0
     worst = 0.0
-    for key, cs, w, r, e in gradient_golden(env):
+    for key, cs, w, r, e in groups:
         ti, N, no = key
-        slv = solver(env, ti, N, no)
+        slv = solver(env, ti, N, no, **kw)
+        total += len(cs)
         ok = [b for b in range(len(cs)) if smooth_case(ti, e["Xpred"][b], m)]
         if not ok:
             continue
@@ -295,8 +304,10 @@ def check_finite_differences(env):
                     err = abs(drows[i, j, k, col] - want) / max(1.0, abs(want))
                     worst = max(worst, err)
                     assert err <= FD_REL, (key, b, j, fams[f][0], k, col, drows[i, j, k, col], want)
-    print(f"finite differences: {used} cases, worst error {worst:.3e} (bound {FD_REL:.1e})")
-    assert used >= 50 and trajs == {1, 2, 3} and with8 >= 1, (used, trajs, with8)
+    print(f"finite differences{what}: {used} of {total} cases, worst error {worst:.3e} (bound {FD_REL:.1e})")
+    if default:
+        assert used >= 50 and trajs == {1, 2, 3} and with8 >= 1, (used, trajs, with8)
+    return used, total, trajs, with8
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import gradient_cases as GC
+import gradient_params_cases as GP
 
 pytestmark = pytest.mark.gpu
 
@@ -145,3 +146,38 @@ def test_gradient_beside_a_solve_on_another_stream(env):
         assert GC.same(bufs[k].cpu().numpy(), serial_grad[k]), k
     for k in ("u0", "U", "Xpred", "status", "iters"):
         assert np.array_equal(out[k].cpu().numpy(), serial_solve[k]), k
+
+
+# ---------------------------------------------------------------------------------------------
+# away from the goldens (gradient_params_cases.py)
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", GP.PC.SET_NAMES)
+def test_params_restatement_pin(env, name):
+    GP.check_set_pin(env, name)
+
+
+@pytest.mark.parametrize("name", GP.SUMMARY_SETS)
+def test_params_summary_against_numpy(env, name):
+    GP.check_set_summary(env, name)
+
+
+@pytest.mark.parametrize("name", GP.FD_SETS)
+def test_params_finite_differences(env, name):
+    GP.check_set_finite_differences(env, name)
+
+
+@pytest.mark.parametrize("case", GP.shape_cases(), ids=GP.case_id)
+def test_shape_pin(env, case):
+    """Each lane group with two full wavefronts and one more instance, mixed n_obs, the 64-row slab and both OBS
+    instantiations against the longdouble yardstick; the host backend agrees with the device bit for bit."""
+    GP.check_shape_inputs(case)
+    GP.check_shape(env, case)
+
+
+@pytest.mark.parametrize("case", GP.STATIONARITY_CASES, ids=GP.stationarity_id)
+def test_stationarity(env, case):
+    GP.check_stationarity(env, case)
+
+
+def test_single_qp_is_not_stationary_printed(env):
+    GP.print_single_qp(env, GP.STATIONARITY_CASES[4])

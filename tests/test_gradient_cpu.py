@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import gradient_cases as GC
+import gradient_params_cases as GP
 
 
 @pytest.fixture(scope="module")
@@ -76,3 +77,73 @@ def test_shapes_summary(env, N, mo):
     slv = GC.solver(env, 1, N, mo)
     for what, w in GC.shape_runs(N, mo):
         GC.check_summary(slv, w, GC.gradient(slv, w), (N, mo, what))
+
+
+# ---------------------------------------------------------------------------------------------
+# away from the goldens (gradient_params_cases.py)
+# ---------------------------------------------------------------------------------------------
+def test_params_restatement_is_the_reference():
+    """Before the restatement judges the library under a parameter set, its longdouble run under model_of(mpc_params)
+    reproduces the reference's recorded cost and rows on the 72 records; its float64 run stays within the error the
+    bound was derived from."""
+    import oracle as O
+    assert GP.model_of(O.default_params()) == GC.default_model()
+    worst = {name: GP.check_yardstick_is_the_reference(name) for name in GP.PC.SET_NAMES}
+    print("restatement float64 vs longdouble per set:", {k: f"{v:.3e}" for k, v in worst.items()})
+    assert max(worst.values()) <= GP.PARAMS_F64_WORST
+
+
+@pytest.mark.parametrize("name", GP.PC.SET_NAMES)
+def test_params_restatement_pin(env, name):
+    GP.check_set_pin(env, name)
+
+
+@pytest.mark.parametrize("name", GP.SUMMARY_SETS)
+def test_params_summary_against_numpy(env, name):
+    GP.check_set_summary(env, name)
+
+
+@pytest.mark.parametrize("name", GP.FD_SETS)
+def test_params_finite_differences(env, name):
+    GP.check_set_finite_differences(env, name)
+
+
+def test_shape_yardstick_budget():
+    """Every generated batch holds what it is there for, and the float64 restatement stays within the recorded error
+    per horizon."""
+    for case in GP.shape_cases():
+        GP.check_shape_inputs(case)
+    assert {c[1] for c in GP.shape_cases()} == set(GP.SHAPE_N) == set(GP.SHAPE_F64_WORST)
+    for N in GP.SHAPE_N:
+        worst = GP.measure_shape_error(N)
+        print(f"restatement float64 vs longdouble, N = {N}: worst {worst:.3e}")
+        assert worst <= GP.SHAPE_F64_WORST[N], N
+
+
+@pytest.mark.parametrize("case", GP.shape_cases(), ids=GP.case_id)
+def test_shape_pin(env, case):
+    GP.check_shape_inputs(case)
+    GP.check_shape(env, case)
+
+
+def test_stationarity_oracle_figures(env):
+    """The oracle's SQP through the measure: the figures the stationarity bounds were taken from, re-measured."""
+    worst = {}
+    for case in GP.STATIONARITY_CASES:
+        t = GP.measure_stationarity(env, case, GP.oracle_answer(case))
+        GP.check_stationarity_population(case, t)
+        f = GP.worst_figures(t)
+        print(f"oracle {GP.stationarity_id(case)}: " + ", ".join(f"{n} {g:.3e}" for n, g in zip(GP.FIGURES, f)))
+        worst[case[2]] = tuple(max(a, b) for a, b in zip(worst.get(case[2], f), f))
+    for name, f in worst.items():
+        assert all(a <= b for a, b in zip(f, GP.STATIONARITY_ORACLE[name])), (name, f)
+        assert all(b <= 1.01 * a for a, b in zip(f, GP.STATIONARITY_ORACLE[name])), (name, f)
+
+
+@pytest.mark.parametrize("case", GP.STATIONARITY_CASES, ids=GP.stationarity_id)
+def test_stationarity(env, case):
+    GP.check_stationarity(env, case)
+
+
+def test_single_qp_is_not_stationary_printed(env):
+    GP.print_single_qp(env, GP.STATIONARITY_CASES[4])
