@@ -89,6 +89,10 @@ __host__ __device__ constexpr int stage_cache_xo(int N) { return 2 * N + 5 * (N 
 __host__ __device__ constexpr int stage_cache_lk(int N) { return (stage_cache_xo(N) + 6 * N + 1) & ~1; }
 __host__ __device__ constexpr int stage_cache_doubles(int N) { return stage_cache_lk(N) + 8 * (N + 1); }
 
+// GL, the lanes an instance takes: the smallest of 16, 32, 64 that holds its N + 1 stages (lane k = stage k), so a
+// wavefront serves WAVE / GL instances.  The solver, evaluator and gradient launches all group by it
+__host__ __device__ constexpr int lane_group(int N) { return N + 1 <= 16 ? 16 : (N + 1 <= 32 ? 32 : 64); }
+
 __host__ __device__ inline int lds_doubles(int N, bool acl, bool lite = false) {
     int NP = N + 1;
     int n = (acl ? N * 30 : 0) + N * A5S + (lite ? 0 : NP * 6) + NP * QRS + N * 2 + N * KRS + N * SIS + NP * QHS + N * 2 +

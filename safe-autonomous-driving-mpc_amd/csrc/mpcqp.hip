@@ -31,8 +31,8 @@
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 //   gradient_kernel.h      the batched gradients of that cost and of those rows (reverse sweeps)
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
-// and lookup entry points; the driver the closed-loop entries share is closed_loop_host.h) and, last, the comm
-// layer (comm.h).
+// and lookup entry points; the host entries stage their arrays through staging.h, the driver the closed-loop
+// entries share is closed_loop_host.h) and, last, the comm layer (comm.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,11 +41,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mpcqp.h"
+#include "staging.h"
 #include "host_table.h"
 #include "cpu_backend.h"
 #include "solve_kernel.h"
@@ -99,17 +102,7 @@ struct mpc_ctx {
     mpc_params p;
     DevTable tab;
     double* table_buf;
-    // host-API staging buffers
-    size_t cap_B;
-    int cap_N, cap_obs;
-    double *x0, *obs, *ub, *u0, *U, *X;
-    int *nobs, *status, *iters;
-    double *ls, *lst, *lct;
-    size_t cap_lookup;
-    // mpc_evaluate_batch's output staging (summary, terms, rows) and mpc_gradient_batch's staging (lam and its
-    // outputs), grown on demand
-    double* ev;
-    size_t cap_ev;      // doubles
+    staging::Arena arena;       // what the host entries stage their arrays through (staging.h)
     hipStream_t stream;
     // work list of the two-phase launch: wl[0], wl[1] = counts of the eager calls (alternating), wl[2] = count
     // of a call captured into a graph, wl[3..cap_wl + 2] = deferred instance ids
@@ -292,14 +285,6 @@ extern "C" int mpc_get_params(const mpc_ctx* c, mpc_params* p) {
     return MPC_SUCCESS;
 }
 
-static void free_staging(mpc_ctx* c) {
-    hipFree(c->x0); hipFree(c->obs); hipFree(c->ub); hipFree(c->u0); hipFree(c->U); hipFree(c->X);
-    hipFree(c->nobs); hipFree(c->status); hipFree(c->iters);
-    c->x0 = c->obs = c->ub = c->u0 = c->U = c->X = nullptr;
-    c->nobs = c->status = c->iters = nullptr;
-    c->cap_B = 0;
-}
-
 extern "C" void mpc_destroy(mpc_ctx* c) {
     if (!c) return;
     if (c->cpu) {
@@ -309,9 +294,7 @@ extern "C" void mpc_destroy(mpc_ctx* c) {
     }
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    free_staging(c);
-    hipFree(c->ls); hipFree(c->lst); hipFree(c->lct);
-    hipFree(c->ev);
+    c->arena.release();
     if (c->wl) hipEventDestroy(c->wl_done);
     hipFree(c->wl);
     hipFree(c->stc);
@@ -320,6 +303,19 @@ extern "C" void mpc_destroy(mpc_ctx* c) {
     std::free(c);
 }
 
+// The runtime-horizon launches' choice of kernel: f(GL, obs) with the lane group (lane_group) and whether obstacle
+// rows exist as std::integral_constants, so f names the instantiation <decltype(gl)::value, decltype(ob)::value>
+template <typename F>
+static void for_gl_obs(int GL, bool obs, F&& f) {
+    auto with_gl = [&](auto gl) { obs ? f(gl, std::true_type{}) : f(gl, std::false_type{}); };
+    if (GL == 16) with_gl(std::integral_constant<int, 16>{});
+    else if (GL == 32) with_gl(std::integral_constant<int, 32>{});
+    else with_gl(std::integral_constant<int, 64>{});
+}
+
+// one lane group per instance, WAVE / GL instances per wavefront
+static dim3 group_grid(int B, int GL) { return dim3((B + WAVE / GL - 1) / (WAVE / GL)); }
+
 // launch of the solver kernel for an already validated parameter set
 #define MPC_STAGE_CACHE_CAP ((size_t)1 << 27)
 static int launch_solve(mpc_ctx* c, const KParams& kp, int B, const double* x0, const double* obs, const int* n_obs,
@@ -327,14 +323,14 @@ static int launch_solve(mpc_ctx* c, const KParams& kp, int B, const double* x0, 
                         hipStream_t st) {
     // G = 64 / GL instances per wavefront: the smallest lane group holding the N + 1 stages
     const int* nob = obs ? n_obs : nullptr;
-    const int GL = kp.N + 1 <= 16 ? 16 : (kp.N + 1 <= 32 ? 32 : 64);
+    const int GL = lane_group(kp.N);
     const int G = WAVE / GL;
     // horizon of the specialised kernel that serves N (0: the runtime-horizon kernels)
     const int ntv = kp.N == 20 || kp.N == 30 || kp.N == 40 ? kp.N : 0;
     const size_t lds_wave = sizeof(double) * (size_t)lds_doubles(kp.N, acl_on(GL, ntv)) * G;
     if (lds_wave > 160 * 1024) return fail(MPC_E_ARG, "horizon too long for LDS");
     const size_t lds_lite = sizeof(double) * (size_t)lds_doubles(kp.N, false, true) * G;   // MODE_XO
-    const dim3 grid((B + G - 1) / G);
+    const dim3 grid = group_grid(B, GL);
     // Two-phase launch (MODE_XO then MODE_IPM) for single-QP solves with the crossover on; the work
     // list lives in the context (one list per context: a context is not re-entrant, include/mpcqp.h).
     // With one instance per wavefront (G = 1, N > 31) nothing is stranded behind a slower partner, and
@@ -396,9 +392,7 @@ static int launch_solve(mpc_ctx* c, const KParams& kp, int B, const double* x0, 
         if (ntv == 20) { if (with_obs) MPC_LAUNCH(32, true, MODEV, 20); else MPC_LAUNCH(32, false, MODEV, 20); } \
         else if (ntv == 30) { if (with_obs) MPC_LAUNCH(32, true, MODEV, 30); else MPC_LAUNCH(32, false, MODEV, 30); } \
         else if (ntv == 40) { if (with_obs) MPC_LAUNCH(64, true, MODEV, 40); else MPC_LAUNCH(64, false, MODEV, 40); } \
-        else if (GL == 16) { if (with_obs) MPC_LAUNCH(16, true, MODEV, 0); else MPC_LAUNCH(16, false, MODEV, 0); } \
-        else if (GL == 32) { if (with_obs) MPC_LAUNCH(32, true, MODEV, 0); else MPC_LAUNCH(32, false, MODEV, 0); } \
-        else { if (with_obs) MPC_LAUNCH(64, true, MODEV, 0); else MPC_LAUNCH(64, false, MODEV, 0); } \
+        else for_gl_obs(GL, with_obs, [&](auto gl, auto ob) { MPC_LAUNCH(decltype(gl)::value, decltype(ob)::value, MODEV, 0); }); \
     } while (0)
     const bool with_obs = obs != nullptr && kp.max_obs > 0;
     if (split) {
@@ -437,20 +431,49 @@ static int launch_solve(mpc_ctx* c, const KParams& kp, int B, const double* x0, 
     return MPC_SUCCESS;
 }
 
-extern "C" int mpc_solve_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
-                                      const double* ubar, double* u0, double* U, double* Xpred, int* status,
-                                      int* iters, void* stream) {
+// ------------------------------------------------------------------------------------------
+// the batch entries.  Each host / device pair shares one *_args: the checks that hold for both, B == 0 included (it
+// passes, and the entry returns success on it).  What only the device side can be asked is device_args: n_obs without
+// obs (a host entry stages n_obs only together with obs) and the alignment of raw addresses (staging.h aligns).
+// ------------------------------------------------------------------------------------------
+// the checks of all three pairs in the order they fire; u_missing: the refusal of a NULL U that the entry needs
+static int batch_args(mpc_ctx* c, int B, const double* x0, const double* obs, const char* u_missing = nullptr,
+                      bool jtl_without_lam = false) {
     if (!c) return fail(MPC_E_ARG, "ctx is NULL");
     if (B < 0) return fail(MPC_E_ARG, "B < 0");
     if (B == 0) return MPC_SUCCESS;
     if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
-    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
+    if (u_missing) return fail(MPC_E_ARG, u_missing);
     if (obs && c->p.max_obs == 0)
         return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    if (((uintptr_t)u0 | (uintptr_t)U | (uintptr_t)x0 | (uintptr_t)Xpred | (uintptr_t)obs | (uintptr_t)ubar) & 7)
-        return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    if (jtl_without_lam) return fail(MPC_E_ARG, "jtl asked for but lam is NULL (J' lam needs the row weights)");
+    return check_params(&c->p);
+}
+
+static int solve_args(mpc_ctx* c, int B, const double* x0, const double* obs) { return batch_args(c, B, x0, obs); }
+static int evaluate_args(mpc_ctx* c, int B, const double* x0, const double* obs, const double* U) {
+    return batch_args(c, B, x0, obs, U ? nullptr : "U is NULL (the evaluator needs the control sequence to evaluate)");
+}
+
+static int gradient_args(mpc_ctx* c, int B, const double* x0, const double* obs, const double* U, const double* lam,
+                         const double* jtl) {
+    return batch_args(c, B, x0, obs, U ? nullptr : "U is NULL (the gradient needs the control sequence to differentiate at)",
+                      jtl && !lam);
+}
+
+static int device_args(const mpc_ctx* c, const double* obs, const int* n_obs, std::initializer_list<const double*> arrays) {
+    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
+    for (const double* a : arrays)
+        if ((uintptr_t)a & 7) return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_solve_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                      const double* ubar, double* u0, double* U, double* Xpred, int* status,
+                                      int* iters, void* stream) {
+    int rc = solve_args(c, B, x0, obs);
+    if (rc || B == 0) return rc;
+    if ((rc = device_args(c, obs, n_obs, {u0, U, x0, Xpred, obs, ubar}))) return rc;
     if (c->cpu) {
         // host context: the pointers are host memory and the call is synchronous (stream ignored)
         return host_call([&] { c->cpu->solve_batch(c->p, B, x0, obs, n_obs, ubar, u0, U, Xpred, status, iters); });
@@ -461,68 +484,42 @@ extern "C" int mpc_solve_batch_device(mpc_ctx* c, int B, const double* x0, const
     return launch_solve(c, kp, B, x0, obs, n_obs, ubar, u0, U, Xpred, status, iters, (hipStream_t)stream);
 }
 
-template <typename T>
-static int grow(T** ptr, size_t n) {
-    hipFree(*ptr);
-    *ptr = nullptr;
-    if (n == 0) return 0;
-    return hipMalloc(ptr, n * sizeof(T)) == hipSuccess ? 0 : -1;
-}
-
-// the host entries' staging buffers for a batch of B instances, horizon N and slab width mo (grow only)
-static int ensure_staging(mpc_ctx* c, int B, int N, int mo) {
-    if ((size_t)B > c->cap_B || N > c->cap_N || mo > c->cap_obs) {
-        size_t nb = (size_t)B > c->cap_B ? (size_t)B : c->cap_B;
-        int nn = N > c->cap_N ? N : c->cap_N;
-        int no = mo > c->cap_obs ? mo : c->cap_obs;
-        free_staging(c);
-        if (grow(&c->x0, nb * 5) || grow(&c->obs, nb * (no > 0 ? no : 1) * 2) || grow(&c->ub, nb * 2 * nn) ||
-            grow(&c->u0, nb * 2) || grow(&c->U, nb * 2 * nn) || grow(&c->X, nb * 5 * (nn + 1)) ||
-            grow(&c->nobs, nb) || grow(&c->status, nb) || grow(&c->iters, nb))
-            return fail(MPC_E_ALLOC, "hipMalloc staging");
-        c->cap_B = nb;
-        c->cap_N = nn;
-        c->cap_obs = no;
-    }
+// a host entry's round trip: its arrays bound to the context's arena, the uploads, its device twin on the device
+// arrays and the downloads, all on the context's stream, then one synchronisation
+template <typename Bind, typename Call>
+static int staged_call(mpc_ctx* c, const char* no_memory, Bind&& bindings, Call&& device_entry) {
+    staging::Staging S(c->arena);
+    if (!S.bind([&] { bindings(S); })) return fail(MPC_E_ALLOC, no_memory);
+    HIPCHK(S.upload(c->stream), MPC_E_DEVICE);
+    if (int rc = device_entry()) return rc;
+    HIPCHK(S.fetch(c->stream), MPC_E_DEVICE);
+    HIPCHK(S.sync(c->stream), MPC_E_DEVICE);
     return MPC_SUCCESS;
 }
 
 extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                const double* ubar, double* u0, double* U, double* Xpred, int* status, int* iters) {
-    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(MPC_E_ARG, "B < 0");
-    if (B == 0) return MPC_SUCCESS;
-    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    const int N = c->p.N, mo = c->p.max_obs;
-    if (obs && mo == 0) return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->solve_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, ubar, u0, U, Xpred, status, iters);
-        });
+    int rc = solve_args(c, B, x0, obs);
+    if (rc || B == 0) return rc;
+    if (c->cpu) return host_call([&] { c->cpu->solve_batch(c->p, B, x0, obs, n_obs, ubar, u0, U, Xpred, status, iters); });
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    rc = ensure_staging(c, B, N, mo);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    const bool use_obs = mo > 0 && obs;
-    if (use_obs) {
-        HIPCHK(hipMemcpyAsync(c->obs, obs, sizeof(double) * 2 * mo * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-        if (n_obs) HIPCHK(hipMemcpyAsync(c->nobs, n_obs, sizeof(int) * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    }
-    if (ubar) HIPCHK(hipMemcpyAsync(c->ub, ubar, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    rc = mpc_solve_batch_device(c, B, c->x0, use_obs ? c->obs : nullptr, use_obs && n_obs ? c->nobs : nullptr,
-                                ubar ? c->ub : nullptr, c->u0, c->U, c->X, c->status, c->iters, (void*)s);
-    if (rc) return rc;
-    if (u0) HIPCHK(hipMemcpyAsync(u0, c->u0, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (U) HIPCHK(hipMemcpyAsync(U, c->U, sizeof(double) * 2 * N * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (Xpred)
-        HIPCHK(hipMemcpyAsync(Xpred, c->X, sizeof(double) * 5 * (N + 1) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (status) HIPCHK(hipMemcpyAsync(status, c->status, sizeof(int) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (iters) HIPCHK(hipMemcpyAsync(iters, c->iters, sizeof(int) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
-    return MPC_SUCCESS;
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+    double *d_x0, *d_obs, *d_ub, *d_u0, *d_U, *d_X;
+    int *d_nobs, *d_status, *d_iters;
+    // n_obs travels only with obs; the kernel writes all five outputs, asked for or not
+    return staged_call(c, "hipMalloc staging", [&](staging::Staging& S) {
+        d_x0 = S.in(x0, nb * 5);
+        d_obs = S.in(obs, nb * mo * 2);
+        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
+        d_ub = S.in(ubar, nb * N * 2);
+        d_u0 = S.out_or_scratch(u0, nb * 2);
+        d_U = S.out_or_scratch(U, nb * N * 2);
+        d_X = S.out_or_scratch(Xpred, nb * (N + 1) * 5);
+        d_status = S.out_or_scratch(status, nb);
+        d_iters = S.out_or_scratch(iters, nb);
+    }, [&] {
+        return mpc_solve_batch_device(c, B, d_x0, d_obs, d_nobs, d_ub, d_u0, d_U, d_X, d_status, d_iters, (void*)c->stream);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -531,19 +528,9 @@ extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double
 extern "C" int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                          const double* U, double* Xpred, double* summary, double* terms,
                                          double* rows, void* stream) {
-    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(MPC_E_ARG, "B < 0");
-    if (B == 0) return MPC_SUCCESS;
-    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
-    if (!U) return fail(MPC_E_ARG, "U is NULL (the evaluator needs the control sequence to evaluate)");
-    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
-    if (obs && c->p.max_obs == 0)
-        return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    if (((uintptr_t)x0 | (uintptr_t)obs | (uintptr_t)U | (uintptr_t)Xpred | (uintptr_t)summary | (uintptr_t)terms |
-         (uintptr_t)rows) & 7)
-        return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    int rc = evaluate_args(c, B, x0, obs, U);
+    if (rc || B == 0) return rc;
+    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, Xpred, summary, terms, rows}))) return rc;
     if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
     if (c->cpu)
         return host_call([&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); });
@@ -551,93 +538,50 @@ extern "C" int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, co
     const int rw = 7 + c->p.max_obs;       // the row width keeps the context's slab width without obstacles too
     if (!obs) kp.max_obs = 0;
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const int GL = kp.N + 1 <= 16 ? 16 : (kp.N + 1 <= 32 ? 32 : 64);     // launch_solve's rule
-    const dim3 grid((B + WAVE / GL - 1) / (WAVE / GL));
-    hipStream_t st = (hipStream_t)stream;
-#define MPC_EV_LAUNCH(GLV, OBSV)                                                                              \
-    hipLaunchKernelGGL((mpc_evaluate_kernel<GLV, OBSV>), grid, dim3(WAVE), 0, st, c->tab, kp, B, rw, x0, obs, \
-                       obs ? n_obs : nullptr, U, Xpred, summary, terms, rows)
-    if (GL == 16) { if (obs) MPC_EV_LAUNCH(16, true); else MPC_EV_LAUNCH(16, false); }
-    else if (GL == 32) { if (obs) MPC_EV_LAUNCH(32, true); else MPC_EV_LAUNCH(32, false); }
-    else { if (obs) MPC_EV_LAUNCH(64, true); else MPC_EV_LAUNCH(64, false); }
-#undef MPC_EV_LAUNCH
+    const int GL = lane_group(kp.N);
+    for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
+        hipLaunchKernelGGL((mpc_evaluate_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL), dim3(WAVE), 0,
+                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, Xpred, summary, terms,
+                           rows);
+    });
     HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
     return MPC_SUCCESS;
 }
 
 extern "C" int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                   const double* U, double* Xpred, double* summary, double* terms, double* rows) {
-    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(MPC_E_ARG, "B < 0");
-    if (B == 0) return MPC_SUCCESS;
-    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
-    if (!U) return fail(MPC_E_ARG, "U is NULL (the evaluator needs the control sequence to evaluate)");
-    int rc = check_params(&c->p);
-    if (rc) return rc;
-    const int N = c->p.N, mo = c->p.max_obs, rw = 7 + mo;
-    if (obs && mo == 0) return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
+    int rc = evaluate_args(c, B, x0, obs, U);
+    if (rc || B == 0) return rc;
     if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
     if (c->cpu)
-        return host_call([&] {
-            c->cpu->evaluate_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, U, Xpred, summary, terms, rows);
-        });
+        return host_call([&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); });
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    rc = ensure_staging(c, B, N, mo);
-    if (rc) return rc;
-    const size_t n_sum = (size_t)B * MPC_EV_NQ, n_terms = (size_t)B * 5, n_rows = (size_t)B * N * rw;
-    if (n_sum + n_terms + n_rows > c->cap_ev) {
-        c->cap_ev = 0;
-        if (grow(&c->ev, n_sum + n_terms + n_rows)) return fail(MPC_E_ALLOC, "hipMalloc evaluator staging");
-        c->cap_ev = n_sum + n_terms + n_rows;
-    }
-    double *d_sum = c->ev, *d_terms = c->ev + n_sum, *d_rows = c->ev + n_sum + n_terms;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    const bool use_obs = obs != nullptr;
-    if (use_obs) {
-        HIPCHK(hipMemcpyAsync(c->obs, obs, sizeof(double) * 2 * mo * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-        if (n_obs) HIPCHK(hipMemcpyAsync(c->nobs, n_obs, sizeof(int) * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    }
-    HIPCHK(hipMemcpyAsync(c->ub, U, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    rc = mpc_evaluate_batch_device(c, B, c->x0, use_obs ? c->obs : nullptr, use_obs && n_obs ? c->nobs : nullptr,
-                                   c->ub, Xpred ? c->X : nullptr, summary ? d_sum : nullptr,
-                                   terms ? d_terms : nullptr, rows ? d_rows : nullptr, (void*)s);
-    if (rc) return rc;
-    if (Xpred)
-        HIPCHK(hipMemcpyAsync(Xpred, c->X, sizeof(double) * 5 * (N + 1) * B, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, sizeof(double) * n_sum, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (terms) HIPCHK(hipMemcpyAsync(terms, d_terms, sizeof(double) * n_terms, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (rows) HIPCHK(hipMemcpyAsync(rows, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
-    return MPC_SUCCESS;
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+    double *d_x0, *d_obs, *d_U, *d_X, *d_sum, *d_terms, *d_rows;
+    int* d_nobs;
+    return staged_call(c, "hipMalloc evaluator staging", [&](staging::Staging& S) {
+        d_x0 = S.in(x0, nb * 5);
+        d_obs = S.in(obs, nb * mo * 2);
+        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
+        d_U = S.in(U, nb * N * 2);
+        d_X = S.out(Xpred, nb * (N + 1) * 5);
+        d_sum = S.out(summary, nb * MPC_EV_NQ);
+        d_terms = S.out(terms, nb * 5);
+        d_rows = S.out(rows, nb * N * (7 + mo));
+    }, [&] {
+        return mpc_evaluate_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_X, d_sum, d_terms, d_rows, (void*)c->stream);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
 // batched gradients (gradient_kernel.h)
 // ------------------------------------------------------------------------------------------
-// the argument checks both entries share (after ctx, B and the B == 0 return)
-static int gradient_args(mpc_ctx* c, const double* x0, const double* obs, const double* U, const double* lam,
-                         const double* jtl) {
-    if (!x0) return fail(MPC_E_ARG, "x0 is NULL");
-    if (!U) return fail(MPC_E_ARG, "U is NULL (the gradient needs the control sequence to differentiate at)");
-    if (obs && c->p.max_obs == 0)
-        return fail(MPC_E_ARG, "obs given but params.max_obs == 0 (the obstacles would be ignored)");
-    if (jtl && !lam) return fail(MPC_E_ARG, "jtl asked for but lam is NULL (J' lam needs the row weights)");
-    return check_params(&c->p);
-}
-
 extern "C" int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                          const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                                          double* costate, double* summary, void* stream) {
-    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(MPC_E_ARG, "B < 0");
-    if (B == 0) return MPC_SUCCESS;
-    if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
-    int rc = gradient_args(c, x0, obs, U, lam, jtl);
-    if (rc) return rc;
-    if (((uintptr_t)x0 | (uintptr_t)obs | (uintptr_t)U | (uintptr_t)lam | (uintptr_t)grad | (uintptr_t)jtl |
-         (uintptr_t)gx0 | (uintptr_t)costate | (uintptr_t)summary) & 7)
-        return fail(MPC_E_ARG, "double arrays must be 8-byte aligned");
+    int rc = gradient_args(c, B, x0, obs, U, lam, jtl);
+    if (rc || B == 0) return rc;
+    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, grad, jtl, gx0, costate, summary}))) return rc;
     if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
     if (c->cpu)
         return host_call([&] {
@@ -647,16 +591,12 @@ extern "C" int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, co
     const int rw = 7 + c->p.max_obs;       // lam keeps the context's slab width without obstacles too
     if (!obs) kp.max_obs = 0;
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const int GL = kp.N + 1 <= 16 ? 16 : (kp.N + 1 <= 32 ? 32 : 64);     // launch_solve's rule
-    const dim3 grid((B + WAVE / GL - 1) / (WAVE / GL));
-    hipStream_t st = (hipStream_t)stream;
-#define MPC_GR_LAUNCH(GLV, OBSV)                                                                              \
-    hipLaunchKernelGGL((mpc_gradient_kernel<GLV, OBSV>), grid, dim3(WAVE), 0, st, c->tab, kp, B, rw, x0, obs, \
-                       obs ? n_obs : nullptr, U, lam, grad, jtl, gx0, costate, summary)
-    if (GL == 16) { if (obs) MPC_GR_LAUNCH(16, true); else MPC_GR_LAUNCH(16, false); }
-    else if (GL == 32) { if (obs) MPC_GR_LAUNCH(32, true); else MPC_GR_LAUNCH(32, false); }
-    else { if (obs) MPC_GR_LAUNCH(64, true); else MPC_GR_LAUNCH(64, false); }
-#undef MPC_GR_LAUNCH
+    const int GL = lane_group(kp.N);
+    for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
+        hipLaunchKernelGGL((mpc_gradient_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL), dim3(WAVE), 0,
+                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, lam, grad, jtl, gx0,
+                           costate, summary);
+    });
     HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
     return MPC_SUCCESS;
 }
@@ -664,53 +604,32 @@ extern "C" int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, co
 extern "C" int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                   const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                                   double* costate, double* summary) {
-    if (!c) return fail(MPC_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(MPC_E_ARG, "B < 0");
-    if (B == 0) return MPC_SUCCESS;
-    int rc = gradient_args(c, x0, obs, U, lam, jtl);
-    if (rc) return rc;
-    const int N = c->p.N, mo = c->p.max_obs, rw = 7 + mo;
+    int rc = gradient_args(c, B, x0, obs, U, lam, jtl);
+    if (rc || B == 0) return rc;
     if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
     if (c->cpu)
         return host_call([&] {
-            c->cpu->gradient_batch(c->p, B, x0, mo > 0 ? obs : nullptr, n_obs, U, lam, grad, jtl, gx0, costate,
-                                   summary);
+            c->cpu->gradient_batch(c->p, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary);
         });
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    rc = ensure_staging(c, B, N, mo);
-    if (rc) return rc;
-    const size_t n_lam = lam ? (size_t)B * N * rw : 0, n_u = (size_t)B * N * 2, n_x0 = (size_t)B * 5,
-                 n_cos = (size_t)B * N * 5, n_sum = (size_t)B * MPC_GR_NQ;
-    const size_t need = n_lam + 2 * n_u + n_x0 + n_cos + n_sum;
-    if (need > c->cap_ev) {
-        c->cap_ev = 0;
-        if (grow(&c->ev, need)) return fail(MPC_E_ALLOC, "hipMalloc gradient staging");
-        c->cap_ev = need;
-    }
-    double *d_lam = c->ev, *d_grad = d_lam + n_lam, *d_jtl = d_grad + n_u, *d_gx0 = d_jtl + n_u,
-           *d_cos = d_gx0 + n_x0, *d_sum = d_cos + n_cos;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    const bool use_obs = obs != nullptr;
-    if (use_obs) {
-        HIPCHK(hipMemcpyAsync(c->obs, obs, sizeof(double) * 2 * mo * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-        if (n_obs) HIPCHK(hipMemcpyAsync(c->nobs, n_obs, sizeof(int) * B, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    }
-    HIPCHK(hipMemcpyAsync(c->ub, U, sizeof(double) * n_u, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    if (lam) HIPCHK(hipMemcpyAsync(d_lam, lam, sizeof(double) * n_lam, hipMemcpyHostToDevice, s), MPC_E_DEVICE);
-    rc = mpc_gradient_batch_device(c, B, c->x0, use_obs ? c->obs : nullptr, use_obs && n_obs ? c->nobs : nullptr,
-                                   c->ub, lam ? d_lam : nullptr, grad ? d_grad : nullptr, jtl ? d_jtl : nullptr,
-                                   gx0 ? d_gx0 : nullptr, costate ? d_cos : nullptr, summary ? d_sum : nullptr,
-                                   (void*)s);
-    if (rc) return rc;
-    if (grad) HIPCHK(hipMemcpyAsync(grad, d_grad, sizeof(double) * n_u, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (jtl) HIPCHK(hipMemcpyAsync(jtl, d_jtl, sizeof(double) * n_u, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (gx0) HIPCHK(hipMemcpyAsync(gx0, d_gx0, sizeof(double) * n_x0, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (costate)
-        HIPCHK(hipMemcpyAsync(costate, d_cos, sizeof(double) * n_cos, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, sizeof(double) * n_sum, hipMemcpyDeviceToHost, s), MPC_E_DEVICE);
-    HIPCHK(hipStreamSynchronize(s), MPC_E_DEVICE);
-    return MPC_SUCCESS;
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+    double *d_x0, *d_obs, *d_U, *d_lam, *d_grad, *d_jtl, *d_gx0, *d_cos, *d_sum;
+    int* d_nobs;
+    return staged_call(c, "hipMalloc gradient staging", [&](staging::Staging& S) {
+        d_x0 = S.in(x0, nb * 5);
+        d_obs = S.in(obs, nb * mo * 2);
+        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
+        d_U = S.in(U, nb * N * 2);
+        d_lam = S.in(lam, nb * N * (7 + mo));
+        d_grad = S.out(grad, nb * N * 2);
+        d_jtl = S.out(jtl, nb * N * 2);
+        d_gx0 = S.out(gx0, nb * 5);
+        d_cos = S.out(costate, nb * N * 5);
+        d_sum = S.out(summary, nb * MPC_GR_NQ);
+    }, [&] {
+        return mpc_gradient_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_lam, d_grad, d_jtl, d_gx0, d_cos, d_sum,
+                                         (void*)c->stream);
+    });
 }
 
 extern "C" void mpc_default_fsm(mpc_fsm* f) {
@@ -1227,25 +1146,28 @@ extern "C" int mpc_noise_draw(mpc_ctx* c, unsigned long long seed, int n, const 
     }
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
     const size_t nn = (size_t)n;
-    DevBufs mem;
-    long long* d_ego = mem.alloc<long long>(nn);
-    int* d_step = mem.alloc<int>(nn);
-    int* d_ch = mem.alloc<int>(nn);
-    unsigned* d_w = words ? mem.alloc<unsigned>(nn * 4) : nullptr;
-    double* d_z = z ? mem.alloc<double>(nn) : nullptr;
-    if (!mem.ok()) return fail(MPC_E_ALLOC, "hipMalloc noise-draw buffers");
+    staging::Staging S(c->arena);
+    long long* d_ego;
+    int *d_step, *d_ch;
+    unsigned* d_w;
+    double* d_z;
+    const bool bound = S.bind([&] {
+        d_ego = S.in(ego, nn);
+        d_step = S.in(step, nn);
+        d_ch = S.in(channel, nn);
+        d_w = S.out(words, nn * 4);
+        d_z = S.out(z, nn);
+    });
+    if (!bound) return fail(MPC_E_ALLOC, "hipMalloc noise-draw buffers");
     hipStream_t st = c->stream;
-    bool ok = hipMemcpyAsync(d_ego, ego, nn * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok = ok && hipMemcpyAsync(d_step, step, nn * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok = ok && hipMemcpyAsync(d_ch, channel, nn * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    bool ok = S.upload(st) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(nz_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (unsigned)(seed & 0xffffffffull),
                            (unsigned)(seed >> 32), d_ego, d_step, d_ch, d_w, d_z);
         ok = hipGetLastError() == hipSuccess;
     }
-    if (words) ok = ok && hipMemcpyAsync(words, d_w, nn * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (z) ok = ok && hipMemcpyAsync(z, d_z, nn * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    ok = ok && S.fetch(st) == hipSuccess;
+    ok = S.sync(st) == hipSuccess && ok;
     return ok ? MPC_SUCCESS : fail(MPC_E_DEVICE, "noise draw");
 }
 
@@ -1258,22 +1180,24 @@ extern "C" int mpc_global_pose(mpc_ctx* c, int n, const double* s, const double*
         return MPC_SUCCESS;
     }
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    double* buf = nullptr;
-    HIPCHK(hipMalloc(&buf, sizeof(double) * 5 * (size_t)n), MPC_E_ALLOC);
+    staging::Staging S(c->arena);
+    double *d_s, *d_d, *d_out;
+    const bool bound = S.bind([&] {
+        d_s = S.in(s, (size_t)n);
+        d_d = S.in(d, (size_t)n);
+        d_out = S.out(out, 3 * (size_t)n);
+    });
+    if (!bound) return fail(MPC_E_ALLOC, "hipMalloc global pose staging");
     hipStream_t st = c->stream;
     int rc = MPC_SUCCESS;
-    if (hipMemcpyAsync(buf, s, sizeof(double) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(buf + n, d, sizeof(double) * n, hipMemcpyHostToDevice, st) != hipSuccess) {
+    if (S.upload(st) != hipSuccess) {
         rc = fail(MPC_E_DEVICE, "hipMemcpy global pose inputs");
     } else {
-        hipLaunchKernelGGL(mpc_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c->tab, n, buf, buf + n, buf + 2 * n);
+        hipLaunchKernelGGL(mpc_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c->tab, n, d_s, d_d, d_out);
         if (hipGetLastError() != hipSuccess) rc = fail(MPC_E_LAUNCH, "global pose kernel");
-        else if (hipMemcpyAsync(out, buf + 2 * n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                 hipStreamSynchronize(st) != hipSuccess)
-            rc = fail(MPC_E_DEVICE, "hipMemcpy global pose");
+        else if (S.fetch(st) != hipSuccess || S.sync(st) != hipSuccess) rc = fail(MPC_E_DEVICE, "hipMemcpy global pose");
     }
-    hipStreamSynchronize(st);
-    hipFree(buf);
+    if (rc) S.sync(st);     // the caller's arrays are free again when the entry returns
     return rc;
 }
 
@@ -1324,21 +1248,17 @@ extern "C" int mpc_lookup(mpc_ctx* c, int n, const double* s, double* out_state,
         return MPC_SUCCESS;
     }
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    if ((size_t)n > c->cap_lookup) {
-        if (grow(&c->ls, n) || grow(&c->lst, (size_t)n * 5) || grow(&c->lct, (size_t)n * 2))
-            return fail(MPC_E_ALLOC, "hipMalloc lookup");
-        c->cap_lookup = n;
-    }
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(c->ls, s, sizeof(double) * n, hipMemcpyHostToDevice, st), MPC_E_DEVICE);
-    hipLaunchKernelGGL(mpc_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c->tab, n, c->ls, c->lst, c->lct);
-    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
-    if (out_state)
-        HIPCHK(hipMemcpyAsync(out_state, c->lst, sizeof(double) * 5 * n, hipMemcpyDeviceToHost, st), MPC_E_DEVICE);
-    if (out_control)
-        HIPCHK(hipMemcpyAsync(out_control, c->lct, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st), MPC_E_DEVICE);
-    HIPCHK(hipStreamSynchronize(st), MPC_E_DEVICE);
-    return MPC_SUCCESS;
+    double *d_s, *d_state, *d_control;
+    return staged_call(c, "hipMalloc lookup", [&](staging::Staging& S) {
+        d_s = S.in(s, (size_t)n);
+        d_state = S.out_or_scratch(out_state, 5 * (size_t)n);     // the kernel writes both
+        d_control = S.out_or_scratch(out_control, 2 * (size_t)n);
+    }, [&] {
+        hipLaunchKernelGGL(mpc_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->tab, n, d_s, d_state,
+                           d_control);
+        HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+        return (int)MPC_SUCCESS;
+    });
 }
 
 // multi-GPU: the ego-shard communicator (RCCL gather behind the C ABI)

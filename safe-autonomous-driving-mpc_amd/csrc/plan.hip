@@ -24,14 +24,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
-
 #include "../../include/mpcplan.h"
 #include "../../include/mpcplan_evaluate.h"
+#include "staging.h"
 #include "plan_kernel.h"
 #include "plan_evaluate_kernel.h"
 #include "plan_host.h"
@@ -58,9 +59,7 @@ struct plan_ctx {
     DevRoute R;
     double* d_route;          // s | cx | cy | vmax
     size_t lds_max;           // the device's LDS per workgroup
-    // host-entry staging
-    void* io;
-    size_t io_bytes;
+    staging::Arena arena;     // what the host entries stage their arrays through (staging.h)
     // longest-first dispatch (plan_order_*_kernel): a small pool of buffers (2 * ORDER_BUCKETS counters, then
     // bucket[cap], order[cap]), each remembering the stream it last served and an event recorded after its last
     // chunk kernel.  A call prefers its stream's buffer, else a new one (up to ORDER_POOL), else the least
@@ -125,6 +124,54 @@ static int check_params(const plan_params* p) {
     if (!(p->defect_sign == 1.0 || p->defect_sign == -1.0)) return fail(PLAN_E_ARG, "defect_sign must be +1 or -1");
     if (!(p->u_min[0] < p->u_max[0]) || !(p->u_min[1] < p->u_max[1]) || !(p->k_min < p->k_max))
         return fail(PLAN_E_ARG, "bounds must satisfy min < max");
+    return PLAN_SUCCESS;
+}
+
+// The checks each host / device pair of entries shares; B == 0 passes (the entry returns success on it).  A device
+// entry refuses a host context before it calls its pair's
+static int chunks_args(plan_ctx* c, int B, const double* x0, const double* s_target) {
+    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
+    if (B == 0) return PLAN_SUCCESS;
+    if (!x0 || !s_target) return fail(PLAN_E_ARG, "x0 and s_target are required");
+    return PLAN_SUCCESS;
+}
+
+static int optimize_args(plan_ctx* c, const char* entry, int B, int Nmax, std::initializer_list<const void*> arrays,
+                         double max_chunk_size, int max_chunks, int nav) {
+    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
+    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
+    if (B == 0) return PLAN_SUCCESS;
+    for (const void* a : arrays)
+        if (!a) return fail(PLAN_E_ARG, std::string(entry) + ": every array is required");
+    if (Nmax < 1 || Nmax > PLAN_MAX_N) return fail(PLAN_E_ARG, "Nmax out of range [1, PLAN_MAX_N]");
+    if (max_chunks < 1) return fail(PLAN_E_ARG, "max_chunks must be >= 1");
+    if (nav < 1) return fail(PLAN_E_ARG, "avg must have at least one entry");
+    if (!(max_chunk_size > 0.0) || !std::isfinite(max_chunk_size)) return fail(PLAN_E_ARG, "max_chunk_size must be > 0");
+    return PLAN_SUCCESS;
+}
+
+// *lds = the dynamic LDS `kernel` needs at row stride Nmax on the context's device; above 64 KiB its limit is raised
+static int kernel_lds(plan_ctx* c, int Nmax, const void* kernel, size_t* lds) {
+    *lds = lds_bytes(Nmax);
+    if (*lds > c->lds_max) return fail(PLAN_E_ARG, "Nmax too large for the device's LDS");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
+    if (*lds > 65536 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
+        return fail(PLAN_E_LAUNCH, "cannot raise the kernel's LDS limit");
+    return PLAN_SUCCESS;
+}
+
+// A host entry's round trip: its arrays bound to the context's arena (staging.h), then in blocking order on the null
+// stream the uploads, its device twin on the device arrays, a device synchronisation and the downloads
+template <typename Bind, typename Call>
+static int staged_call(plan_ctx* c, const char* kernel, Bind&& bindings, Call&& device_entry) {
+    staging::Staging S(c->arena);
+    if (!S.bind([&] { bindings(S); })) return fail(PLAN_E_ALLOC, "staging allocation failed");
+    if (S.upload() != hipSuccess) return fail(PLAN_E_DEVICE, "input upload failed");
+    if (int rc = device_entry()) return rc;
+    if (hipError_t e = S.sync(); e != hipSuccess)
+        return fail(PLAN_E_DEVICE, std::string(kernel) + " failed: " + hipGetErrorString(e));
+    if (S.fetch() != hipSuccess) return fail(PLAN_E_DEVICE, "output download failed");
     return PLAN_SUCCESS;
 }
 
@@ -243,7 +290,7 @@ void plan_destroy(plan_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     if (c->d_route) (void)hipFree(c->d_route);
-    if (c->io) (void)hipFree(c->io);
+    c->arena.release();
     for (auto& e : c->order_bufs) {
         (void)hipFree(e.ptr);
         (void)hipEventDestroy(e.done);
@@ -254,20 +301,13 @@ void plan_destroy(plan_ctx* c) {
 int plan_solve_chunks_device(plan_ctx* c, int B, int Nmax, const int* N, const double* x0, const double* s_target,
                              const int* is_final, double* X, double* U, double* S, int* status, int* iters, int* sqp,
                              void* stream) {
-    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
-    if (c->host) return fail(PLAN_E_DEVICE, "plan_solve_chunks_device on a host context (device = -1): use plan_solve_chunks");
-    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
-    if (B == 0) return PLAN_SUCCESS;
-    if (!x0 || !s_target) return fail(PLAN_E_ARG, "x0 and s_target are required");
+    if (c && c->host) return fail(PLAN_E_DEVICE, "plan_solve_chunks_device on a host context (device = -1): use plan_solve_chunks");
+    if (int rc = chunks_args(c, B, x0, s_target); rc || B == 0) return rc;
     // Nmax is always the caller's row stride; without per-chunk N every chunk has the params' horizon
     if (Nmax < 1 || Nmax > PLAN_MAX_N) return fail(PLAN_E_ARG, "Nmax out of range [1, PLAN_MAX_N]");
     if (!N && Nmax < c->p.N) return fail(PLAN_E_ARG, "Nmax must be >= params N when N is NULL (Nmax is the row stride)");
-    const size_t lds = lds_bytes(Nmax);
-    if (lds > c->lds_max) return fail(PLAN_E_ARG, "Nmax too large for the device's LDS");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)plan_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return fail(PLAN_E_LAUNCH, "cannot raise the kernel's LDS limit");
+    size_t lds = 0;
+    if (int rc = kernel_lds(c, Nmax, (const void*)plan_chunk_kernel, &lds)) return rc;
     KArgs a;
     a.R = c->R;
     a.P = c->p;
@@ -323,12 +363,8 @@ int plan_chunks_per_cu(plan_ctx* c, int Nmax, int* out) {
     if (!c || !out) return fail(PLAN_E_ARG, "ctx and out are required");
     if (c->host) return fail(PLAN_E_DEVICE, "plan_chunks_per_cu on a host context (device = -1)");
     if (Nmax < 1 || Nmax > PLAN_MAX_N) return fail(PLAN_E_ARG, "Nmax out of range [1, PLAN_MAX_N]");
-    const size_t lds = lds_bytes(Nmax);
-    if (lds > c->lds_max) return fail(PLAN_E_ARG, "Nmax too large for the device's LDS");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)plan_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return fail(PLAN_E_LAUNCH, "cannot raise the kernel's LDS limit");
+    size_t lds = 0;
+    if (int rc = kernel_lds(c, Nmax, (const void*)plan_chunk_kernel, &lds)) return rc;
     // one workgroup (one wavefront) per chunk: the residency is set by the kernel's registers and its LDS
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan_chunk_kernel, WAVE, lds) != hipSuccess)
@@ -340,22 +376,13 @@ int plan_chunks_per_cu(plan_ctx* c, int Nmax, int* out) {
 int plan_optimize_device(plan_ctx* c, int B, int Nmax, const double* starts, double max_chunk_size, int max_chunks,
                          const double* avg, int nav, double* X, double* U, double* S, int* N, int* is_final,
                          int* status, int* iters, int* sqp, int* nchunks, void* stream) {
-    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
-    if (c->host) return fail(PLAN_E_DEVICE, "plan_optimize_device on a host context (device = -1): use plan_optimize");
-    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
-    if (B == 0) return PLAN_SUCCESS;
-    if (!starts || !avg || !X || !U || !S || !N || !is_final || !status || !iters || !sqp || !nchunks)
-        return fail(PLAN_E_ARG, "plan_optimize_device: every array is required");
-    if (Nmax < 1 || Nmax > PLAN_MAX_N) return fail(PLAN_E_ARG, "Nmax out of range [1, PLAN_MAX_N]");
-    if (max_chunks < 1) return fail(PLAN_E_ARG, "max_chunks must be >= 1");
-    if (nav < 1) return fail(PLAN_E_ARG, "avg must have at least one entry");
-    if (!(max_chunk_size > 0.0) || !std::isfinite(max_chunk_size)) return fail(PLAN_E_ARG, "max_chunk_size must be > 0");
-    const size_t lds = lds_bytes(Nmax);
-    if (lds > c->lds_max) return fail(PLAN_E_ARG, "Nmax too large for the device's LDS");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)plan_loop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return fail(PLAN_E_LAUNCH, "cannot raise the kernel's LDS limit");
+    if (c && c->host) return fail(PLAN_E_DEVICE, "plan_optimize_device on a host context (device = -1): use plan_optimize");
+    if (int rc = optimize_args(c, "plan_optimize_device", B, Nmax,
+                               {starts, avg, X, U, S, N, is_final, status, iters, sqp, nchunks}, max_chunk_size, max_chunks, nav);
+        rc || B == 0)
+        return rc;
+    size_t lds = 0;
+    if (int rc = kernel_lds(c, Nmax, (const void*)plan_loop_kernel, &lds)) return rc;
     LArgs a;
     a.R = c->R;
     a.P = c->p;
@@ -383,10 +410,7 @@ int plan_optimize_device(plan_ctx* c, int B, int Nmax, const double* starts, dou
 
 int plan_solve_chunks(plan_ctx* c, int B, const int* N, const double* x0, const double* s_target, const int* is_final,
                       double* X, double* U, double* S, int* status, int* iters, int* sqp) {
-    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
-    if (B == 0) return PLAN_SUCCESS;
-    if (!x0 || !s_target) return fail(PLAN_E_ARG, "x0 and s_target are required");
+    if (int rc = chunks_args(c, B, x0, s_target); rc || B == 0) return rc;
     int Nmax = c->p.N;
     if (N) {
         Nmax = 0;
@@ -400,103 +424,58 @@ int plan_solve_chunks(plan_ctx* c, int B, const int* N, const double* x0, const 
         return PLAN_SUCCESS;
     }
     if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    const size_t nX = (size_t)B * (Nmax + 1) * 5, nU = (size_t)B * Nmax * 2, nS = (size_t)B * Nmax;
-    const size_t bytes = sizeof(double) * (5 * (size_t)B + B + nX + nU + nS) + sizeof(int) * (5 * (size_t)B);
-    if (bytes > c->io_bytes) {
-        if (c->io) (void)hipFree(c->io);
-        c->io = nullptr;
-        c->io_bytes = 0;
-        if (hipMalloc(&c->io, bytes) != hipSuccess) return fail(PLAN_E_ALLOC, "staging allocation failed");
-        c->io_bytes = bytes;
-    }
-    double* d_x0 = (double*)c->io;
-    double* d_st = d_x0 + 5 * (size_t)B;
-    double* d_X = d_st + B;
-    double* d_U = d_X + nX;
-    double* d_S = d_U + nU;
-    int* d_N = (int*)(d_S + nS);
-    int* d_fin = d_N + B;
-    int* d_status = d_fin + B;
-    int* d_iters = d_status + B;
-    int* d_sqp = d_iters + B;
-    bool ok = hipMemcpy(d_x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_st, s_target, sizeof(double) * B, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && N) ok = hipMemcpy(d_N, N, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && is_final) ok = hipMemcpy(d_fin, is_final, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) return fail(PLAN_E_DEVICE, "input upload failed");
-    int rc = plan_solve_chunks_device(c, B, Nmax, N ? d_N : nullptr, d_x0, d_st, is_final ? d_fin : nullptr, d_X, d_U,
-                                      d_S, d_status, d_iters, d_sqp, nullptr);
-    if (rc != PLAN_SUCCESS) return rc;
-    if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
-        return fail(PLAN_E_DEVICE, std::string("plan kernel failed: ") + hipGetErrorString(e));
-    ok = (!X || hipMemcpy(X, d_X, sizeof(double) * nX, hipMemcpyDeviceToHost) == hipSuccess) &&
-         (!U || hipMemcpy(U, d_U, sizeof(double) * nU, hipMemcpyDeviceToHost) == hipSuccess) &&
-         (!S || hipMemcpy(S, d_S, sizeof(double) * nS, hipMemcpyDeviceToHost) == hipSuccess) &&
-         (!status || hipMemcpy(status, d_status, sizeof(int) * B, hipMemcpyDeviceToHost) == hipSuccess) &&
-         (!iters || hipMemcpy(iters, d_iters, sizeof(int) * B, hipMemcpyDeviceToHost) == hipSuccess) &&
-         (!sqp || hipMemcpy(sqp, d_sqp, sizeof(int) * B, hipMemcpyDeviceToHost) == hipSuccess);
-    if (!ok) return fail(PLAN_E_DEVICE, "output download failed");
-    return PLAN_SUCCESS;
+    const size_t nb = (size_t)B, nm = (size_t)Nmax;
+    double *d_x0, *d_st, *d_X, *d_U, *d_S;
+    int *d_N, *d_fin, *d_status, *d_iters, *d_sqp;
+    // the kernel writes all six outputs, asked for or not
+    return staged_call(c, "plan kernel", [&](staging::Staging& G) {
+        d_x0 = G.in(x0, nb * 5);
+        d_st = G.in(s_target, nb);
+        d_N = G.in(N, nb);
+        d_fin = G.in(is_final, nb);
+        d_X = G.out_or_scratch(X, nb * (nm + 1) * 5);
+        d_U = G.out_or_scratch(U, nb * nm * 2);
+        d_S = G.out_or_scratch(S, nb * nm);
+        d_status = G.out_or_scratch(status, nb);
+        d_iters = G.out_or_scratch(iters, nb);
+        d_sqp = G.out_or_scratch(sqp, nb);
+    }, [&] {
+        return plan_solve_chunks_device(c, B, Nmax, d_N, d_x0, d_st, d_fin, d_X, d_U, d_S, d_status, d_iters, d_sqp, nullptr);
+    });
 }
 
 int plan_optimize(plan_ctx* c, int B, int Nmax, const double* starts, double max_chunk_size, int max_chunks,
                   const double* avg, int nav, double* X, double* U, double* S, int* N, int* is_final, int* status,
                   int* iters, int* sqp, int* nchunks) {
-    if (!c) return fail(PLAN_E_ARG, "ctx is NULL");
-    if (B < 0) return fail(PLAN_E_ARG, "B must be >= 0");
-    if (B == 0) return PLAN_SUCCESS;
-    if (!starts || !avg || !X || !U || !S || !N || !is_final || !status || !iters || !sqp || !nchunks)
-        return fail(PLAN_E_ARG, "plan_optimize: every array is required");
-    if (Nmax < 1 || Nmax > PLAN_MAX_N) return fail(PLAN_E_ARG, "Nmax out of range [1, PLAN_MAX_N]");
-    if (max_chunks < 1) return fail(PLAN_E_ARG, "max_chunks must be >= 1");
-    if (nav < 1) return fail(PLAN_E_ARG, "avg must have at least one entry");
+    if (int rc = optimize_args(c, "plan_optimize", B, Nmax, {starts, avg, X, U, S, N, is_final, status, iters, sqp, nchunks},
+                               max_chunk_size, max_chunks, nav);
+        rc || B == 0)
+        return rc;
     if (c->host) {
-        if (!(max_chunk_size > 0.0) || !std::isfinite(max_chunk_size)) return fail(PLAN_E_ARG, "max_chunk_size must be > 0");
         plan_host::optimize(c->host, &c->p, B, Nmax, starts, max_chunk_size, max_chunks, avg, nav, X, U, S, N, is_final,
                             status, iters, sqp, nchunks, c->host_threads);
         return PLAN_SUCCESS;
     }
     if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    const size_t slots = (size_t)B * max_chunks;
-    const size_t nX = slots * (Nmax + 1) * 5, nU = slots * Nmax * 2, nS = slots * Nmax;
-    const size_t bytes = sizeof(double) * (5 * (size_t)B + nav + nX + nU + nS) + sizeof(int) * (5 * slots + B);
-    if (bytes > c->io_bytes) {
-        if (c->io) (void)hipFree(c->io);
-        c->io = nullptr;
-        c->io_bytes = 0;
-        if (hipMalloc(&c->io, bytes) != hipSuccess) return fail(PLAN_E_ALLOC, "staging allocation failed");
-        c->io_bytes = bytes;
-    }
-    double* d_st = (double*)c->io;
-    double* d_avg = d_st + 5 * (size_t)B;
-    double* d_X = d_avg + nav;
-    double* d_U = d_X + nX;
-    double* d_S = d_U + nU;
-    int* d_N = (int*)(d_S + nS);
-    int* d_fin = d_N + slots;
-    int* d_status = d_fin + slots;
-    int* d_iters = d_status + slots;
-    int* d_sqp = d_iters + slots;
-    int* d_nch = d_sqp + slots;
-    if (hipMemcpy(d_st, starts, sizeof(double) * 5 * B, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_avg, avg, sizeof(double) * nav, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(PLAN_E_DEVICE, "input upload failed");
-    int rc = plan_optimize_device(c, B, Nmax, d_st, max_chunk_size, max_chunks, d_avg, nav, d_X, d_U, d_S, d_N,
-                                  d_fin, d_status, d_iters, d_sqp, d_nch, nullptr);
-    if (rc != PLAN_SUCCESS) return rc;
-    if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
-        return fail(PLAN_E_DEVICE, std::string("plan loop kernel failed: ") + hipGetErrorString(e));
-    const bool ok = hipMemcpy(X, d_X, sizeof(double) * nX, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(U, d_U, sizeof(double) * nU, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(S, d_S, sizeof(double) * nS, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(N, d_N, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(is_final, d_fin, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(status, d_status, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(iters, d_iters, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(sqp, d_sqp, sizeof(int) * slots, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(nchunks, d_nch, sizeof(int) * B, hipMemcpyDeviceToHost) == hipSuccess;
-    if (!ok) return fail(PLAN_E_DEVICE, "output download failed");
-    return PLAN_SUCCESS;
+    const size_t nb = (size_t)B, nm = (size_t)Nmax, slots = nb * max_chunks;
+    double *d_st, *d_avg, *d_X, *d_U, *d_S;
+    int *d_N, *d_fin, *d_status, *d_iters, *d_sqp, *d_nch;
+    return staged_call(c, "plan loop kernel", [&](staging::Staging& G) {
+        d_st = G.in(starts, nb * 5);
+        d_avg = G.in(avg, (size_t)nav);
+        d_X = G.out(X, slots * (nm + 1) * 5);
+        d_U = G.out(U, slots * nm * 2);
+        d_S = G.out(S, slots * nm);
+        d_N = G.out(N, slots);
+        d_fin = G.out(is_final, slots);
+        d_status = G.out(status, slots);
+        d_iters = G.out(iters, slots);
+        d_sqp = G.out(sqp, slots);
+        d_nch = G.out(nchunks, nb);
+    }, [&] {
+        return plan_optimize_device(c, B, Nmax, d_st, max_chunk_size, max_chunks, d_avg, nav, d_X, d_U, d_S, d_N, d_fin,
+                                    d_status, d_iters, d_sqp, d_nch, nullptr);
+    });
 }
 
 // ---- the evaluator (plan_evaluate_kernel.h; host backend: plan_evaluate_host.h) ----
@@ -554,62 +533,36 @@ int plan_evaluate_chunks(plan_ctx* c, int B, int Nmax, const int* N, const doubl
     if (c->host)
         return plan_evaluate_chunks_device(c, B, Nmax, N, x0, s_target, is_final, X, U, S, summary, defects, rows, nullptr);
     if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    const size_t nX = (size_t)B * (Nmax + 1) * 5, nU = (size_t)B * Nmax * 2, nS = (size_t)B * Nmax;
-    const size_t nQ = (size_t)B * PLAN_EV_NQ, nD = (size_t)B * Nmax * 5, nR = (size_t)B * (Nmax + 1) * PLAN_EV_NR;
-    const size_t bytes = sizeof(double) * (5 * (size_t)B + B + nX + nU + nS + nQ + nD + nR) + sizeof(int) * (2 * (size_t)B);
-    if (bytes > c->io_bytes) {
-        if (c->io) (void)hipFree(c->io);
-        c->io = nullptr;
-        c->io_bytes = 0;
-        if (hipMalloc(&c->io, bytes) != hipSuccess) return fail(PLAN_E_ALLOC, "staging allocation failed");
-        c->io_bytes = bytes;
-    }
-    double* d_x0 = (double*)c->io;
-    double* d_st = d_x0 + 5 * (size_t)B;
-    double* d_X = d_st + B;
-    double* d_U = d_X + nX;
-    double* d_S = d_U + nU;
-    double* d_Q = d_S + nS;
-    double* d_D = d_Q + nQ;
-    double* d_R = d_D + nD;
-    int* d_N = (int*)(d_R + nR);
-    int* d_fin = d_N + B;
-    bool ok = hipMemcpy(d_x0, x0, sizeof(double) * 5 * B, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_st, s_target, sizeof(double) * B, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_X, X, sizeof(double) * nX, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_U, U, sizeof(double) * nU, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && S) ok = hipMemcpy(d_S, S, sizeof(double) * nS, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && N) ok = hipMemcpy(d_N, N, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && is_final) ok = hipMemcpy(d_fin, is_final, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) return fail(PLAN_E_DEVICE, "input upload failed");
-    int rc = plan_evaluate_chunks_device(c, B, Nmax, N ? d_N : nullptr, d_x0, d_st, is_final ? d_fin : nullptr, d_X, d_U,
-                                         S ? d_S : nullptr, summary ? d_Q : nullptr, defects ? d_D : nullptr,
-                                         rows ? d_R : nullptr, nullptr);
-    if (rc != PLAN_SUCCESS) return rc;
-    if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
-        return fail(PLAN_E_DEVICE, std::string("plan evaluate kernel failed: ") + hipGetErrorString(e));
     // a chunk whose N[b] is out of range leaves its rows and defects unwritten on the device; the caller's buffers
-    // keep their contents there, as with device pointers
+    // keep their contents there, as with device pointers: then the two are copied back chunk by chunk below
     bool all_in = true;
     for (int b = 0; b < B && N && all_in; ++b) all_in = N[b] >= 1 && N[b] <= Nmax;
-    ok = true;
-    if (all_in) {
-        if (defects) ok = hipMemcpy(defects, d_D, sizeof(double) * nD, hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok && rows) ok = hipMemcpy(rows, d_R, sizeof(double) * nR, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    for (int b = 0; b < B && ok && !all_in; ++b) {
-        const int n = N[b];
-        if (n < 1 || n > Nmax) continue;
+    const size_t nb = (size_t)B, nm = (size_t)Nmax, def_row = nm * 5, rows_row = (nm + 1) * PLAN_EV_NR;
+    double *d_x0, *d_st, *d_X, *d_U, *d_S, *d_Q, *d_D, *d_R;
+    int *d_N, *d_fin;
+    int rc = staged_call(c, "plan evaluate kernel", [&](staging::Staging& G) {
+        d_x0 = G.in(x0, nb * 5);
+        d_st = G.in(s_target, nb);
+        d_X = G.in(X, nb * (nm + 1) * 5);
+        d_U = G.in(U, nb * nm * 2);
+        d_S = G.in(S, nb * nm);
+        d_N = G.in(N, nb);
+        d_fin = G.in(is_final, nb);
+        d_D = all_in ? G.out(defects, nb * def_row) : (defects ? G.scratch<double>(nb * def_row) : nullptr);
+        d_R = all_in ? G.out(rows, nb * rows_row) : (rows ? G.scratch<double>(nb * rows_row) : nullptr);
+        d_Q = G.out(summary, nb * PLAN_EV_NQ);
+    }, [&] {
+        return plan_evaluate_chunks_device(c, B, Nmax, d_N, d_x0, d_st, d_fin, d_X, d_U, d_S, d_Q, d_D, d_R, nullptr);
+    });
+    bool ok = true;
+    for (int b = 0; b < B && rc == PLAN_SUCCESS && ok && !all_in; ++b) {
+        if (N[b] < 1 || N[b] > Nmax) continue;
         if (defects)
-            ok = hipMemcpy(defects + (size_t)b * Nmax * 5, d_D + (size_t)b * Nmax * 5, sizeof(double) * Nmax * 5,
-                           hipMemcpyDeviceToHost) == hipSuccess;
+            ok = hipMemcpy(defects + b * def_row, d_D + b * def_row, sizeof(double) * def_row, hipMemcpyDeviceToHost) == hipSuccess;
         if (ok && rows)
-            ok = hipMemcpy(rows + (size_t)b * (Nmax + 1) * PLAN_EV_NR, d_R + (size_t)b * (Nmax + 1) * PLAN_EV_NR,
-                           sizeof(double) * (Nmax + 1) * PLAN_EV_NR, hipMemcpyDeviceToHost) == hipSuccess;
+            ok = hipMemcpy(rows + b * rows_row, d_R + b * rows_row, sizeof(double) * rows_row, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (ok && summary) ok = hipMemcpy(summary, d_Q, sizeof(double) * nQ, hipMemcpyDeviceToHost) == hipSuccess;
-    if (!ok) return fail(PLAN_E_DEVICE, "output download failed");
-    return PLAN_SUCCESS;
+    return ok ? rc : fail(PLAN_E_DEVICE, "output download failed");
 }
 
 int plan_check_verdicts(const plan_ctx* c, int B, const double* summary, int* verdicts, int counts[8]) {
@@ -639,22 +592,20 @@ int plan_route_eval(plan_ctx* c, int n, const double* s, double* kappa, double* 
         return PLAN_SUCCESS;
     }
     if (hipSetDevice(c->device) != hipSuccess) return fail(PLAN_E_DEVICE, "hipSetDevice failed");
-    double* d = nullptr;
-    if (hipMalloc(&d, sizeof(double) * 4 * (size_t)n) != hipSuccess) return fail(PLAN_E_ALLOC, "allocation failed");
-    int rc = PLAN_SUCCESS;
-    if (hipMemcpy(d, s, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(PLAN_E_DEVICE, "upload failed");
-    if (rc == PLAN_SUCCESS) {
-        hipLaunchKernelGGL(route_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, c->R, n, d, d + n, d + 2 * n,
-                           d + 3 * n);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = fail(PLAN_E_LAUNCH, "route kernel failed");
-    }
-    if (rc == PLAN_SUCCESS &&
-        (hipMemcpy(kappa, d + n, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-         hipMemcpy(dkappa, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-         hipMemcpy(vmax, d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(PLAN_E_DEVICE, "download failed");
-    (void)hipFree(d);
-    return rc;
+    staging::Staging G(c->arena);
+    double *d_s, *d_kappa, *d_dkappa, *d_vmax;
+    const bool bound = G.bind([&] {
+        d_s = G.in(s, (size_t)n);
+        d_kappa = G.out(kappa, (size_t)n);
+        d_dkappa = G.out(dkappa, (size_t)n);
+        d_vmax = G.out(vmax, (size_t)n);
+    });
+    if (!bound) return fail(PLAN_E_ALLOC, "allocation failed");
+    if (G.upload() != hipSuccess) return fail(PLAN_E_DEVICE, "upload failed");
+    hipLaunchKernelGGL(route_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, c->R, n, d_s, d_kappa, d_dkappa, d_vmax);
+    if (hipGetLastError() != hipSuccess || G.sync() != hipSuccess) return fail(PLAN_E_LAUNCH, "route kernel failed");
+    if (G.fetch() != hipSuccess) return fail(PLAN_E_DEVICE, "download failed");
+    return PLAN_SUCCESS;
 }
 
 #ifdef PLAN_PROF
