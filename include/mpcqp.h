@@ -36,8 +36,8 @@ extern "C" {
  * 5: mpc_closed_loop_traffic, mpc_actors_from_fsm (mpc_actor); nothing else changed.
  *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
  *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device,
- *    mpc_closed_loop_traced, mpc_closed_loop_warm / mpc_default_warm and mpc_gradient_batch /
- *    mpc_gradient_batch_device. */
+ *    mpc_closed_loop_traced, mpc_closed_loop_warm / mpc_default_warm, mpc_gradient_batch /
+ *    mpc_gradient_batch_device and mpc_multipliers_batch / mpc_multipliers_batch_device. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -243,6 +243,66 @@ int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const double* obs, c
 int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                               const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                               double* costate, double* summary, void* stream);
+
+/* Batched multiplier estimates for the rows of constraints(x0, obstacles) at ANY control sequence U: the least-squares
+ * lam of  grad = J' lam  over the active rows and the controls off their bounds, where grad is mpc_gradient_batch's
+ * cost gradient and J the Jacobian of the rows.  Only (x0, obs, U) enter: no solver state.  The output lam can be
+ * handed to mpc_gradient_batch as it is.  No version step: detect it by the presence of its symbol.
+ *   x0, obs, n_obs, U   mpc_evaluate_batch's contract exactly
+ *   active_tol          a row is active when g <= active_tol (may be negative; NaN is MPC_E_ARG)
+ *   bound_tol           component c of control k is free iff u_min[c] + bound_tol < u < u_max[c] - bound_tol
+ *   rank_tol            the drop rule of the factorisation (below); bound_tol and rank_tol negative or NaN are MPC_E_ARG
+ * outputs (any may be NULL; all NULL is allowed and launches nothing):
+ *   lam     [B][N][7 + max_obs]   the layout of `rows`; every element is written, 0.0 wherever no multiplier is
+ *                                 estimated (columns past n_obs too).  Either sign, as least squares gives it
+ *   active  [B][MPC_MAX_ACTIVE]   the active rows in list order as (stage - 1) * (7 + max_obs) + column; -1 past
+ *                                 N_ACTIVE; all -1 on MPC_MU_OVERFLOW
+ *   summary [B][MPC_MU_NQ]        the MPC_MUQ_* columns below
+ * Per instance, with every sum in the stated order (the results do not depend on the backend or on B; a NaN stays in
+ * its instance; the host backend and the device agree bit for bit):
+ *   1  the rollout, the rows and grad are mpc_evaluate_batch's and mpc_gradient_batch's, the same bits
+ *   2  the active list takes the rows with g <= active_tol (a NaN row is never active) in the reference's order:
+ *      stage 1..N, within a stage the six lane rows, obstacles 0..n_obs-1, then v.  N_ACTIVE is their number; with
+ *      more than MPC_MAX_ACTIVE the status is MPC_MU_OVERFLOW and lam is zero
+ *   3  N_FREE counts the free components i = 2k + c.  N_ACTIVE > 0 with N_FREE == 0 is MPC_MU_NO_FREE, lam zero
+ *   4  j_a = J' e_a [2N] of active row a at stage t: p_t = grad_x g of that row alone (the coefficients of
+ *      mpc_gradient_batch's c_k for a unit weight), p_k = A_k' p_k+1 for k = t-1..1, j_a[2k + c] = dt p_k+1[3 + c] for
+ *      k < t and 0 for k >= t: jtl of a unit-lam call under ==.  If grad or a j_a is not finite on a free component,
+ *      or a row of the instance is NaN, the status is MPC_MU_NONFINITE and lam is zero
+ *   5  G[a][b] = sum_i j_a[i] j_b[i] and r[a] = sum_i j_a[i] grad[i], each one running sum from 0 over the free i
+ *      in increasing order
+ *   6  Cholesky in list order with a drop rule.  For c = 0, 1, ...: d = G[c][c] - sum L[c][e]^2 over the kept e < c,
+ *      subtracted one by one in increasing e.  Row c is dropped (lam 0, no part in anything later) when
+ *      !(d > rank_tol * G[c][c]) with the original diagonal; else L[c][c] = sqrt(d) and, for a > c,
+ *      L[a][c] = (G[a][c] - sum L[a][e] L[c][e]) / L[c][c] with the same subtraction order.  Forward substitution
+ *      y_c = (r[c] - sum L[c][e] y_e) / L[c][c], increasing e; back substitution lam_c = (y_c - sum L[e][c] lam_e)
+ *      / L[c][c] over the kept e > c, subtracted in decreasing e.  This picks independent rows greedily in the
+ *      reference's order; on a full-rank list it is the least-squares solution
+ * Misuse is MPC_E_ARG with a message; B == 0 succeeds. */
+#define MPC_MAX_ACTIVE 64
+#define MPC_MU_OK 0              /* also an empty active list (lam zero)                                       */
+#define MPC_MU_OVERFLOW 1        /* more than MPC_MAX_ACTIVE active rows; N_ACTIVE carries the true count      */
+#define MPC_MU_NO_FREE 2         /* active rows but every control component on a bound                         */
+#define MPC_MU_NONFINITE 3       /* grad or a row gradient is not finite on a free component, or a row is NaN  */
+#define MPC_MUQ_STATUS 0
+#define MPC_MUQ_N_ACTIVE 1
+#define MPC_MUQ_N_FREE 2
+#define MPC_MUQ_N_USED 3         /* the rows kept by the drop rule (0 unless the status is MPC_MU_OK)          */
+#define MPC_MUQ_RESID 4          /* max over the free i of |grad[i] - sum_a lam_a j_a[i]|, the sum from 0 over the
+                                    kept a in list order; NaN unless the status is OK; 0 with no free component */
+#define MPC_MUQ_MIN_PIVOT 5      /* the least d / G[c][c] over the kept rows; NaN if none is kept              */
+#define MPC_MU_NQ 6
+int mpc_multipliers_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs, const double* U,
+                          double active_tol, double bound_tol, double rank_tol, double* lam, int* active,
+                          double* summary);
+/* Same, with device pointers, launched asynchronously on `stream`: one kernel (one wavefront per instance), no host
+ * synchronisation, no allocation, graph-capturable.  The double arrays must be 8-byte aligned (MPC_E_ARG otherwise);
+ * n_obs without obs is MPC_E_ARG.  The call shares no state with the solver, so it may overlap a solve on another
+ * stream of the same context.  On a host context (device = -1) the pointers are host memory and the call is
+ * synchronous; every output equals the device's bit for bit. */
+int mpc_multipliers_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                 const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
+                                 int* active, double* summary, void* stream);
 
 /* Reference-signal service on the device table: TrajectoryLoader.get_state / get_control
  * (trajectory_loader.py:86-102), batched. Host buffers, synchronous.  out_state [n][5], out_control [n][2]. */

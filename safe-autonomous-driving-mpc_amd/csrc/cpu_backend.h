@@ -929,6 +929,128 @@ inline void gradient_one(const DevTable& R, const mpc_params& p, const double (*
     if (summary) gr_summary(summary, ev_sums(N, &ct[0][0], part).cost, G, lam != nullptr);
 }
 
+// mpc_multipliers_batch for one instance (include/mpcqp.h): the evaluator's rows and the gradient's cost sweep as
+// above, then tracker_model.h's mu_* steps, which mpc_multipliers_kernel (multiplier_kernel.h) runs with a lane per
+// active row, folded here one after the other in the order the header states, so every output equals the device's
+// bit for bit.  lam [N][rw], active [MPC_MAX_ACTIVE] and summary [MPC_MU_NQ] may be null.
+inline void multipliers_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
+                            int rw, const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
+                            int* active, double* summary) {
+    constexpr int MA = MPC_MAX_ACTIVE;
+    const int N = p.N, n2 = 2 * N;
+    const KParams P = model_params(p);
+    double A[kMaxN][5], q[kMaxN][5], rows[7 + MPC_MAX_OBS];
+    int list[MA], na = 0;
+    bool nonfinite = false;
+    EvRun run = ev_run_begin();
+    GrRun Gd = gr_run_begin();
+    for (int j = 0; j <= N; ++j) {
+        double st[5], sl[4], ct[3], cd[5];
+        get_state(R, X[j][0], st, sl);
+        if (j < N) stage_A(X[j], P.dt, st[3], sl[2], A[j]);
+        if (j >= 1) {
+            EvStage S = ev_stage_begin();
+            ev_stage(P, j, X[j], st, obs, nobs, rw, ct, rows, S, run);
+            gr_stage(P, j, X[j], st, sl, obs, nobs, nullptr, q[j - 1], cd, Gd);
+            for (int i = 0; i < 7 + nobs; ++i) {
+                const int col = mu_list_col(i, nobs);
+                if (rows[col] != rows[col]) nonfinite = true;
+                if (!mu_active(rows[col], active_tol)) continue;
+                if (na < MA) list[na] = (j - 1) * rw + col;
+                ++na;
+            }
+        }
+    }
+    double g0x[5], grad[2 * kMaxN];
+    bool fr[2 * kMaxN];
+    int nf = 0;
+    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0x);
+    for (int k = 0; k < N; ++k) {
+        double jt[2];
+        gr_control(P, U[2 * k], U[2 * k + 1], q[k], nullptr, grad + 2 * k, jt, Gd);
+        fr[2 * k] = mu_free(U[2 * k], P.u_min0, P.u_max0, bound_tol);
+        fr[2 * k + 1] = mu_free(U[2 * k + 1], P.u_min1, P.u_max1, bound_tol);
+        for (int c = 0; c < 2; ++c)
+            if (fr[2 * k + c]) {
+                ++nf;
+                if (!mu_finite(grad[2 * k + c])) nonfinite = true;
+            }
+    }
+    const bool listed = na <= MA && na > 0 && nf > 0;
+    static thread_local double J[MA][2 * kMaxN], W[MA][MA];
+    if (listed)
+        for (int a = 0; a < na; ++a) {
+            const int t = list[a] / rw + 1;
+            double c[5];
+            mu_row_grad(P, list[a] % rw, X[t], c);
+            for (int i = 0; i < n2; ++i) J[a][i] = 0.0;
+            mu_row_chain(t, P.dt, &A[0][0], c, [&](int i, double v) {
+                J[a][i] = v;
+                if (fr[i] && !mu_finite(v)) nonfinite = true;
+            });
+        }
+    const int status = mu_status(na, nf, nonfinite);
+    double lamv[MA], resid = 0.0, minpiv = INFINITY;
+    bool keep[MA];
+    int nu = 0;
+    for (int a = 0; a < MA; ++a) { lamv[a] = 0.0; keep[a] = false; }
+    if (status == MPC_MU_OK) {
+        const int m = listed ? na : 0;
+        double r[MA], g0[MA];
+        for (int a = 0; a < m; ++a) {
+            for (int b = 0; b <= a; ++b) {
+                double s = 0.0;
+                for (int i = 0; i < n2; ++i)
+                    if (fr[i]) s = s + J[a][i] * J[b][i];
+                W[a][b] = s;
+            }
+            double s = 0.0;
+            for (int i = 0; i < n2; ++i)
+                if (fr[i]) s = s + J[a][i] * grad[i];
+            r[a] = s;
+            g0[a] = W[a][a];
+        }
+        // right-looking: after column c every later row has L[a][c] L[b][c] taken off its entries, so the terms of
+        // an entry are subtracted in increasing c; r turns into y the same way
+        for (int c = 0; c < m; ++c) {
+            const double d = W[c][c];
+            keep[c] = mu_keep(d, g0[c], rank_tol);
+            if (!keep[c]) continue;
+            ++nu;
+            const double piv = d / g0[c];
+            if (piv < minpiv) minpiv = piv;
+            const double lcc = std::sqrt(d);
+            W[c][c] = lcc;
+            r[c] = r[c] / lcc;
+            for (int a = c + 1; a < m; ++a) {
+                W[a][c] = W[a][c] / lcc;
+                r[a] = r[a] - W[a][c] * r[c];
+                for (int b = c + 1; b <= a; ++b) W[a][b] = W[a][b] - W[a][c] * W[b][c];
+            }
+        }
+        for (int c = m - 1; c >= 0; --c) {
+            if (!keep[c]) continue;
+            lamv[c] = r[c] / W[c][c];
+            for (int a = 0; a < c; ++a) r[a] = r[a] - W[c][a] * lamv[c];
+        }
+        for (int i = 0; i < n2; ++i) {
+            if (!fr[i]) continue;
+            double s = 0.0;
+            for (int a = 0; a < m; ++a)
+                if (keep[a]) s = s + lamv[a] * J[a][i];
+            gr_nmax(resid, fabs(grad[i] - s));
+        }
+    }
+    if (lam) {
+        for (int i = 0; i < N * rw; ++i) lam[i] = 0.0;
+        for (int a = 0; a < MA; ++a)
+            if (keep[a]) lam[list[a]] = lamv[a];
+    }
+    if (active)
+        for (int a = 0; a < MA; ++a) active[a] = (na <= MA && a < na) ? list[a] : -1;
+    if (summary) mu_summary(summary, status, na, nf, nu, resid, minpiv);
+}
+
 // ---------------------------------------------------------------------------------------------
 // shared pieces of the closed-loop members of Backend
 // ---------------------------------------------------------------------------------------------
@@ -1125,6 +1247,24 @@ struct Backend {
                          jtl ? jtl + (size_t)b * 2 * N : nullptr, gx0 ? gx0 + 5 * (size_t)b : nullptr,
                          costate ? costate + (size_t)b * 5 * N : nullptr,
                          summary ? summary + (size_t)b * MPC_GR_NQ : nullptr);
+        });
+    }
+
+    // mpc_multipliers_batch on host buffers (the device entry's argument contract); lam is [B][N][7 + p.max_obs]
+    void multipliers_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                           const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
+                           int* active, double* summary) const {
+        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
+        parallel(p, B, [&](Worker& w, int b) {
+            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
+            no = no < 0 ? 0 : (no > mo ? mo : no);
+            double X[kMaxN + 1][5];
+            const double* Ub = U + (size_t)b * 2 * N;
+            w.predict(x0 + 5 * (size_t)b, Ub, X);
+            multipliers_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub, active_tol, bound_tol,
+                            rank_tol, lam ? lam + (size_t)b * N * rw : nullptr,
+                            active ? active + (size_t)b * MPC_MAX_ACTIVE : nullptr,
+                            summary ? summary + (size_t)b * MPC_MU_NQ : nullptr);
         });
     }
 

@@ -30,6 +30,7 @@
 //   warm_kernels.h         the warm starts' carry and keep kernels (the previous plan as the next ubar)
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 //   gradient_kernel.h      the batched gradients of that cost and of those rows (reverse sweeps)
+//   multiplier_kernel.h    the batched multiplier estimates of those rows (least squares over the active rows)
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points; the host entries stage their arrays through staging.h, the driver the closed-loop
 // entries share is closed_loop_host.h) and, last, the comm layer (comm.h).
@@ -61,6 +62,7 @@
 #include "warm_kernels.h"
 #include "evaluate_kernel.h"
 #include "gradient_kernel.h"
+#include "multiplier_kernel.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -461,6 +463,16 @@ static int gradient_args(mpc_ctx* c, int B, const double* x0, const double* obs,
                       jtl && !lam);
 }
 
+static int multipliers_args(mpc_ctx* c, int B, const double* x0, const double* obs, const double* U, double active_tol,
+                            double bound_tol, double rank_tol) {
+    int rc = batch_args(c, B, x0, obs, U ? nullptr : "U is NULL (the multiplier estimate needs the control sequence to estimate at)");
+    if (rc || B == 0) return rc;
+    if (active_tol != active_tol) return fail(MPC_E_ARG, "active_tol is NaN");
+    if (!(bound_tol >= 0.0)) return fail(MPC_E_ARG, "bound_tol is negative or NaN");
+    if (!(rank_tol >= 0.0)) return fail(MPC_E_ARG, "rank_tol is negative or NaN");
+    return MPC_SUCCESS;
+}
+
 static int device_args(const mpc_ctx* c, const double* obs, const int* n_obs, std::initializer_list<const double*> arrays) {
     if (c->p.max_obs > 0 && n_obs && !obs) return fail(MPC_E_ARG, "n_obs given but obs is NULL");
     for (const double* a : arrays)
@@ -629,6 +641,62 @@ extern "C" int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const dou
     }, [&] {
         return mpc_gradient_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_lam, d_grad, d_jtl, d_gx0, d_cos, d_sum,
                                          (void*)c->stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// batched multiplier estimates (multiplier_kernel.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int mpc_multipliers_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                            const double* U, double active_tol, double bound_tol, double rank_tol,
+                                            double* lam, int* active, double* summary, void* stream) {
+    int rc = multipliers_args(c, B, x0, obs, U, active_tol, bound_tol, rank_tol);
+    if (rc || B == 0) return rc;
+    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, summary}))) return rc;
+    if (!lam && !active && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->multipliers_batch(c->p, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary);
+        });
+    KParams kp = kparams(&c->p);
+    const int rw = 7 + c->p.max_obs;       // lam keeps the context's slab width without obstacles too
+    if (!obs) kp.max_obs = 0;
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    // one wavefront per instance; the lane-group class of N sizes the kernel's LDS
+    for_gl_obs(lane_group(kp.N), obs != nullptr, [&](auto gl, auto ob) {
+        hipLaunchKernelGGL((mpc_multipliers_kernel<decltype(gl)::value, decltype(ob)::value>), dim3(B), dim3(WAVE), 0,
+                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, active_tol, bound_tol,
+                           rank_tol, lam, active, summary);
+    });
+    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_multipliers_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                     const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
+                                     int* active, double* summary) {
+    int rc = multipliers_args(c, B, x0, obs, U, active_tol, bound_tol, rank_tol);
+    if (rc || B == 0) return rc;
+    if (!lam && !active && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->multipliers_batch(c->p, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary);
+        });
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+    double *d_x0, *d_obs, *d_U, *d_lam, *d_sum;
+    int *d_nobs, *d_act;
+    return staged_call(c, "hipMalloc multiplier staging", [&](staging::Staging& S) {
+        d_x0 = S.in(x0, nb * 5);
+        d_obs = S.in(obs, nb * mo * 2);
+        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
+        d_U = S.in(U, nb * N * 2);
+        d_lam = S.out(lam, nb * N * (7 + mo));
+        d_act = S.out(active, nb * MPC_MAX_ACTIVE);
+        d_sum = S.out(summary, nb * MPC_MU_NQ);
+    }, [&] {
+        return mpc_multipliers_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, active_tol, bound_tol, rank_tol, d_lam, d_act,
+                                            d_sum, (void*)c->stream);
     });
 }
 

@@ -493,3 +493,66 @@ TRACKER_MODEL_INLINE void gr_summary(double* o, double cost, const GrRun& R, boo
     o[MPC_GRQ_COMPL] = has_lam ? R.compl_ : NAN;
     o[MPC_GRQ_MIN_LAM] = has_lam ? R.minlam + 0.0 : NAN;
 }
+
+// ------------------------------------------------------------------------------------------
+// the multiplier estimate (mpc_multipliers_batch, include/mpcqp.h): least squares of grad = J' lam over the active
+// rows and the free controls.  The steps both sides decide by: the active test, the free test, the list order, a
+// row's own gradient and its reverse chain, the drop test and the summary
+// ------------------------------------------------------------------------------------------
+// a NaN row is never active
+TRACKER_MODEL_INLINE bool mu_active(double g, double active_tol) { return g <= active_tol; }
+// component c of a control u with its bounds (lo, hi); a NaN control is never free
+TRACKER_MODEL_INLINE bool mu_free(double u, double lo, double hi, double bound_tol) {
+    return lo + bound_tol < u && u < hi - bound_tol;
+}
+TRACKER_MODEL_INLINE bool mu_finite(double x) { return fabs(x) < INFINITY; }
+// the column (`rows` layout) of the i-th row of a stage in the reference's order, i = 0..6 + nobs: the six lane rows,
+// the obstacles, v
+TRACKER_MODEL_INLINE int mu_list_col(int i, int nobs) { return i < 6 ? i : (i < 6 + nobs ? i + 1 : 6); }
+// grad_x g of the row in column col alone at the rolled-out state x: gr_stage's c for a unit weight on that row
+TRACKER_MODEL_INLINE void mu_row_grad(const KParams& P, int col, const double* x, double* c) {
+    c[0] = c[1] = c[2] = c[3] = c[4] = 0.0;
+    if (col < 6) {
+        const double go = col < 2 ? 0.0 : (col < 4 ? P.L / 2.0 : P.L);
+        c[1] = (col & 1) ? 1.0 : -1.0;
+        if (col >= 2) c[2] = (col & 1) ? go : -go;
+    } else if (col == 6) {
+        c[4] = 1.0;
+    } else {
+        c[0] = -1.0;
+        if (x[4] * P.tgap > P.osd) c[4] = -P.tgap;
+    }
+}
+// The reverse chain of a row at stage t (1..N) from c = mu_row_grad: p_t = c, p_k = A_k' p_k+1; store(i, v) takes
+// j_a[i] for i = 2t-1 .. 0 (the components at or after stage t are zero and are not visited)
+template <typename Store>
+TRACKER_MODEL_INLINE void mu_row_chain(int t, double dt, const double* A, const double* c, Store store) {
+    double p[5] = {c[0], c[1], c[2], c[3], c[4]}, y[5];
+    for (int k = t - 1; k >= 0; --k) {
+        store(2 * k + 1, dt * p[4]);
+        store(2 * k, dt * p[3]);
+        if (k >= 1) {
+            gr_AT(A + 5 * k, dt, p, y);
+            TRACKER_UNROLL
+            for (int a = 0; a < 5; ++a) p[a] = y[a];
+        }
+    }
+}
+// the drop rule: the pivot d against the original diagonal g0
+TRACKER_MODEL_INLINE bool mu_keep(double d, double g0, double rank_tol) { return d > rank_tol * g0; }
+// the status from the counts (nonfinite: grad or a row gradient is not finite on a free component)
+TRACKER_MODEL_INLINE int mu_status(int n_active, int n_free, bool nonfinite) {
+    return n_active > MPC_MAX_ACTIVE ? MPC_MU_OVERFLOW
+                                     : (n_active > 0 && n_free == 0 ? MPC_MU_NO_FREE : (nonfinite ? MPC_MU_NONFINITE : MPC_MU_OK));
+}
+// The summary row o [MPC_MU_NQ]; resid and min_pivot are taken as they are when the status is OK
+TRACKER_MODEL_INLINE void mu_summary(double* o, int status, int n_active, int n_free, int n_used, double resid,
+                                     double min_pivot) {
+    const bool ok = status == MPC_MU_OK;
+    o[MPC_MUQ_STATUS] = (double)status;
+    o[MPC_MUQ_N_ACTIVE] = (double)n_active;
+    o[MPC_MUQ_N_FREE] = (double)n_free;
+    o[MPC_MUQ_N_USED] = ok ? (double)n_used : 0.0;
+    o[MPC_MUQ_RESID] = ok ? resid : NAN;
+    o[MPC_MUQ_MIN_PIVOT] = (ok && n_used > 0) ? min_pivot : NAN;
+}

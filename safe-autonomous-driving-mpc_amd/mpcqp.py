@@ -72,7 +72,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_gradient_batch", "mpc_gradient_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_gradient_batch", "mpc_gradient_batch_device", "mpc_multipliers_batch", "mpc_multipliers_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -120,6 +120,13 @@ EVQ_FIELDS = ("cost", "min_row", "argmin_stage", "argmin_kind", "l1", "n_neg", "
 GRQ_COST, GRQ_GRAD_INF, GRQ_LAG_INF, GRQ_PG_INF, GRQ_COMPL, GRQ_MIN_LAM = 0, 1, 2, 3, 4, 5
 GR_NQ = 6
 GRQ_FIELDS = ("cost", "grad_inf", "lag_inf", "pg_inf", "compl", "min_lam")
+# mpc_multipliers_batch: the list limit, the statuses (MPC_MU_*) and the columns of its summary (MPC_MUQ_*)
+MAX_ACTIVE = 64
+MU_OK, MU_OVERFLOW, MU_NO_FREE, MU_NONFINITE = 0, 1, 2, 3
+MU_NAMES = ("ok", "overflow", "no_free", "nonfinite")
+MUQ_STATUS, MUQ_N_ACTIVE, MUQ_N_FREE, MUQ_N_USED, MUQ_RESID, MUQ_MIN_PIVOT = 0, 1, 2, 3, 4, 5
+MU_NQ = 6
+MUQ_FIELDS = ("status", "n_active", "n_free", "n_used", "resid", "min_pivot")
 
 _lib = None
 
@@ -148,6 +155,12 @@ def lib():
     L.mpc_gradient_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     L.mpc_gradient_batch_device.restype = C.c_int
     L.mpc_gradient_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
+    L.mpc_multipliers_batch.restype = C.c_int
+    L.mpc_multipliers_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, C.c_double, C.c_double, C.c_double,
+                                        _dp, _ip, _dp]
+    L.mpc_multipliers_batch_device.restype = C.c_int
+    L.mpc_multipliers_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 3 + \
+        [C.c_void_p] * 4
     L.mpc_lookup.restype = C.c_int
     L.mpc_lookup.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.mpc_set_params.restype = C.c_int
@@ -471,6 +484,59 @@ class Solver:
         _check(lib().mpc_gradient_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, grad_ptr,
                                                jtl_ptr, gx0_ptr, costate_ptr, summary_ptr, C.c_void_p(stream)),
                "mpc_gradient_batch_device")
+
+    def multipliers_batch(self, x0, U, obs=None, n_obs=None, active_tol=1e-6, bound_tol=1e-9, rank_tol=1e-10,
+                          outputs=("lam", "active", "summary")):
+        """mpc_multipliers_batch: least-squares multiplier estimates of the constraint rows at ANY control sequences
+        U [B,N,2] from x0 [B,5] (obs, n_obs as in evaluate_batch): grad = J' lam over the rows with g <= active_tol
+        and the control components more than bound_tol inside their bounds, rows dropped greedily by rank_tol.
+        Returns dict(lam [B,N,7+max_obs] in the layout of evaluate_batch's rows (0 where nothing is estimated; hand
+        it to gradient_batch as it is), active [B,64] int32 (the active rows in the reference's order as
+        (stage - 1) * (7 + max_obs) + column, -1 past the count), summary [B,6] (columns MUQ_FIELDS: status MU_*,
+        active rows, free components, rows kept, least-squares residual, least pivot ratio)); `outputs` names the
+        ones to compute."""
+        p = self.params
+        N, mo = p.N, p.max_obs
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        if U is None:
+            raise ValueError("U is required: the control sequences to estimate the multipliers at")
+        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
+        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
+            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
+        if obs is not None and mo > 0:
+            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
+            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
+        else:
+            obs, n_obs = None, None
+        out = {}
+        if "lam" in outputs:
+            out["lam"] = np.empty((B, N, 7 + mo))
+        if "active" in outputs:
+            out["active"] = np.empty((B, MAX_ACTIVE), np.int32)
+        if "summary" in outputs:
+            out["summary"] = np.empty((B, MU_NQ))
+        _check(lib().mpc_multipliers_batch(self.h, B, _p(x0), _p(obs), _pi(n_obs), _p(U), float(active_tol),
+                                           float(bound_tol), float(rank_tol), _p(out.get("lam")),
+                                           _pi(out.get("active")), _p(out.get("summary"))), "mpc_multipliers_batch")
+        return out
+
+    def multipliers_batch_device(self, B, x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, active_ptr, summary_ptr,
+                                 active_tol=1e-6, bound_tol=1e-9, rank_tol=1e-10, stream=0):
+        """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr(); 0 / None = NULL)."""
+        _check(lib().mpc_multipliers_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, float(active_tol),
+                                                  float(bound_tol), float(rank_tol), lam_ptr, active_ptr, summary_ptr,
+                                                  C.c_void_p(stream)), "mpc_multipliers_batch_device")
+
+    def certify_batch(self, x0, U, obs=None, n_obs=None, active_tol=1e-6, bound_tol=1e-9, rank_tol=1e-10):
+        """The first-order certificate of U: multipliers_batch, then gradient_batch with its lam.  Returns
+        dict(lam, active, multipliers [B,6] (MUQ_FIELDS), summary [B,6] (GRQ_FIELDS: with lam, so pg_inf is the
+        projected gradient of the Lagrangian, compl the complementarity and min_lam the least multiplier), grad,
+        jtl)."""
+        m = self.multipliers_batch(x0, U, obs, n_obs, active_tol, bound_tol, rank_tol)
+        g = self.gradient_batch(x0, U, obs, n_obs, lam=m["lam"])
+        return dict(lam=m["lam"], active=m["active"], multipliers=m["summary"], summary=g["summary"], grad=g["grad"],
+                    jtl=g["jtl"])
 
     def closed_loop(self, x_init, fsm=None, max_steps=1000, s_stop=None, s_max=None):
         """Batched run_simulation (trajectory_tracking.py:377-443) on the device.

@@ -204,6 +204,18 @@ class TrajectoryTracker:
         r["n_obs"] = np.zeros(B, np.int32) if n is None else n
         return r
 
+    def certify_batch(self, x0, U, obstacles=None):
+        """The first-order certificate of the control sequences U [B,N,2] at x0 [B,5], on the library
+        (mpc_multipliers_batch, then mpc_gradient_batch with its multipliers); obstacles as in solve_batch.  Returns
+        mpcqp.Solver.certify_batch's dict, plus 'n_obs' [B]."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        obs, n = _obstacle_slab(B, obstacles)
+        slv = self.solver(max_obs=0 if obs is None else obs.shape[1])
+        r = slv.certify_batch(x0, U, obs, n)
+        r["n_obs"] = np.zeros(B, np.int32) if n is None else n
+        return r
+
 
 def _obstacle_slab(B, obstacles):
     """(obs [B,M,2], n_obs [B]) of solve_batch's obstacle forms: None, an array [B,M,2], or a list (len B) of

@@ -17,7 +17,12 @@ Times are reported as measured, no target: on a GPU the device-pointer entries o
 around `--inner` back-to-back calls, the median of `--runs` such windows after `--warmup` untimed ones, the entries
 alternating (the whole batch); with --device -1 the wall clock of the host backend's calls, the median of `--runs`.
 
-    python tools/optimality_report.py [--config C2] [--B n] [--sample 256] [--device 0 | -1] [--json]
+With --multipliers device the multipliers come from mpc_multipliers_batch instead (Solver.certify_batch) and the
+WHOLE batch is certified, not the sample: the same per-class tables, plus the instances per MPC_MU_* status and the
+rows the drop rule left out; the entry is timed beside the others, and the host estimate of the sample is timed
+once (wall clock) for comparison.  The default stays the host estimate on the sample.
+
+    python tools/optimality_report.py [--config C2] [--B n] [--sample 256] [--device 0 | -1] [--multipliers host | device] [--json]
 """
 import argparse
 import json
@@ -112,6 +117,7 @@ def device_times(a, solvers, wb, answers, B, N, mo):
     x0, obs, nob = t(wb["x0"]), t(wb["obs"]), t(wb["n_obs"], torch.int32)
     U = t(answers["bench"]["U"])
     lam = torch.zeros((B, N, 7 + mo), dtype=torch.float64, device=dev)
+    mu = dict(lam=e(B, N, 7 + mo), act=e(B, mpcqp.MAX_ACTIVE, dt=torch.int32), s=e(B, mpcqp.MU_NQ))
     o = dict(u0=e(B, 2), U=e(B, N, 2), X=e(B, N + 1, 5), st=e(B, dt=torch.int32), it=e(B, dt=torch.int32),
              ev=e(B, mpcqp.EV_NQ), grad=e(B, N, 2), jtl=e(B, N, 2), gx0=e(B, 5), gr=e(B, mpcqp.GR_NQ))
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -132,6 +138,10 @@ def device_times(a, solvers, wb, answers, B, N, mo):
                "gradient (all, with lam)": (lambda: bench.gradient_batch_device(
                    B, p(x0), p(obs), p(nob), p(U), p(lam), p(o["grad"]), p(o["jtl"]), p(o["gx0"]), None, p(o["gr"]),
                    stream=stream), a.inner)}
+    if a.multipliers == "device":
+        entries["multipliers (all)"] = (lambda: bench.multipliers_batch_device(
+            B, p(x0), p(obs), p(nob), p(U), p(mu["lam"]), p(mu["act"]), p(mu["s"]), active_tol=a.active_tol,
+            stream=stream), a.inner)
     ms = {k: [] for k in entries}
     for r in range(a.warmup + a.runs):
         for k, (fn, inner) in entries.items():
@@ -158,6 +168,9 @@ def host_times(a, solvers, wb, answers):
                "evaluate (summary)": lambda: bench.evaluate_batch(wb["x0"], U, wb["obs"], wb["n_obs"]),
                "gradient (grad, summary)": lambda: bench.gradient_batch(wb["x0"], U, wb["obs"], wb["n_obs"]),
                "gradient (all, with lam)": lambda: bench.gradient_batch(wb["x0"], U, wb["obs"], wb["n_obs"], lam=lam)}
+    if a.multipliers == "device":
+        entries["multipliers (all)"] = lambda: bench.multipliers_batch(wb["x0"], U, wb["obs"], wb["n_obs"],
+                                                                       active_tol=a.active_tol)
     ms = {k: [] for k in entries}
     for r in range(a.warmup + a.runs):
         for k, fn in entries.items():
@@ -179,6 +192,8 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--multipliers", default="host", choices=["host", "device"],
+                    help="host: numpy least squares on the sample (default); device: mpc_multipliers_batch on the whole batch")
     ap.add_argument("--json", action="store_true", help="also print one JSON line with every figure")
     a = ap.parse_args()
 
@@ -200,10 +215,24 @@ def main():
                                        mpcqp.default_params(N=N, max_obs=mo, sqp_iters=TT.SQP_ITERS), device=a.device))
     idx = np.unique(np.linspace(0, B - 1, min(a.sample, B)).astype(int))
     sub = lambda x: None if x is None else x[idx]
-    answers, tables = {}, {}
+    answers, tables, mu_counts, host_ms = {}, {}, {}, None
     for which, slv in solvers.items():
         answers[which] = slv.solve_batch(wb["x0"], wb["obs"], wb["n_obs"])
         xs, Us, os_, ns = wb["x0"][idx], answers[which]["U"][idx], sub(wb["obs"]), sub(wb["n_obs"])
+        if a.multipliers == "device":
+            c = solvers["bench"].certify_batch(wb["x0"], answers[which]["U"], wb["obs"], wb["n_obs"],
+                                               active_tol=a.active_tol)
+            m = c["multipliers"]
+            tables[which] = class_table(answers[which]["status"], c["summary"], m[:, mpcqp.MUQ_N_ACTIVE])
+            ok = m[:, mpcqp.MUQ_STATUS] == mpcqp.MU_OK
+            mu_counts[which] = dict({n: int((m[:, mpcqp.MUQ_STATUS] == i).sum()) for i, n in enumerate(mpcqp.MU_NAMES)},
+                                    dropped_rows=int((m[ok, mpcqp.MUQ_N_ACTIVE] - m[ok, mpcqp.MUQ_N_USED]).sum()),
+                                    instances_with_drops=int((m[ok, mpcqp.MUQ_N_ACTIVE] > m[ok, mpcqp.MUQ_N_USED]).sum()))
+            if which == "bench":
+                t0 = time.perf_counter()
+                estimate_multipliers(solvers["bench"], xs, Us, os_, ns, a.active_tol)
+                host_ms = 1e3 * (time.perf_counter() - t0)
+            continue
         lam, n_active = estimate_multipliers(solvers["bench"], xs, Us, os_, ns, a.active_tol)
         summary = solvers["bench"].gradient_batch(xs, Us, os_, ns, lam=lam)["summary"]
         tables[which] = class_table(answers[which]["status"][idx], summary, n_active)
@@ -213,8 +242,12 @@ def main():
     where = f"HIP device {a.device}" if a.device >= 0 else "host backend"
     print(f"optimality report {a.config} on the {where}: trajectory{wb['traj']}, N = {N}, B = {B}, max_obs = {mo}, "
           f"sample = {len(idx)}, active rows <= {a.active_tol:g}")
+    if a.multipliers == "device":
+        print(f"multipliers from mpc_multipliers_batch: the tables cover the whole batch of {B}")
     print_table("single QP at the warm start (sqp_iters = 1, what bench.py times):", tables["bench"])
     print_table(f"drop-in default (Gauss-Newton SQP, sqp_iters = {TT.SQP_ITERS}):", tables["dropin"])
+    for which, c in mu_counts.items():
+        print(f"  multiplier status ({which}): " + ", ".join(f"{k} {v}" for k, v in c.items()))
     if a.device >= 0:
         print(f"device time per call over the whole batch, median of {a.runs} windows of {a.inner} calls "
               f"({max(1, a.inner // 10)} for the SQP solve), min .. max:")
@@ -222,8 +255,11 @@ def main():
         print(f"wall clock per call over the whole batch, median of {a.runs} calls, min .. max:")
     for k, v in timing.items():
         print(f"  {k:<26}{v['median_ms']:>10.4f} ms   ({v['min_ms']:.4f} .. {v['max_ms']:.4f})")
+    if host_ms is not None:
+        print(f"  {'host estimate of the sample':<26}{host_ms:>10.4f} ms   (estimate_multipliers on {len(idx)} instances, "
+              f"wall clock, one call)")
     if a.json:
-        print(json.dumps(dict(config=a.config, device=a.device, traj=wb["traj"], N=N, B=B, max_obs=mo,
+        print(json.dumps(dict(multipliers=a.multipliers, mu_counts=mu_counts, host_estimate_ms=host_ms, config=a.config, device=a.device, traj=wb["traj"], N=N, B=B, max_obs=mo,
                               sample=int(len(idx)), active_tol=a.active_tol, tables=tables, timing_ms=timing)))
     for slv in solvers.values():
         slv.close()
