@@ -37,7 +37,8 @@ extern "C" {
  *    mpc_closed_loop_convoy was added later without a version step: detect it by the presence of its symbol.
  *    So were mpc_closed_loop_noisy / mpc_noise_draw, mpc_evaluate_batch / mpc_evaluate_batch_device,
  *    mpc_closed_loop_traced, mpc_closed_loop_warm / mpc_default_warm, mpc_gradient_batch /
- *    mpc_gradient_batch_device and mpc_multipliers_batch / mpc_multipliers_batch_device. */
+ *    mpc_gradient_batch_device, mpc_multipliers_batch / mpc_multipliers_batch_device and mpc_hessvec_batch /
+ *    mpc_hessvec_batch_device. */
 #define MPCQP_VERSION 5
 #define MPC_MAX_N 63          /* horizon limit (one lane per stage k=0..N in the kernel)   */
 #define MPC_MAX_OBS 64        /* obstacle slab limit per instance                            */
@@ -303,6 +304,71 @@ int mpc_multipliers_batch(mpc_ctx* c, int B, const double* x0, const double* obs
 int mpc_multipliers_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                  const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
                                  int* active, double* summary, void* stream);
+
+/* Batched Hessian-vector products and row tangents of what mpc_evaluate_batch computes, at ANY control sequence U:
+ * for M directions v in U per instance, (d2 L / dU2) v with L = cost - lam . g (the sign convention of
+ * MPC_GRQ_LAG_INF; L = cost when lam is NULL) and J v, the directional derivative of every row -- exact, by one
+ * forward tangent chain and one second-order reverse chain per direction over the rollout predict(x0, U).  The function
+ * differentiated is the evaluator's, as for mpc_gradient_batch: the table is piecewise linear with the lookup's
+ * interval, and the obstacle max follows v only where v * max_time_2_obs > obstacle_safety_distance.  Hence every row
+ * and every reference has zero second derivative, and H consists of the cost's own Hessian and of the bilinear dynamics
+ * (v o, v (k - k_ref(s))) weighted by the costate.  No version step: detect it by the presence of its symbol.
+ *   x0, obs, n_obs, U, lam   mpc_gradient_batch's contract exactly (lam may be NULL; columns >= 7 + n_obs[b] are never
+ *                       read)
+ *   M, V [B][M][N][2]   the directions, 1 <= M <= MPC_HV_MAX_DIRS.  V NULL: direction m is the unit vector e_m
+ *                       (m = 2k + c) and M <= 2N is required; M = 2N then yields the dense Hessian (HV[b][m] is its
+ *                       row and column m) and the dense row Jacobian (JV[b][m] is its column m) in one call
+ *   mode                MPC_HV_EXACT or MPC_HV_GAUSS_NEWTON (anything else is MPC_E_ARG)
+ * outputs (any may be NULL; all NULL is allowed and launches nothing):
+ *   HV   [B][M][N][2]             H v
+ *   JV   [B][M][N][7 + max_obs]   J v in the layout of `rows`, NaN past n_obs
+ *   curv [B][M][2]                (v'Hv, v'v), each one running sum from 0 over i = 0..2N-1 (i = 2k + c): + v_i HV_i,
+ *                                 + v_i v_i
+ *   summary [B][MPC_HV_NQ]        the MPC_HVQ_* columns below
+ * Per instance and direction, with x_k the rollout, a12..a24 mpc_gradient_batch's coefficients of A_k at x_k and
+ * d_ref', o_ref', k_ref', v_ref' the table slopes at s_k:
+ *   1  the rollout, A_k, q_k, c_k and both reverse sweeps are mpc_gradient_batch's, the same bits.  The Lagrangian
+ *      costate is pi_k = p_k - p'_k for k = 1..N, one subtraction per component; without lam it is p_k
+ *   2  tangent: dx_0 = 0; dx_k+1 = A_k dx_k + dt (0, 0, 0, v1_k, v2_k), by components
+ *        ds + dt dv;  (dd + a12 do) + a14 dv;  ((do + a20 ds) + a23 dk) + a24 dv;  dk + dt v1;  dv + dt v2
+ *   3  JV[m][k-1][col] = grad_x g_k,col . dx_k with the coefficients of mpc_multipliers_batch's step 4: the lane rows
+ *      dd + c do (c = 0, wheelbase / 2, wheelbase per pair; c do is formed only where c is not 0), negated for the even
+ *      columns; column 6 is dv; obstacle columns -ds, and (-ds) - max_time_2_obs dv where the max follows v
+ *   4  second-order reverse sweep: dpi_N = Q_N dx_N; dpi_k = (Q_k dx_k + A_k' dpi_k+1) + E_k for k = N-1..1, one
+ *      addition each per component, A_k' as in mpc_gradient_batch.  With t_d = (2 w_d) (dd - d_ref' ds), t_o and t_v
+ *      alike:  Q_k dx = (-((t_d d_ref' + t_o o_ref') + t_v v_ref'), t_d, t_o, 0, t_v).
+ *      E_k = (dA_k[dx_k])' pi_k+1 = (da20 pi[2], 0, da12 pi[1], da23 pi[2], da14 pi[1] + da24 pi[2]) with
+ *      da12 = dt dv, da14 = dt do, da20 = dt (-dv k_ref'), da23 = dt dv, da24 = dt (dk - k_ref' ds) at x_k.
+ *      In MPC_HV_GAUSS_NEWTON mode E_k is left out and lam does not enter HV: the curvature of the cost with the
+ *      dynamics linearised.  JV does not depend on the mode
+ *   5  HV[m][k] = ((2 w_u1) v1_k + dt dpi_k+1[3], (2 w_u2) v2_k + dt dpi_k+1[4])
+ * The results do not depend on the backend, on B, on M or on which other directions are in the call; a NaN stays in
+ * its instance and its direction.  Misuse is MPC_E_ARG with a message; B == 0 succeeds. */
+#define MPC_HV_MAX_DIRS 128
+#define MPC_HV_EXACT 0
+#define MPC_HV_GAUSS_NEWTON 1
+/* The device kernel carries 64 directions per pass of a wavefront for N <= MPC_HV_N64_MAX and 32 beyond; its LDS in
+ * doubles is 30 N + 10 + 2 MPC_HV_MAX_DIRS for the instance and 5 N (W + 1) for the W directions of a pass:
+ *   N = 20, W = 64:  58.9 KB (two workgroups per CU)     N = 56, W = 64: 161.2 KB     N = 63, W = 32: 100.4 KB
+ * The results do not depend on the pass width. */
+#define MPC_HV_N64_MAX 56
+#define MPC_HVQ_COST 0           /* the same bits as MPC_EVQ_COST                                              */
+#define MPC_HVQ_MIN_RAYLEIGH 1   /* min over m of v'Hv / v'v; numpy's rule: a NaN enters and stays, 0 / 0 is NaN */
+#define MPC_HVQ_MAX_RAYLEIGH 2   /* max over m of the same                                                     */
+#define MPC_HVQ_ARGMIN_DIR 3     /* np.argmin's direction: the first minimising m, or the first NaN one        */
+#define MPC_HVQ_N_NEG 4          /* the number of directions with v'Hv < 0                                     */
+#define MPC_HV_NQ 5
+int mpc_hessvec_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs, const double* U,
+                      const double* lam, int M, const double* V, int mode, double* HV, double* JV, double* curv,
+                      double* summary);
+/* Same, with device pointers, launched asynchronously on `stream`: one kernel (one wavefront per instance), no host
+ * synchronisation, no allocation, graph-capturable.  The double arrays must be 8-byte aligned (MPC_E_ARG otherwise);
+ * n_obs without obs is MPC_E_ARG.  The call shares no state with the solver, so it may overlap a solve on another
+ * stream of the same context.  On a host context (device = -1) the pointers are host memory and the call is
+ * synchronous; every output equals the device's bit for bit. */
+int mpc_hessvec_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                             const double* U, const double* lam, int M, const double* V, int mode, double* HV,
+                             double* JV, double* curv, double* summary, void* stream);
 
 /* Reference-signal service on the device table: TrajectoryLoader.get_state / get_control
  * (trajectory_loader.py:86-102), batched. Host buffers, synchronous.  out_state [n][5], out_control [n][2]. */

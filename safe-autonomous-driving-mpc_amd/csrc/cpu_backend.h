@@ -1051,6 +1051,83 @@ inline void multipliers_one(const DevTable& R, const mpc_params& p, const double
     if (summary) mu_summary(summary, status, na, nf, nu, resid, minpiv);
 }
 
+// mpc_hessvec_batch for one instance (include/mpcqp.h): the gradient's first phase as above (the rollout's stage
+// data, both reverse sweeps, pi = p - p'), then tracker_model.h's hv_* steps, which mpc_hessvec_kernel
+// (hessvec_kernel.h) runs with a lane per direction, folded here one direction after the other, so every output
+// equals the device's bit for bit.  V [M][N][2] or null (unit directions), HV [M][N][2], JV [M][N][rw], curv [M][2]
+// and summary [MPC_HV_NQ] may be null.
+inline void hessvec_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
+                        int rw, const double* U, const double* lam, int M, const double* V, int mode, double* HV,
+                        double* JV, double* curv, double* summary) {
+    const int N = p.N;
+    const KParams P = model_params(p);
+    const bool exact = mode == MPC_HV_EXACT;
+    double ct[kMaxN][5], part[kMaxN], A[kMaxN][5], q[kMaxN][5], c[kMaxN][5], sl[kMaxN + 1][4];
+    EvRun run = ev_run_begin();
+    GrRun G = gr_run_begin();
+    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], ct[k], run);
+    for (int j = 0; j <= N; ++j) {
+        double st[5];
+        get_state(R, X[j][0], st, sl[j]);
+        if (j < N) stage_A(X[j], P.dt, st[3], sl[j][2], A[j]);
+        if (j >= 1) {
+            EvStage S = ev_stage_begin();
+            ev_stage(P, j, X[j], st, obs, nobs, rw, ct[j - 1], nullptr, S, run);
+            gr_stage(P, j, X[j], st, sl[j], obs, nobs, lam ? lam + (size_t)(j - 1) * rw : nullptr, q[j - 1], c[j - 1], G);
+            part[j - 1] = 0.0;
+        }
+    }
+    double g0[5];
+    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0);
+    if (lam) {
+        gr_sweep(N, P.dt, &A[0][0], &c[0][0], g0);
+        for (int k = 0; k < N; ++k)
+            for (int a = 0; a < 5; ++a) q[k][a] = q[k][a] - c[k][a];      // pi = p - p'
+    }
+    double cvs[MPC_HV_MAX_DIRS][2];
+    for (int m = 0; m < M; ++m) {
+        const double* Vd = V ? V + (size_t)m * 2 * N : nullptr;
+        double dX[kMaxN][5];                   // dX[k] = dx_k+1
+        double dx[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < N; ++k) {
+            hv_tangent_step(A[k], P.dt, dx, hv_dir(Vd, m, k, 0), hv_dir(Vd, m, k, 1), dX[k]);
+            std::memcpy(dx, dX[k], sizeof(dx));
+        }
+        if (JV)
+            for (int k = 0; k < N; ++k)
+                for (int col = 0; col < rw; ++col)
+                    JV[((size_t)m * N + k) * rw + col] = hv_row_tangent(P, col, nobs, X[k + 1], dX[k]);
+        if (!HV && !curv && !summary) continue;
+        double dp[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, qd[5], e[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, y[5], dpc[kMaxN][2];
+        for (int k = N; k >= 1; --k) {
+            hv_stage(P, sl[k], dX[k - 1], qd);
+            if (k == N) {
+                std::memcpy(y, qd, sizeof(y));
+            } else {
+                if (exact) hv_second_order(P.dt, sl[k][2], dX[k - 1], q[k], e);
+                hv_reverse_step(A[k], P.dt, qd, dp, exact, e, y);
+            }
+            std::memcpy(dp, y, sizeof(dp));
+            dpc[k - 1][0] = y[3];
+            dpc[k - 1][1] = y[4];
+        }
+        double cv[2] = {0.0, 0.0}, hv[2];
+        for (int k = 0; k < N; ++k) {
+            const double v1 = hv_dir(Vd, m, k, 0), v2 = hv_dir(Vd, m, k, 1);
+            dp[3] = dpc[k][0];
+            dp[4] = dpc[k][1];
+            hv_control(P, v1, v2, dp, hv);
+            hv_curv(cv, v1, hv[0]);
+            hv_curv(cv, v2, hv[1]);
+            if (HV) std::memcpy(HV + ((size_t)m * N + k) * 2, hv, sizeof(hv));
+        }
+        cvs[m][0] = cv[0];
+        cvs[m][1] = cv[1];
+    }
+    if (curv) std::memcpy(curv, cvs, sizeof(double) * 2 * M);
+    if (summary) hv_summary(summary, ev_sums(N, &ct[0][0], part).cost, M, &cvs[0][0]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // shared pieces of the closed-loop members of Backend
 // ---------------------------------------------------------------------------------------------
@@ -1265,6 +1342,25 @@ struct Backend {
                             rank_tol, lam ? lam + (size_t)b * N * rw : nullptr,
                             active ? active + (size_t)b * MPC_MAX_ACTIVE : nullptr,
                             summary ? summary + (size_t)b * MPC_MU_NQ : nullptr);
+        });
+    }
+
+    // mpc_hessvec_batch on host buffers (the device entry's argument contract)
+    void hessvec_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                       const double* U, const double* lam, int M, const double* V, int mode, double* HV, double* JV,
+                       double* curv, double* summary) const {
+        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
+        parallel(p, B, [&](Worker& w, int b) {
+            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
+            no = no < 0 ? 0 : (no > mo ? mo : no);
+            double X[kMaxN + 1][5];
+            const double* Ub = U + (size_t)b * 2 * N;
+            const size_t bm = (size_t)b * M;
+            w.predict(x0 + 5 * (size_t)b, Ub, X);
+            hessvec_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
+                        lam ? lam + (size_t)b * N * rw : nullptr, M, V ? V + bm * 2 * N : nullptr, mode,
+                        HV ? HV + bm * 2 * N : nullptr, JV ? JV + bm * N * rw : nullptr, curv ? curv + bm * 2 : nullptr,
+                        summary ? summary + (size_t)b * MPC_HV_NQ : nullptr);
         });
     }
 

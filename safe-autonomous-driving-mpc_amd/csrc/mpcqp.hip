@@ -30,6 +30,7 @@
 //   warm_kernels.h         the warm starts' carry and keep kernels (the previous plan as the next ubar)
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 //   gradient_kernel.h      the batched gradients of that cost and of those rows (reverse sweeps)
+//   hessvec_kernel.h       the batched Hessian-vector products and row tangents (a lane per direction)
 //   multiplier_kernel.h    the batched multiplier estimates of those rows (least squares over the active rows)
 // Below them: the host side (error plumbing, mpc_ctx, mpc_create, launch_solve, the batch, closed-loop, pose
 // and lookup entry points; the host entries stage their arrays through staging.h, the driver the closed-loop
@@ -63,6 +64,7 @@
 #include "evaluate_kernel.h"
 #include "gradient_kernel.h"
 #include "multiplier_kernel.h"
+#include "hessvec_kernel.h"
 
 // ------------------------------------------------------------------------------------------
 // host side: C ABI
@@ -267,6 +269,17 @@ extern "C" int mpc_create(const double* X, int T, const double* U, int Tu, const
         hipFree(c->wl);
         c->wl = nullptr;
         c->cap_wl = 0;
+        (void)hipGetLastError();
+    }
+    // mpc_hessvec_kernel's dynamic LDS goes beyond 64 KB: declare the most a launch may ask for (here, so that no
+    // hessvec call does anything but launch).  A runtime that needs no such declaration may refuse it: ignored
+    {
+        const int n64 = (int)sizeof(double) * hv_lds_doubles(MPC_HV_N64_MAX, 64);
+        const int n32 = (int)sizeof(double) * hv_lds_doubles(MPC_MAX_N, 32);
+        (void)hipFuncSetAttribute((const void*)mpc_hessvec_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, n64);
+        (void)hipFuncSetAttribute((const void*)mpc_hessvec_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, n64);
+        (void)hipFuncSetAttribute((const void*)mpc_hessvec_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, n32);
+        (void)hipFuncSetAttribute((const void*)mpc_hessvec_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, n32);
         (void)hipGetLastError();
     }
     *out = c;
@@ -697,6 +710,78 @@ extern "C" int mpc_multipliers_batch(mpc_ctx* c, int B, const double* x0, const 
     }, [&] {
         return mpc_multipliers_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, active_tol, bound_tol, rank_tol, d_lam, d_act,
                                             d_sum, (void*)c->stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// batched Hessian-vector products and row tangents (hessvec_kernel.h)
+// ------------------------------------------------------------------------------------------
+static int hessvec_args(mpc_ctx* c, int B, const double* x0, const double* obs, const double* U, int M, const double* V,
+                        int mode) {
+    int rc = batch_args(c, B, x0, obs, U ? nullptr : "U is NULL (the Hessian needs the control sequence to differentiate at)");
+    if (rc || B == 0) return rc;
+    if (M < 1 || M > MPC_HV_MAX_DIRS) return fail(MPC_E_ARG, "M must be in 1..MPC_HV_MAX_DIRS");
+    if (!V && M > 2 * c->p.N) return fail(MPC_E_ARG, "V is NULL (unit directions) but M > 2 N");
+    if (mode != MPC_HV_EXACT && mode != MPC_HV_GAUSS_NEWTON)
+        return fail(MPC_E_ARG, "mode must be MPC_HV_EXACT or MPC_HV_GAUSS_NEWTON");
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_hessvec_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                        const double* U, const double* lam, int M, const double* V, int mode, double* HV,
+                                        double* JV, double* curv, double* summary, void* stream) {
+    int rc = hessvec_args(c, B, x0, obs, U, M, V, mode);
+    if (rc || B == 0) return rc;
+    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, V, HV, JV, curv, summary}))) return rc;
+    if (!HV && !JV && !curv && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->hessvec_batch(c->p, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary);
+        });
+    KParams kp = kparams(&c->p);
+    const int rw = 7 + c->p.max_obs;       // lam and JV keep the context's slab width without obstacles too
+    if (!obs) kp.max_obs = 0;
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    // one wavefront per instance; the pass width and the actual N size its LDS
+    const int W = hv_pass_width(kp.N);
+    const size_t lds = sizeof(double) * (size_t)hv_lds_doubles(kp.N, W);
+    for_gl_obs(W, obs != nullptr, [&](auto w, auto ob) {
+        constexpr int WV = decltype(w)::value == 32 ? 32 : 64;
+        hipLaunchKernelGGL((mpc_hessvec_kernel<WV, decltype(ob)::value>), dim3(B), dim3(WAVE), lds, (hipStream_t)stream,
+                           c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, lam, M, V, mode, HV, JV, curv, summary);
+    });
+    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+    return MPC_SUCCESS;
+}
+
+extern "C" int mpc_hessvec_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
+                                 const double* U, const double* lam, int M, const double* V, int mode, double* HV,
+                                 double* JV, double* curv, double* summary) {
+    int rc = hessvec_args(c, B, x0, obs, U, M, V, mode);
+    if (rc || B == 0) return rc;
+    if (!HV && !JV && !curv && !summary) return MPC_SUCCESS;
+    if (c->cpu)
+        return host_call([&] {
+            c->cpu->hessvec_batch(c->p, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary);
+        });
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs, nm = nb * (size_t)M;
+    double *d_x0, *d_obs, *d_U, *d_lam, *d_V, *d_HV, *d_JV, *d_curv, *d_sum;
+    int* d_nobs;
+    return staged_call(c, "hipMalloc hessvec staging", [&](staging::Staging& S) {
+        d_x0 = S.in(x0, nb * 5);
+        d_obs = S.in(obs, nb * mo * 2);
+        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
+        d_U = S.in(U, nb * N * 2);
+        d_lam = S.in(lam, nb * N * (7 + mo));
+        d_V = S.in(V, nm * N * 2);
+        d_HV = S.out(HV, nm * N * 2);
+        d_JV = S.out(JV, nm * N * (7 + mo));
+        d_curv = S.out(curv, nm * 2);
+        d_sum = S.out(summary, nb * MPC_HV_NQ);
+    }, [&] {
+        return mpc_hessvec_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_lam, M, d_V, mode, d_HV, d_JV, d_curv, d_sum,
+                                        (void*)c->stream);
     });
 }
 

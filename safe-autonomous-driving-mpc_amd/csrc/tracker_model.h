@@ -556,3 +556,102 @@ TRACKER_MODEL_INLINE void mu_summary(double* o, int status, int n_active, int n_
     o[MPC_MUQ_RESID] = ok ? resid : NAN;
     o[MPC_MUQ_MIN_PIVOT] = (ok && n_used > 0) ? min_pivot : NAN;
 }
+
+// ------------------------------------------------------------------------------------------
+// the Hessian-vector products and row tangents (mpc_hessvec_batch, include/mpcqp.h): for a direction v in U the
+// forward tangent chain dx_k over the rollout, the directional derivative of every row, and the second-order reverse
+// chain dpi_k whose control components give (d2 L / dU2) v.  Rows and references are piecewise linear, so the only
+// second-order terms are the cost's own Hessian (hv_stage) and the bilinear dynamics weighted by the costate
+// (hv_second_order)
+// ------------------------------------------------------------------------------------------
+// the pass width of the device kernel (hessvec_kernel.h): the directions a wavefront carries at once
+TRACKER_MODEL_INLINE constexpr int hv_pass_width(int N) { return N <= MPC_HV_N64_MAX ? 64 : 32; }
+// component c of control k of direction m: V's entry, or that of the unit vector e_m (m = 2k + c) without V
+TRACKER_MODEL_INLINE double hv_dir(const double* V, int m, int k, int c) {
+    return V ? V[2 * k + c] : (m == 2 * k + c ? 1.0 : 0.0);
+}
+// y = dx_k+1 = A_k dx_k + dt (0, 0, 0, v1, v2) with a = stage_A's (a12, a14, a20, a23, a24) at x_k
+TRACKER_MODEL_INLINE void hv_tangent_step(const double* a, double dt, const double* dx, double v1, double v2,
+                                          double* y) {
+    y[0] = dx[0] + dt * dx[4];
+    y[1] = (dx[1] + a[0] * dx[2]) + a[1] * dx[4];
+    y[2] = ((dx[2] + a[2] * dx[0]) + a[3] * dx[3]) + a[4] * dx[4];
+    y[3] = dx[3] + dt * v1;
+    y[4] = dx[4] + dt * v2;
+}
+// grad_x g . dx of the row in column col (`rows` layout) at the rolled-out state x: mu_row_grad's coefficients.
+// NaN for a column past the instance's obstacles
+TRACKER_MODEL_INLINE double hv_row_tangent(const KParams& P, int col, int nobs, const double* x, const double* dx) {
+    if (col < 6) {
+        const double go = col < 2 ? 0.0 : (col < 4 ? P.L / 2.0 : P.L);
+        const double t = col < 2 ? dx[1] : dx[1] + go * dx[2];
+        return (col & 1) ? t : -t;
+    }
+    if (col == 6) return dx[4];
+    if (col - 7 >= nobs) return NAN;
+    return x[4] * P.tgap > P.osd ? -dx[0] - P.tgap * dx[4] : -dx[0];
+}
+// y = Q_k dx: the Hessian of stage k's cost terms (sl = the slopes d', o', k', v' at x_k) applied to dx
+TRACKER_MODEL_INLINE void hv_stage(const KParams& P, const double* sl, const double* dx, double* y) {
+    const double td = (2.0 * P.w_d) * (dx[1] - sl[0] * dx[0]);
+    const double to = (2.0 * P.w_o) * (dx[2] - sl[1] * dx[0]);
+    const double tv = (2.0 * P.w_v) * (dx[4] - sl[3] * dx[0]);
+    y[0] = -((td * sl[0] + to * sl[1]) + tv * sl[3]);
+    y[1] = td;
+    y[2] = to;
+    y[3] = 0.0;
+    y[4] = tv;
+}
+// e = E_k = (dA_k[dx_k])' pi_k+1: the bilinear dynamics' second-order term, dk = k_ref' at x_k, pi = pi_k+1
+TRACKER_MODEL_INLINE void hv_second_order(double dt, double dk, const double* dx, const double* pi, double* e) {
+    const double da12 = dt * dx[4], da14 = dt * dx[2], da20 = dt * (-dx[4] * dk), da23 = dt * dx[4];
+    const double da24 = dt * (dx[3] - dk * dx[0]);
+    e[0] = da20 * pi[2];
+    e[1] = 0.0;
+    e[2] = da12 * pi[1];
+    e[3] = da23 * pi[2];
+    e[4] = da14 * pi[1] + da24 * pi[2];
+}
+// y = dpi_k = (qd + A_k' dpi_k+1) + e with qd = hv_stage's and e = hv_second_order's; e is left out (not read) in
+// Gauss-Newton mode
+TRACKER_MODEL_INLINE void hv_reverse_step(const double* a, double dt, const double* qd, const double* dpn,
+                                          bool exact, const double* e, double* y) {
+    double t[5];
+    gr_AT(a, dt, dpn, t);
+    TRACKER_UNROLL
+    for (int i = 0; i < 5; ++i) y[i] = exact ? (qd[i] + t[i]) + e[i] : qd[i] + t[i];
+}
+// control k of the direction (v1, v2) with dp = dpi_k+1: its two components of H v
+TRACKER_MODEL_INLINE void hv_control(const KParams& P, double v1, double v2, const double* dp, double* hv) {
+    hv[0] = (2.0 * P.w_u1) * v1 + P.dt * dp[3];
+    hv[1] = (2.0 * P.w_u2) * v2 + P.dt * dp[4];
+}
+// one term of (v'Hv, v'v): both are running sums from 0 over i = 0..2N-1
+TRACKER_MODEL_INLINE void hv_curv(double* cv, double v, double hv) {
+    cv[0] = cv[0] + v * hv;
+    cv[1] = cv[1] + v * v;
+}
+// The summary row o [MPC_HV_NQ] from curv [M][2], visited in increasing m: the Rayleigh quotients' extremes under
+// numpy's NaN rule, np.argmin's direction (the first minimum; the first NaN) and the count of v'Hv < 0
+TRACKER_MODEL_INLINE void hv_summary(double* o, double cost, int M, const double* curv) {
+    double lo = 0.0, hi = 0.0;
+    int arg = 0, nneg = 0;
+    for (int m = 0; m < M; ++m) {
+        const double r = curv[2 * m] / curv[2 * m + 1];
+        if (m == 0) {
+            lo = hi = r;
+        } else {
+            if (lo == lo && (r != r || r < lo)) {
+                lo = r;
+                arg = m;
+            }
+            if (hi == hi && (r != r || r > hi)) hi = r;
+        }
+        nneg += curv[2 * m] < 0.0 ? 1 : 0;
+    }
+    o[MPC_HVQ_COST] = cost;
+    o[MPC_HVQ_MIN_RAYLEIGH] = lo;
+    o[MPC_HVQ_MAX_RAYLEIGH] = hi;
+    o[MPC_HVQ_ARGMIN_DIR] = (double)arg;
+    o[MPC_HVQ_N_NEG] = (double)nneg;
+}

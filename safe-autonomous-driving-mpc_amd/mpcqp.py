@@ -72,7 +72,7 @@ EXPORTS = ["mpc_default_params", "mpc_create", "mpc_solve_batch", "mpc_solve_bat
            "mpc_set_params", "mpc_get_params", "mpc_last_error", "mpc_version", "mpc_destroy", "mpc_default_fsm",
            "mpc_closed_loop", "mpc_closed_loop_sweep", "mpc_cl_verdicts", "mpc_actors_from_fsm",
            "mpc_closed_loop_traffic", "mpc_closed_loop_convoy", "mpc_default_noise", "mpc_closed_loop_noisy",
-           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_gradient_batch", "mpc_gradient_batch_device", "mpc_multipliers_batch", "mpc_multipliers_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
+           "mpc_closed_loop_traced", "mpc_default_warm", "mpc_closed_loop_warm", "mpc_noise_draw", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_gradient_batch", "mpc_gradient_batch_device", "mpc_multipliers_batch", "mpc_multipliers_batch_device", "mpc_hessvec_batch", "mpc_hessvec_batch_device", "mpc_global_pose", "mpc_read_trajectory_json", "mpc_create_from_json",
            "mpc_comm_unique_id", "mpc_comm_create", "mpc_comm_info", "mpc_gather", "mpc_gather_host",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_comm_destroy"]
 COMM_UID_BYTES = 128
@@ -127,6 +127,13 @@ MU_NAMES = ("ok", "overflow", "no_free", "nonfinite")
 MUQ_STATUS, MUQ_N_ACTIVE, MUQ_N_FREE, MUQ_N_USED, MUQ_RESID, MUQ_MIN_PIVOT = 0, 1, 2, 3, 4, 5
 MU_NQ = 6
 MUQ_FIELDS = ("status", "n_active", "n_free", "n_used", "resid", "min_pivot")
+# mpc_hessvec_batch: the direction limit, the modes (MPC_HV_*) and the columns of its summary (MPC_HVQ_*)
+HV_MAX_DIRS = 128
+HV_EXACT, HV_GAUSS_NEWTON = 0, 1
+HV_MODES = {"exact": HV_EXACT, "gauss_newton": HV_GAUSS_NEWTON}
+HVQ_COST, HVQ_MIN_RAYLEIGH, HVQ_MAX_RAYLEIGH, HVQ_ARGMIN_DIR, HVQ_N_NEG = 0, 1, 2, 3, 4
+HV_NQ = 5
+HVQ_FIELDS = ("cost", "min_rayleigh", "max_rayleigh", "argmin_dir", "n_neg")
 
 _lib = None
 
@@ -158,6 +165,11 @@ def lib():
     L.mpc_multipliers_batch.restype = C.c_int
     L.mpc_multipliers_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, C.c_double, C.c_double, C.c_double,
                                         _dp, _ip, _dp]
+    L.mpc_hessvec_batch.restype = C.c_int
+    L.mpc_hessvec_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]
+    L.mpc_hessvec_batch_device.restype = C.c_int
+    L.mpc_hessvec_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int] + \
+        [C.c_void_p] * 5
     L.mpc_multipliers_batch_device.restype = C.c_int
     L.mpc_multipliers_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 3 + \
         [C.c_void_p] * 4
@@ -527,6 +539,63 @@ class Solver:
         _check(lib().mpc_multipliers_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, float(active_tol),
                                                   float(bound_tol), float(rank_tol), lam_ptr, active_ptr, summary_ptr,
                                                   C.c_void_p(stream)), "mpc_multipliers_batch_device")
+
+    def hessvec_batch(self, x0, U, V=None, M=None, lam=None, obs=None, n_obs=None, mode="exact",
+                      outputs=("HV", "JV", "curv", "summary")):
+        """mpc_hessvec_batch: Hessian-vector products and row tangents at ANY control sequences U [B,N,2] from x0 [B,5]
+        (obs, n_obs, lam as in gradient_batch).  V [B,M,N,2]: the directions; V None: the unit vectors e_0..e_M-1 of
+        the flattened U (M defaults to 2N, the dense Hessian).  mode "exact" (the Hessian of cost - lam . g) or
+        "gauss_newton" (the cost's with the dynamics linearised), or the HV_* integers.  Returns dict(HV [B,M,N,2] =
+        H v, JV [B,M,N,7+max_obs] = J v in the layout of evaluate_batch's rows, curv [B,M,2] = (v'Hv, v'v),
+        summary [B,5] (columns HVQ_FIELDS: cost, min and max Rayleigh quotient, its first minimising direction, the
+        directions of negative curvature)); `outputs` names the ones to compute."""
+        p = self.params
+        N, mo = p.N, p.max_obs
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        if U is None:
+            raise ValueError("U is required: the control sequences to differentiate at")
+        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
+        if V is not None:
+            V = np.ascontiguousarray(V, np.float64)
+            M = V.size // max(B * N * 2, 1) if M is None else int(M)
+            V = V.reshape(B, M, N, 2)
+        elif M is None:
+            M = 2 * N
+        M = int(M)
+        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
+            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
+        if obs is not None and mo > 0:
+            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
+            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
+        else:
+            obs, n_obs = None, None
+        if lam is not None:
+            lam = np.ascontiguousarray(lam, np.float64).reshape(B, N, 7 + mo)
+        Mo = max(M, 0)
+        shapes = dict(HV=(B, Mo, N, 2), JV=(B, Mo, N, 7 + mo), curv=(B, Mo, 2), summary=(B, HV_NQ))
+        out = {k: np.empty(shapes[k]) for k in shapes if k in outputs}
+        _check(lib().mpc_hessvec_batch(self.h, B, _p(x0), _p(obs), _pi(n_obs), _p(U), _p(lam), M, _p(V),
+                                       int(HV_MODES.get(mode, mode)), _p(out.get("HV")), _p(out.get("JV")),
+                                       _p(out.get("curv")), _p(out.get("summary"))), "mpc_hessvec_batch")
+        return out
+
+    def hessvec_batch_device(self, B, x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, M, V_ptr, mode, HV_ptr, JV_ptr,
+                             curv_ptr, summary_ptr, stream=0):
+        """Device-pointer variant (ints are raw device addresses, e.g. torch tensor.data_ptr(); 0 / None = NULL)."""
+        _check(lib().mpc_hessvec_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, U_ptr, lam_ptr, int(M), V_ptr,
+                                              int(HV_MODES.get(mode, mode)), HV_ptr, JV_ptr, curv_ptr, summary_ptr,
+                                              C.c_void_p(stream)), "mpc_hessvec_batch_device")
+
+    def hessian_batch(self, x0, U, lam=None, obs=None, n_obs=None, mode="exact"):
+        """The dense second-order data of U in one call (V NULL, M = 2N): dict(H [B,2N,2N] = the Hessian of
+        cost - lam . g in the flattened U (index 2k + c), J [B,N*(7+max_obs),2N] = the Jacobian of the rows in the
+        flattened layout of evaluate_batch's rows (NaN rows past n_obs), curv, summary as hessvec_batch)."""
+        N = self.params.N
+        r = self.hessvec_batch(x0, U, None, 2 * N, lam, obs, n_obs, mode)
+        B = r["HV"].shape[0]
+        return dict(H=r["HV"].reshape(B, 2 * N, 2 * N), J=r["JV"].reshape(B, 2 * N, -1).transpose(0, 2, 1).copy(),
+                    curv=r["curv"], summary=r["summary"])
 
     def certify_batch(self, x0, U, obs=None, n_obs=None, active_tol=1e-6, bound_tol=1e-9, rank_tol=1e-10):
         """The first-order certificate of U: multipliers_batch, then gradient_batch with its lam.  Returns

@@ -216,6 +216,18 @@ class TrajectoryTracker:
         r["n_obs"] = np.zeros(B, np.int32) if n is None else n
         return r
 
+    def hessian_batch(self, x0, U, lam=None, obstacles=None, mode="exact"):
+        """The dense Hessian of cost - lam . g and the dense Jacobian of the rows at the control sequences U [B,N,2]
+        from x0 [B,5], on the library (mpc_hessvec_batch with unit directions); obstacles as in solve_batch, lam as
+        certify_batch returns it.  Returns mpcqp.Solver.hessian_batch's dict, plus 'n_obs' [B]."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 5)
+        B = x0.shape[0]
+        obs, n = _obstacle_slab(B, obstacles)
+        slv = self.solver(max_obs=0 if obs is None else obs.shape[1])
+        r = slv.hessian_batch(x0, U, lam, obs, n, mode)
+        r["n_obs"] = np.zeros(B, np.int32) if n is None else n
+        return r
+
 
 def _obstacle_slab(B, obstacles):
     """(obs [B,M,2], n_obs [B]) of solve_batch's obstacle forms: None, an array [B,M,2], or a list (len B) of

@@ -62,6 +62,12 @@ def gradient_kernel_key(name):
     return tuple(int(x) for x in m.groups()) if m else None
 
 
+def hessvec_kernel_key(name):
+    """(W, OBS) of a mangled mpc_hessvec_kernel<W, OBS> name, else None."""
+    m = re.search(r"mpc_hessvec_kernelILi(\d+)ELb([01])E", name)
+    return tuple(int(x) for x in m.groups()) if m else None
+
+
 def plan_evaluate_kernel_key(name):
     """True for the mangled name of libmpcplan.so's plan_evaluate_kernel (one instantiation), else None."""
     return True if re.search(r"^_Z\d+plan_evaluate_kernel", name) else None
