@@ -891,46 +891,68 @@ inline void evaluate_one(const DevTable& R, const mpc_params& p, const double (*
     if (terms) std::memcpy(terms, Z.t, sizeof(Z.t));
 }
 
-// mpc_gradient_batch for one instance (include/mpcqp.h): tracker_model.h's steps of a stage, of the reverse sweep
-// and of a control, which mpc_gradient_kernel (gradient_kernel.h) runs a lane each, folded here one after the
-// other, so every output equals the device's bit for bit.  X is the rollout predict(x0, U) [N+1][5]; lam [N][rw]
+// The linearisation the gradient, the multiplier estimate and the Hessian-vector products start from, for one instance:
+// the host twin of evaluator_common.h's evc_linearise and evc_sweeps, folded over the stages one after the other.  From
+// the rollout X [N+1][5] it fills the cost terms ct and the zero L1 partials (ev_sums' operands), A_0..A_N-1, the
+// slopes of the reference at s_0..s_N, the stage gradients q and c (c weighted by lam [N][rw], zero without it), and
+// then sweeps q (and c, with lam) in place into the costates; g0 = A_0' p_1 of the cost.  With `rows` [rw] each stage's
+// rows are stored there and after_stage(j) is called while they hold stage j's.
+struct Linearised {
+    double ct[kMaxN][5], part[kMaxN], A[kMaxN][5], q[kMaxN][5], c[kMaxN][5], sl[kMaxN + 1][4], g0[5];
+};
+template <typename AfterStage>
+inline void linearise_one(const DevTable& R, const KParams& P, int N, const double (*X)[5], const double* obs, int nobs,
+                          int rw, const double* U, const double* lam, double* rows, Linearised& L, GrRun& G,
+                          AfterStage after_stage) {
+    EvRun run = ev_run_begin();
+    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], L.ct[k], run);
+    for (int j = 0; j <= N; ++j) {
+        double st[5];
+        get_state(R, X[j][0], st, L.sl[j]);
+        if (j < N) stage_A(X[j], P.dt, st[3], L.sl[j][2], L.A[j]);
+        if (j >= 1) {
+            EvStage S = ev_stage_begin();
+            ev_stage(P, j, X[j], st, obs, nobs, rw, L.ct[j - 1], rows, S, run);
+            gr_stage(P, j, X[j], st, L.sl[j], obs, nobs, lam ? lam + (size_t)(j - 1) * rw : nullptr, L.q[j - 1],
+                     L.c[j - 1], G);
+            L.part[j - 1] = 0.0;
+            after_stage(j);
+        }
+    }
+    double g0r[5];
+    for (int rows_too = 0; rows_too <= (lam ? 1 : 0); ++rows_too)
+        gr_sweep(N, P.dt, &L.A[0][0], rows_too ? &L.c[0][0] : &L.q[0][0], rows_too ? g0r : L.g0);
+}
+inline void linearise_one(const DevTable& R, const KParams& P, int N, const double (*X)[5], const double* obs, int nobs,
+                          int rw, const double* U, const double* lam, Linearised& L, GrRun& G) {
+    linearise_one(R, P, N, X, obs, nobs, rw, U, lam, nullptr, L, G, [](int) {});
+}
+
+// mpc_gradient_batch for one instance (include/mpcqp.h): the linearisation above, then tracker_model.h's step of a
+// control, which mpc_gradient_kernel (gradient_kernel.h) runs a lane each, folded here one after the other, so every
+// output equals the device's bit for bit.  X is the rollout predict(x0, U) [N+1][5]; lam [N][rw]
 // (rw = 7 + params.max_obs), grad [N][2], jtl [N][2], gx0 [5], costate [N][5] and summary [MPC_GR_NQ] may be null.
 inline void gradient_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
                          int rw, const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                          double* costate, double* summary) {
     const int N = p.N;
     const KParams P = model_params(p);
-    double ct[kMaxN][5], part[kMaxN], A[kMaxN][5], q[kMaxN][5], c[kMaxN][5];
-    EvRun run = ev_run_begin();
+    Linearised L;
     GrRun G = gr_run_begin();
-    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], ct[k], run);
-    for (int j = 0; j <= N; ++j) {
-        double st[5], sl[4];
-        get_state(R, X[j][0], st, sl);
-        if (j < N) stage_A(X[j], P.dt, st[3], sl[2], A[j]);
-        if (j >= 1) {
-            EvStage S = ev_stage_begin();
-            ev_stage(P, j, X[j], st, obs, nobs, rw, ct[j - 1], nullptr, S, run);
-            gr_stage(P, j, X[j], st, sl, obs, nobs, lam ? lam + (size_t)(j - 1) * rw : nullptr, q[j - 1], c[j - 1], G);
-            part[j - 1] = 0.0;
-        }
-    }
-    double g0[5], g0r[5];
-    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0);
-    if (lam) gr_sweep(N, P.dt, &A[0][0], &c[0][0], g0r);
+    linearise_one(R, P, N, X, obs, nobs, rw, U, lam, L, G);
     for (int k = 0; k < N; ++k) {
         double g[2], jt[2];
-        gr_control(P, U[2 * k], U[2 * k + 1], q[k], lam ? c[k] : nullptr, g, jt, G);
+        gr_control(P, U[2 * k], U[2 * k + 1], L.q[k], lam ? L.c[k] : nullptr, g, jt, G);
         if (grad) std::memcpy(grad + 2 * k, g, sizeof(g));
         if (jtl) std::memcpy(jtl + 2 * k, jt, sizeof(jt));
     }
-    if (gx0) std::memcpy(gx0, g0, sizeof(g0));
-    if (costate) std::memcpy(costate, q, sizeof(double) * 5 * N);
-    if (summary) gr_summary(summary, ev_sums(N, &ct[0][0], part).cost, G, lam != nullptr);
+    if (gx0) std::memcpy(gx0, L.g0, sizeof(L.g0));
+    if (costate) std::memcpy(costate, L.q, sizeof(double) * 5 * N);
+    if (summary) gr_summary(summary, ev_sums(N, &L.ct[0][0], L.part).cost, G, lam != nullptr);
 }
 
-// mpc_multipliers_batch for one instance (include/mpcqp.h): the evaluator's rows and the gradient's cost sweep as
-// above, then tracker_model.h's mu_* steps, which mpc_multipliers_kernel (multiplier_kernel.h) runs with a lane per
+// mpc_multipliers_batch for one instance (include/mpcqp.h): the linearisation above without row weights, its rows
+// listed stage by stage, then tracker_model.h's mu_* steps, which mpc_multipliers_kernel (multiplier_kernel.h) runs with a lane per
 // active row, folded here one after the other in the order the header states, so every output equals the device's
 // bit for bit.  lam [N][rw], active [MPC_MAX_ACTIVE] and summary [MPC_MU_NQ] may be null.
 inline void multipliers_one(const DevTable& R, const mpc_params& p, const double (*X)[5], const double* obs, int nobs,
@@ -939,32 +961,24 @@ inline void multipliers_one(const DevTable& R, const mpc_params& p, const double
     constexpr int MA = MPC_MAX_ACTIVE;
     const int N = p.N, n2 = 2 * N;
     const KParams P = model_params(p);
-    double A[kMaxN][5], q[kMaxN][5], rows[7 + MPC_MAX_OBS];
+    double rows[7 + MPC_MAX_OBS];
     int list[MA], na = 0;
     bool nonfinite = false;
-    EvRun run = ev_run_begin();
+    Linearised L;
     GrRun Gd = gr_run_begin();
-    for (int j = 0; j <= N; ++j) {
-        double st[5], sl[4], ct[3], cd[5];
-        get_state(R, X[j][0], st, sl);
-        if (j < N) stage_A(X[j], P.dt, st[3], sl[2], A[j]);
-        if (j >= 1) {
-            EvStage S = ev_stage_begin();
-            ev_stage(P, j, X[j], st, obs, nobs, rw, ct, rows, S, run);
-            gr_stage(P, j, X[j], st, sl, obs, nobs, nullptr, q[j - 1], cd, Gd);
-            for (int i = 0; i < 7 + nobs; ++i) {
-                const int col = mu_list_col(i, nobs);
-                if (rows[col] != rows[col]) nonfinite = true;
-                if (!mu_active(rows[col], active_tol)) continue;
-                if (na < MA) list[na] = (j - 1) * rw + col;
-                ++na;
-            }
+    linearise_one(R, P, N, X, obs, nobs, rw, U, nullptr, rows, L, Gd, [&](int j) {
+        for (int i = 0; i < 7 + nobs; ++i) {
+            const int col = mu_list_col(i, nobs);
+            if (rows[col] != rows[col]) nonfinite = true;
+            if (!mu_active(rows[col], active_tol)) continue;
+            if (na < MA) list[na] = (j - 1) * rw + col;
+            ++na;
         }
-    }
-    double g0x[5], grad[2 * kMaxN];
+    });
+    const double(*A)[5] = L.A, (*q)[5] = L.q;
+    double grad[2 * kMaxN];
     bool fr[2 * kMaxN];
     int nf = 0;
-    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0x);
     for (int k = 0; k < N; ++k) {
         double jt[2];
         gr_control(P, U[2 * k], U[2 * k + 1], q[k], nullptr, grad + 2 * k, jt, Gd);
@@ -1051,8 +1065,8 @@ inline void multipliers_one(const DevTable& R, const mpc_params& p, const double
     if (summary) mu_summary(summary, status, na, nf, nu, resid, minpiv);
 }
 
-// mpc_hessvec_batch for one instance (include/mpcqp.h): the gradient's first phase as above (the rollout's stage
-// data, both reverse sweeps, pi = p - p'), then tracker_model.h's hv_* steps, which mpc_hessvec_kernel
+// mpc_hessvec_batch for one instance (include/mpcqp.h): the linearisation above (the rollout's stage data, both
+// reverse sweeps), pi = p - p', then tracker_model.h's hv_* steps, which mpc_hessvec_kernel
 // (hessvec_kernel.h) runs with a lane per direction, folded here one direction after the other, so every output
 // equals the device's bit for bit.  V [M][N][2] or null (unit directions), HV [M][N][2], JV [M][N][rw], curv [M][2]
 // and summary [MPC_HV_NQ] may be null.
@@ -1062,28 +1076,14 @@ inline void hessvec_one(const DevTable& R, const mpc_params& p, const double (*X
     const int N = p.N;
     const KParams P = model_params(p);
     const bool exact = mode == MPC_HV_EXACT;
-    double ct[kMaxN][5], part[kMaxN], A[kMaxN][5], q[kMaxN][5], c[kMaxN][5], sl[kMaxN + 1][4];
-    EvRun run = ev_run_begin();
+    Linearised L;
     GrRun G = gr_run_begin();
-    for (int k = 0; k < N; ++k) ev_control(P, U[2 * k], U[2 * k + 1], ct[k], run);
-    for (int j = 0; j <= N; ++j) {
-        double st[5];
-        get_state(R, X[j][0], st, sl[j]);
-        if (j < N) stage_A(X[j], P.dt, st[3], sl[j][2], A[j]);
-        if (j >= 1) {
-            EvStage S = ev_stage_begin();
-            ev_stage(P, j, X[j], st, obs, nobs, rw, ct[j - 1], nullptr, S, run);
-            gr_stage(P, j, X[j], st, sl[j], obs, nobs, lam ? lam + (size_t)(j - 1) * rw : nullptr, q[j - 1], c[j - 1], G);
-            part[j - 1] = 0.0;
-        }
-    }
-    double g0[5];
-    gr_sweep(N, P.dt, &A[0][0], &q[0][0], g0);
-    if (lam) {
-        gr_sweep(N, P.dt, &A[0][0], &c[0][0], g0);
+    linearise_one(R, P, N, X, obs, nobs, rw, U, lam, L, G);
+    double(*q)[5] = L.q;
+    const double(*A)[5] = L.A, (*sl)[4] = L.sl;
+    if (lam)
         for (int k = 0; k < N; ++k)
-            for (int a = 0; a < 5; ++a) q[k][a] = q[k][a] - c[k][a];      // pi = p - p'
-    }
+            for (int a = 0; a < 5; ++a) q[k][a] = q[k][a] - L.c[k][a];    // pi = p - p'
     double cvs[MPC_HV_MAX_DIRS][2];
     for (int m = 0; m < M; ++m) {
         const double* Vd = V ? V + (size_t)m * 2 * N : nullptr;
@@ -1125,7 +1125,7 @@ inline void hessvec_one(const DevTable& R, const mpc_params& p, const double (*X
         cvs[m][1] = cv[1];
     }
     if (curv) std::memcpy(curv, cvs, sizeof(double) * 2 * M);
-    if (summary) hv_summary(summary, ev_sums(N, &ct[0][0], part).cost, M, &cvs[0][0]);
+    if (summary) hv_summary(summary, ev_sums(N, &L.ct[0][0], L.part).cost, M, &cvs[0][0]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1277,8 +1277,7 @@ struct Backend {
                      const double* ubar, double* u0, double* U, double* Xpred, int* status, int* iters) const {
         const int N = p.N, mo = obs ? p.max_obs : 0;
         parallel(p, B, [&](Worker& w, int b) {
-            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
-            no = no < 0 ? 0 : (no > mo ? mo : no);
+            const int no = obstacle_count(obs, n_obs, mo, b);
             int it = 0;
             const int st = w.solve(x0 + 5 * (size_t)b, obs ? obs + (size_t)b * mo * 2 : nullptr, no,
                                    ubar ? ubar + (size_t)b * 2 * N : nullptr, u0 ? u0 + 2 * (size_t)b : nullptr,
@@ -1289,22 +1288,38 @@ struct Backend {
         });
     }
 
-    // mpc_evaluate_batch on host buffers (the device entry's argument contract); rows are [B][N][7 + p.max_obs]
-    void evaluate_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
-                        const double* U, double* Xpred, double* summary, double* terms, double* rows) const {
-        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
+    // the obstacle count of instance b as the solver reads it: none without obs, NULL = all max_obs rows, clamped
+    static int obstacle_count(const double* obs, const int* n_obs, int mo, int b) {
+        const int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
+        return no < 0 ? 0 : (no > mo ? mo : no);
+    }
+    // instance b's part of an optional array of `stride` elements per instance
+    template <typename T>
+    static T* at(T* a, int b, size_t stride) { return a ? a + (size_t)b * stride : nullptr; }
+
+    // What the evaluators do per instance (the host twin of evaluator_common.h's evc_instance and evc_rollout): the
+    // obstacle slab and count, the control sequence and the rollout X = predict(x0, U); one(b, X, Ub, obs_b, no)
+    // then computes the entry's outputs of instance b
+    template <typename One>
+    void evaluator_instances(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                             const double* U, One one) const {
+        const int N = p.N, mo = obs ? p.max_obs : 0;
         parallel(p, B, [&](Worker& w, int b) {
-            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
-            no = no < 0 ? 0 : (no > mo ? mo : no);
             double X[kMaxN + 1][5];
             const double* Ub = U + (size_t)b * 2 * N;
             w.predict(x0 + 5 * (size_t)b, Ub, X);
+            one(b, X, Ub, at(obs, b, (size_t)mo * 2), obstacle_count(obs, n_obs, mo, b));
+        });
+    }
+
+    // mpc_evaluate_batch on host buffers (the device entry's argument contract); rows are [B][N][7 + p.max_obs]
+    void evaluate_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
+                        const double* U, double* Xpred, double* summary, double* terms, double* rows) const {
+        const size_t N = p.N, rw = 7 + p.max_obs;
+        evaluator_instances(p, B, x0, obs, n_obs, U, [&](int b, const double (*X)[5], const double* Ub, const double* ob, int no) {
             if (Xpred) std::memcpy(Xpred + (size_t)b * 5 * (N + 1), X, sizeof(double) * 5 * (N + 1));
             if (summary || terms || rows)
-                evaluate_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
-                             summary ? summary + (size_t)b * MPC_EV_NQ : nullptr,
-                             terms ? terms + 5 * (size_t)b : nullptr,
-                             rows ? rows + (size_t)b * N * rw : nullptr);
+                evaluate_one(ref, p, X, ob, no, (int)rw, Ub, at(summary, b, MPC_EV_NQ), at(terms, b, 5), at(rows, b, N * rw));
         });
     }
 
@@ -1312,18 +1327,10 @@ struct Backend {
     void gradient_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
                         const double* U, const double* lam, double* grad, double* jtl, double* gx0, double* costate,
                         double* summary) const {
-        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
-        parallel(p, B, [&](Worker& w, int b) {
-            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
-            no = no < 0 ? 0 : (no > mo ? mo : no);
-            double X[kMaxN + 1][5];
-            const double* Ub = U + (size_t)b * 2 * N;
-            w.predict(x0 + 5 * (size_t)b, Ub, X);
-            gradient_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
-                         lam ? lam + (size_t)b * N * rw : nullptr, grad ? grad + (size_t)b * 2 * N : nullptr,
-                         jtl ? jtl + (size_t)b * 2 * N : nullptr, gx0 ? gx0 + 5 * (size_t)b : nullptr,
-                         costate ? costate + (size_t)b * 5 * N : nullptr,
-                         summary ? summary + (size_t)b * MPC_GR_NQ : nullptr);
+        const size_t N = p.N, rw = 7 + p.max_obs;
+        evaluator_instances(p, B, x0, obs, n_obs, U, [&](int b, const double (*X)[5], const double* Ub, const double* ob, int no) {
+            gradient_one(ref, p, X, ob, no, (int)rw, Ub, at(lam, b, N * rw), at(grad, b, 2 * N), at(jtl, b, 2 * N),
+                         at(gx0, b, 5), at(costate, b, 5 * N), at(summary, b, MPC_GR_NQ));
         });
     }
 
@@ -1331,17 +1338,10 @@ struct Backend {
     void multipliers_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
                            const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
                            int* active, double* summary) const {
-        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
-        parallel(p, B, [&](Worker& w, int b) {
-            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
-            no = no < 0 ? 0 : (no > mo ? mo : no);
-            double X[kMaxN + 1][5];
-            const double* Ub = U + (size_t)b * 2 * N;
-            w.predict(x0 + 5 * (size_t)b, Ub, X);
-            multipliers_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub, active_tol, bound_tol,
-                            rank_tol, lam ? lam + (size_t)b * N * rw : nullptr,
-                            active ? active + (size_t)b * MPC_MAX_ACTIVE : nullptr,
-                            summary ? summary + (size_t)b * MPC_MU_NQ : nullptr);
+        const size_t N = p.N, rw = 7 + p.max_obs;
+        evaluator_instances(p, B, x0, obs, n_obs, U, [&](int b, const double (*X)[5], const double* Ub, const double* ob, int no) {
+            multipliers_one(ref, p, X, ob, no, (int)rw, Ub, active_tol, bound_tol, rank_tol, at(lam, b, N * rw),
+                            at(active, b, MPC_MAX_ACTIVE), at(summary, b, MPC_MU_NQ));
         });
     }
 
@@ -1349,18 +1349,10 @@ struct Backend {
     void hessvec_batch(const mpc_params& p, int B, const double* x0, const double* obs, const int* n_obs,
                        const double* U, const double* lam, int M, const double* V, int mode, double* HV, double* JV,
                        double* curv, double* summary) const {
-        const int N = p.N, mo = obs ? p.max_obs : 0, rw = 7 + p.max_obs;
-        parallel(p, B, [&](Worker& w, int b) {
-            int no = obs ? (n_obs ? n_obs[b] : mo) : 0;
-            no = no < 0 ? 0 : (no > mo ? mo : no);
-            double X[kMaxN + 1][5];
-            const double* Ub = U + (size_t)b * 2 * N;
-            const size_t bm = (size_t)b * M;
-            w.predict(x0 + 5 * (size_t)b, Ub, X);
-            hessvec_one(ref, p, X, obs ? obs + (size_t)b * mo * 2 : nullptr, no, rw, Ub,
-                        lam ? lam + (size_t)b * N * rw : nullptr, M, V ? V + bm * 2 * N : nullptr, mode,
-                        HV ? HV + bm * 2 * N : nullptr, JV ? JV + bm * N * rw : nullptr, curv ? curv + bm * 2 : nullptr,
-                        summary ? summary + (size_t)b * MPC_HV_NQ : nullptr);
+        const size_t N = p.N, rw = 7 + p.max_obs, m = (size_t)M;
+        evaluator_instances(p, B, x0, obs, n_obs, U, [&](int b, const double (*X)[5], const double* Ub, const double* ob, int no) {
+            hessvec_one(ref, p, X, ob, no, (int)rw, Ub, at(lam, b, N * rw), M, at(V, b, m * 2 * N), mode, at(HV, b, m * 2 * N),
+                        at(JV, b, m * N * rw), at(curv, b, m * 2), at(summary, b, MPC_HV_NQ));
         });
     }
 

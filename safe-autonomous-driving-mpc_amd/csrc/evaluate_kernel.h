@@ -3,8 +3,9 @@
 // rows (:155-211) and a per-instance summary of them.  No QP, no solver state.
 //
 // The solver's layout: one lane group of GL lanes per instance (GL = 16, 32, 64 by N + 1, 64 / GL instances per
-// wavefront).  predict_grp rolls the instance out (lane 0 rolls s, k, v; lane j looks the table up at s_j; lane 0
-// rolls d, o) and leaves lane j the whole reference state at s_j, so no table is searched twice.  Lane j = 1..N then
+// wavefront).  The instance is read and rolled out by the shared phase (evaluator_common.h): predict_grp rolls it out
+// (lane 0 rolls s, k, v; lane j looks the table up at s_j; lane 0 rolls d, o) and leaves lane j the whole reference
+// state at s_j, so no table is searched twice.  Lane j = 1..N then
 // owns stage j (its three cost terms, its 7 + n_obs rows, written straight to its slice of `rows`) and lane
 // j = 0..N-1 owns control j (its two cost terms, its box excess).  Minima and counts go through Grp<GL>; the two
 // sums whose bits must not depend on GL, the running cost and the L1 violation, are added by lane 0 from LDS in the
@@ -16,7 +17,7 @@
 // control j.  Until the rollout's first phase is over ct also stages U for lane 0.  The array is static, sized for
 // the longest horizon of the lane group (N = GL - 1): 5.4 - 5.5 KB per wavefront for every GL.
 #pragma once
-#include "device_common.h"
+#include "evaluator_common.h"
 
 __host__ __device__ constexpr int ev_lds_doubles(int N) { return (11 * N + 6 + 1) & ~1; }
 
@@ -37,45 +38,26 @@ mpc_evaluate_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __res
                                      // wave_sync); it writes nothing
     const Grp<GL> Q{grp * GL};
     const int N = Pr.N, NP = N + 1;
-    const double dt = Pr.dt;
     double* Xr = smem + grp * LD;
     double* kap = Xr + 5 * NP;
     double* ct = kap + NP;
     const double inf = __builtin_inf(), qnan = __builtin_nan("");
 
-    double x0[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) x0[j] = x0g[5 * (size_t)b + j];
-    // the obstacle count as the solver reads it: NULL = all max_obs rows, clamped to [0, max_obs]
-    int nobs = 0;
-    const double* obs = nullptr;
-    if (OBS) {
-        nobs = nobsg ? nobsg[b] : Pr.max_obs;
-        nobs = nobs < 0 ? 0 : (nobs > Pr.max_obs ? Pr.max_obs : nobs);
-        obs = obsg + (size_t)b * Pr.max_obs * 2;
-    }
-
-    const bool ctrl = gl < N;                  // this lane owns control gl
-    const bool stage = gl >= 1 && gl <= N;     // this lane owns stage gl
-    double u1 = 0.0, u2 = 0.0;
-    if (ctrl) {
-        u1 = Ug[(size_t)b * 2 * N + 2 * gl];
-        u2 = Ug[(size_t)b * 2 * N + 2 * gl + 1];
-        ct[2 * gl] = u1;
-        ct[2 * gl + 1] = u2;
-    }
-    wave_sync();
-    double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    predict_grp(tab, N, dt, x0, ct, Xr, kap, gl, st, nullptr);
-    // lane 0 read U from ct before predict_grp's first barrier; ct and kap are free from here on
+    // ---- the shared phase (evaluator_common.h): the instance and its rollout; U is staged in ct ----
+    const EvcLds L{Xr, kap, ct, nullptr, nullptr, nullptr};
+    EvcInst I;
+    evc_instance<OBS>(Pr, b, x0g, obsg, nobsg, I);
+    evc_rollout<false>(tab, Pr, b, gl, Ug, ct, L, I);
+    const bool stage = I.stage;
+    const int nobs = I.nobs;
 
     // ---- control gl (cost terms, box excess), then stage gl (cost terms and rows): tracker_model.h's steps ----
     EvRun run = ev_run_begin();
-    if (ctrl) ev_control(Pr, u1, u2, ct + 5 * gl, run);
+    if (I.ctrl) ev_control(Pr, I.u1, I.u2, ct + 5 * gl, run);
     EvStage S = ev_stage_begin();
     if (stage) {
         double* ro = bvalid && rowg ? rowg + ((size_t)b * N + (gl - 1)) * rw : nullptr;
-        ev_stage(Pr, gl, Xr + 5 * gl, st, obs, nobs, rw, ct + 5 * (gl - 1), ro, S, run);
+        ev_stage(Pr, gl, Xr + 5 * gl, I.st, I.obs, nobs, rw, ct + 5 * (gl - 1), ro, S, run);
         kap[gl - 1] = S.p1;
     }
 

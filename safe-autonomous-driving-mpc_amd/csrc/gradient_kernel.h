@@ -3,11 +3,12 @@
 // the rollout predict(x0, U).  No QP, no solver state.
 //
 // The evaluator's layout (evaluate_kernel.h): one lane group of GL lanes per instance (GL = 16, 32, 64 by N + 1,
-// 64 / GL instances per wavefront).  predict_grp rolls the instance out and leaves lane j the reference state at
-// s_j and its slopes.  Lane j = 0..N-1 then owns control j and the coefficients of A_j (stage_A), lane j = 1..N
-// owns stage j: its cost terms, its stage gradient q_j and its weighted row gradient c_j, parked in LDS.  The two
-// reverse recursions are sequential chains of N short steps: lane 0 runs the cost's and lane 1 the rows' in lock
-// step, in place in LDS (q becomes the costate p, c becomes p'), which fixes the order of every addition.  Lane j
+// 64 / GL instances per wavefront).  Everything up to the costates is the shared phase (evaluator_common.h):
+// predict_grp rolls the instance out and leaves lane j the reference state at s_j and its slopes.  Lane j = 0..N-1
+// then owns control j and the coefficients of A_j (stage_A), lane j = 1..N owns stage j: its cost terms, its stage
+// gradient q_j and its weighted row gradient c_j, parked in LDS.  The two reverse recursions are sequential chains
+// of N short steps: lane 0 runs the cost's and lane 1 the rows' in lock step, in place in LDS (q becomes the
+// costate p, c becomes p'), which fixes the order of every addition.  Lane j
 // then reads p_j+1 and p'_j+1 and writes grad[j] and jtl[j]; the extremes go through Grp<GL>, and the cost is
 // added by lane 0 from LDS in the evaluator's order (ev_sums).  The steps are tracker_model.h's, which the host
 // backend's gradient_one (cpu_backend.h) folds sequentially: the two agree bit for bit.
@@ -17,7 +18,7 @@
 // first phase is over it also stages U for lane 0), A [N][5], q [N][5] and c [N][5].  The array is static, sized
 // for the longest horizon of the lane group (N = GL - 1): 12.4 - 12.9 KB per wavefront for every GL.
 #pragma once
-#include "device_common.h"
+#include "evaluator_common.h"
 
 __host__ __device__ constexpr int gr_lds_doubles(int N) { return (26 * N + 6 + 1) & ~1; }
 
@@ -40,7 +41,6 @@ mpc_gradient_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __res
                                      // wave_sync); it writes nothing
     const Grp<GL> Q{grp * GL};
     const int N = Pr.N, NP = N + 1;
-    const double dt = Pr.dt;
     double* Xr = smem + grp * LD;
     double* kap = Xr + 5 * NP;
     double* ct = kap + NP;
@@ -50,63 +50,22 @@ mpc_gradient_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __res
     const double qnan = __builtin_nan("");
     const bool has_lam = lamg != nullptr;
 
-    double x0[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) x0[j] = x0g[5 * (size_t)b + j];
-    // the obstacle count as the solver reads it: NULL = all max_obs rows, clamped to [0, max_obs]
-    int nobs = 0;
-    const double* obs = nullptr;
-    if (OBS) {
-        nobs = nobsg ? nobsg[b] : Pr.max_obs;
-        nobs = nobs < 0 ? 0 : (nobs > Pr.max_obs ? Pr.max_obs : nobs);
-        obs = obsg + (size_t)b * Pr.max_obs * 2;
-    }
-
-    const bool ctrl = gl < N;                  // this lane owns control gl and A_gl
-    const bool stage = gl >= 1 && gl <= N;     // this lane owns stage gl
-    double u1 = 0.0, u2 = 0.0;
-    if (ctrl) {
-        u1 = Ug[(size_t)b * 2 * N + 2 * gl];
-        u2 = Ug[(size_t)b * 2 * N + 2 * gl + 1];
-        ct[2 * gl] = u1;
-        ct[2 * gl + 1] = u2;
-    }
-    wave_sync();
-    double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, sl[4] = {0.0, 0.0, 0.0, 0.0};
-    predict_grp(tab, N, dt, x0, ct, Xr, kap, gl, st, sl);
-    // lane 0 read U from ct before predict_grp's first barrier; ct and kap are free from here on
-
-    // ---- control gl (cost terms) and A_gl, then stage gl (cost terms, q, c): tracker_model.h's steps ----
+    // ---- the shared phase (evaluator_common.h): the instance, its rollout (U is staged in ct), the linearisation
+    // (cost terms, A, q, c) and the reverse sweeps, lane 0 the cost's and lane 1 the rows', in place ----
+    const EvcLds L{Xr, kap, ct, As, qs, cs};
+    EvcInst I;
+    evc_instance<OBS>(Pr, b, x0g, obsg, nobsg, I);
+    evc_rollout<true>(tab, Pr, b, gl, Ug, ct, L, I);
     EvRun run = ev_run_begin();
     GrRun gr = gr_run_begin();
-    if (ctrl) {
-        ev_control(Pr, u1, u2, ct + 5 * gl, run);
-        stage_A(Xr + 5 * gl, dt, st[3], sl[2], As + 5 * gl);
-    }
-    if (stage) {
-        EvStage S = ev_stage_begin();
-        ev_stage(Pr, gl, Xr + 5 * gl, st, obs, nobs, rw, ct + 5 * (gl - 1), nullptr, S, run);
-        const double* lam = has_lam ? lamg + ((size_t)b * N + (gl - 1)) * rw : nullptr;
-        gr_stage(Pr, gl, Xr + 5 * gl, st, sl, obs, nobs, lam, qs + 5 * (gl - 1), cs + 5 * (gl - 1), gr);
-        kap[gl - 1] = 0.0;
-    }
-    wave_sync();
-
-    // ---- the reverse sweeps: lane 0 the cost's, lane 1 the rows', in place ----
-    if (gl == 0 || (gl == 1 && has_lam)) {
-        double g0[5];
-        gr_sweep(N, dt, As, gl == 0 ? qs : cs, g0);
-        if (bvalid && gl == 0 && gx0g) {
-#pragma unroll
-            for (int a = 0; a < 5; ++a) gx0g[(size_t)b * 5 + a] = g0[a];
-        }
-    }
+    evc_linearise<true, true>(Pr, b, rw, gl, L, I, lamg, nullptr, run, gr);
+    evc_sweeps(N, Pr.dt, gl, L, has_lam, bvalid && gx0g ? gx0g + (size_t)b * 5 : nullptr);
     wave_sync();
 
     // ---- control gl: its gradient and J' lam from p_gl+1, p'_gl+1 ----
-    if (ctrl) {
+    if (I.ctrl) {
         double g[2], jt[2];
-        gr_control(Pr, u1, u2, qs + 5 * gl, has_lam ? cs + 5 * gl : nullptr, g, jt, gr);
+        gr_control(Pr, I.u1, I.u2, qs + 5 * gl, has_lam ? cs + 5 * gl : nullptr, g, jt, gr);
         if (bvalid && gradg) {
             gradg[(size_t)b * 2 * N + 2 * gl] = g[0];
             gradg[(size_t)b * 2 * N + 2 * gl + 1] = g[1];

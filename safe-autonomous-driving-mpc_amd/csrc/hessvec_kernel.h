@@ -2,10 +2,10 @@
 // any control sequence U and M directions v, (d2 L / dU2) v and J v, by one forward tangent chain and one second-order
 // reverse chain per direction over the rollout predict(x0, U).  No QP, no solver state.
 //
-// One wavefront per instance.  Phase 1 is the gradient kernel's own on lanes 0..N (gradient_kernel.h with one group
-// of 64 lanes): predict_grp rolls the instance out, lane j = 0..N-1 owns control j and A_j, lane j = 1..N owns stage j
-// (cost terms, q_j, c_j), lanes 0 and 1 run the two reverse sweeps in place, and the Lagrangian costate
-// pi = p - p' replaces q.  It leaves X, A, the slopes and pi in LDS.
+// One wavefront per instance.  Phase 1 is the shared phase (evaluator_common.h) on lanes 0..N, as in
+// gradient_kernel.h with one group of 64 lanes: predict_grp rolls the instance out, lane j = 0..N-1 owns control j
+// and A_j, lane j = 1..N owns stage j (cost terms, q_j, c_j), lanes 0 and 1 run the two reverse sweeps in place, and
+// the Lagrangian costate pi = p - p' replaces q.  It leaves X, A, the slopes and pi in LDS.
 //
 // Phase 2 runs in passes of W = hv_pass_width(N) directions: lane m owns direction pass * W + m and runs its chains
 // alone, so the order of every addition is the header's and does not depend on what the other lanes carry.  The
@@ -24,7 +24,7 @@
 // N <= MPC_HV_N64_MAX = 56, where that still fits the 160 KiB of a CU, and 32 beyond:
 //   N = 20, W = 64:  58.9 KB (two workgroups per CU)     N = 56, W = 64: 161.2 KB     N = 63, W = 32: 100.4 KB
 #pragma once
-#include "device_common.h"
+#include "evaluator_common.h"
 
 __host__ __device__ constexpr int hv_inst_doubles(int N) { return 30 * N + 10 + 2 * MPC_HV_MAX_DIRS; }
 __host__ __device__ constexpr int hv_lds_doubles(int N, int W) { return hv_inst_doubles(N) + 5 * N * (W + 1); }
@@ -55,54 +55,20 @@ mpc_hessvec_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __rest
     const bool has_lam = lamg != nullptr;
     const bool exact = mode == MPC_HV_EXACT;
 
-    double x0[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) x0[j] = x0g[5 * (size_t)b + j];
-    // the obstacle count as the solver reads it: NULL = all max_obs rows, clamped to [0, max_obs]
-    int nobs = 0;
-    const double* obs = nullptr;
-    if (OBS) {
-        nobs = nobsg ? nobsg[b] : Pr.max_obs;
-        nobs = nobs < 0 ? 0 : (nobs > Pr.max_obs ? Pr.max_obs : nobs);
-        obs = obsg + (size_t)b * Pr.max_obs * 2;
-    }
-
-    // ---- phase 1: the gradient kernel's, on lanes 0..N ----
-    const bool ctrl = ln < N;                  // this lane owns control ln and A_ln
-    const bool stage = ln >= 1 && ln <= N;     // this lane owns stage ln
-    double u1 = 0.0, u2 = 0.0;
-    if (ctrl) {
-        u1 = Ug[(size_t)b * n2 + 2 * ln];
-        u2 = Ug[(size_t)b * n2 + 2 * ln + 1];
-        ct[2 * ln] = u1;
-        ct[2 * ln + 1] = u2;
-    }
-    wave_sync();
-    double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, sl[4] = {0.0, 0.0, 0.0, 0.0};
-    predict_grp(tab, N, dt, x0, ct, Xr, kap, ln, st, sl);
-    // lane 0 read U from ct before predict_grp's first barrier; ct and kap are free from here on
+    // ---- phase 1: the shared phase (evaluator_common.h) on lanes 0..N, U staged in ct; the slopes are kept ----
+    const EvcLds L{Xr, kap, ct, As, qs, cs};
+    EvcInst I;
+    evc_instance<OBS>(Pr, b, x0g, obsg, nobsg, I);
+    evc_rollout<true>(tab, Pr, b, ln, Ug, ct, L, I);
+    const int nobs = I.nobs;
     EvRun run = ev_run_begin();
     GrRun gr = gr_run_begin();
     if (ln <= N) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) sls[4 * ln + a] = sl[a];
+        for (int a = 0; a < 4; ++a) sls[4 * ln + a] = I.sl[a];
     }
-    if (ctrl) {
-        ev_control(Pr, u1, u2, ct + 5 * ln, run);
-        stage_A(Xr + 5 * ln, dt, st[3], sl[2], As + 5 * ln);
-    }
-    if (stage) {
-        EvStage S = ev_stage_begin();
-        ev_stage(Pr, ln, Xr + 5 * ln, st, obs, nobs, rw, ct + 5 * (ln - 1), nullptr, S, run);
-        const double* lam = has_lam ? lamg + ((size_t)b * N + (ln - 1)) * rw : nullptr;
-        gr_stage(Pr, ln, Xr + 5 * ln, st, sl, obs, nobs, lam, qs + 5 * (ln - 1), cs + 5 * (ln - 1), gr);
-        kap[ln - 1] = 0.0;
-    }
-    wave_sync();
-    if (ln == 0 || (ln == 1 && has_lam)) {
-        double g0[5];
-        gr_sweep(N, dt, As, ln == 0 ? qs : cs, g0);
-    }
+    evc_linearise<true, true>(Pr, b, rw, ln, L, I, lamg, nullptr, run, gr);
+    evc_sweeps(N, dt, ln, L, has_lam, nullptr);
     wave_sync();
     if (has_lam)
         for (int i = ln; i < 5 * N; i += WAVE) qs[i] = qs[i] - cs[i];      // pi = p - p'

@@ -28,6 +28,7 @@
 //   noise_kernels.h        the disturbance sweeps' Philox source, measure / plant / draw kernels
 //   trace_kernels.h        the plan traces' gap and history kernels (the solver's U / Xpred of every step)
 //   warm_kernels.h         the warm starts' carry and keep kernels (the previous plan as the next ubar)
+//   evaluator_common.h     the phase the four batched evaluators below share: instance, rollout, linearisation
 //   evaluate_kernel.h      the batched evaluator of the reference's cost and constraint rows
 //   gradient_kernel.h      the batched gradients of that cost and of those rows (reverse sweeps)
 //   hessvec_kernel.h       the batched Hessian-vector products and row tangents (a lane per direction)
@@ -522,200 +523,209 @@ static int staged_call(mpc_ctx* c, const char* no_memory, Bind&& bindings, Call&
     return MPC_SUCCESS;
 }
 
+// The inputs the batch entries share, bound to a host entry's arena: x0 [B][5], obs [B][max_obs][2], n_obs [B] (it
+// travels only with obs), U [B][N][2] (the solver's ubar) and lam [B][N][7 + max_obs]; a null array stays null
+struct BatchInputs {
+    double *x0, *obs;
+    int* n_obs;
+    double *U, *lam;
+};
+static BatchInputs stage_inputs(staging::Staging& S, const mpc_ctx* c, int B, const double* x0, const double* obs,
+                                const int* n_obs, const double* U, const double* lam) {
+    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+    BatchInputs d;
+    d.x0 = S.in(x0, nb * 5);
+    d.obs = S.in(obs, nb * mo * 2);
+    d.n_obs = obs ? S.in(n_obs, nb) : nullptr;
+    d.U = S.in(U, nb * N * 2);
+    d.lam = S.in(lam, nb * N * (7 + mo));
+    return d;
+}
+
 extern "C" int mpc_solve_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                const double* ubar, double* u0, double* U, double* Xpred, int* status, int* iters) {
     int rc = solve_args(c, B, x0, obs);
     if (rc || B == 0) return rc;
     if (c->cpu) return host_call([&] { c->cpu->solve_batch(c->p, B, x0, obs, n_obs, ubar, u0, U, Xpred, status, iters); });
     HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
-    double *d_x0, *d_obs, *d_ub, *d_u0, *d_U, *d_X;
-    int *d_nobs, *d_status, *d_iters;
-    // n_obs travels only with obs; the kernel writes all five outputs, asked for or not
+    const size_t nb = (size_t)B, N = (size_t)c->p.N;
+    BatchInputs d;
+    double *d_u0, *d_U, *d_X;
+    int *d_status, *d_iters;
+    // the kernel writes all five outputs, asked for or not
     return staged_call(c, "hipMalloc staging", [&](staging::Staging& S) {
-        d_x0 = S.in(x0, nb * 5);
-        d_obs = S.in(obs, nb * mo * 2);
-        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
-        d_ub = S.in(ubar, nb * N * 2);
+        d = stage_inputs(S, c, B, x0, obs, n_obs, ubar, nullptr);
         d_u0 = S.out_or_scratch(u0, nb * 2);
         d_U = S.out_or_scratch(U, nb * N * 2);
         d_X = S.out_or_scratch(Xpred, nb * (N + 1) * 5);
         d_status = S.out_or_scratch(status, nb);
         d_iters = S.out_or_scratch(iters, nb);
     }, [&] {
-        return mpc_solve_batch_device(c, B, d_x0, d_obs, d_nobs, d_ub, d_u0, d_U, d_X, d_status, d_iters, (void*)c->stream);
+        return mpc_solve_batch_device(c, B, d.x0, d.obs, d.n_obs, d.U, d_u0, d_U, d_X, d_status, d_iters, (void*)c->stream);
     });
 }
 
 // ------------------------------------------------------------------------------------------
-// batched evaluator (evaluate_kernel.h)
+// the batched evaluators (evaluator_common.h and the four kernels over it).  A host / device pair is one *_entry
+// function, which states the pair's own parts once and hands them to evaluator_entry: the pair's checks (rc), the
+// double arrays whose addresses a device call must have aligned, whether any output is asked for, the call of the host
+// backend, the launch, and for the host entry (staged) its arena bindings and the call of itself on the device arrays.
+// The order of a device entry: the shared checks and B == 0, device_args, no output asked for, a device = -1
+// context's host backend, then the kernel's parameters (obstacle rows exist only when obstacles are passed; rw, the
+// width of rows / lam / JV, keeps the context's slab width without them too), the device, the launch.  A host entry
+// skips device_args and the launch: it stages its arrays and calls the device entry on the context's stream.
 // ------------------------------------------------------------------------------------------
+template <typename Host, typename Launch, typename Bind, typename Device>
+static int evaluator_entry(mpc_ctx* c, int B, int rc, bool staged, const double* obs, const int* n_obs,
+                           std::initializer_list<const double*> arrays, bool wanted, const char* no_memory, Host&& host,
+                           Launch&& launch, Bind&& bindings, Device&& device_entry) {
+    if (rc || B == 0) return rc;
+    if (!staged && (rc = device_args(c, obs, n_obs, arrays))) return rc;
+    if (!wanted) return MPC_SUCCESS;
+    if (c->cpu) return host_call(host);
+    if (staged) {
+        HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+        return staged_call(c, no_memory, bindings, device_entry);
+    }
+    KParams kp = kparams(&c->p);
+    const int rw = 7 + c->p.max_obs;
+    if (!obs) kp.max_obs = 0;
+    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
+    launch(kp, rw, obs ? n_obs : nullptr);
+    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
+    return MPC_SUCCESS;
+}
+
+// batched evaluator (evaluate_kernel.h)
+static int evaluate_entry(mpc_ctx* c, bool staged, int B, const double* x0, const double* obs, const int* n_obs,
+                          const double* U, double* Xpred, double* summary, double* terms, double* rows, void* stream) {
+    BatchInputs d;
+    double *d_X, *d_sum, *d_terms, *d_rows;
+    return evaluator_entry(
+        c, B, evaluate_args(c, B, x0, obs, U), staged, obs, n_obs, {x0, obs, U, Xpred, summary, terms, rows},
+        Xpred || summary || terms || rows, "hipMalloc evaluator staging",
+        [&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); },
+        [&](const KParams& kp, int rw, const int* nob) {
+            const int GL = lane_group(kp.N);
+            for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
+                hipLaunchKernelGGL((mpc_evaluate_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL),
+                                   dim3(WAVE), 0, (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, nob, U, Xpred, summary,
+                                   terms, rows);
+            });
+        },
+        [&](staging::Staging& S) {
+            const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+            d = stage_inputs(S, c, B, x0, obs, n_obs, U, nullptr);
+            d_X = S.out(Xpred, nb * (N + 1) * 5);
+            d_sum = S.out(summary, nb * MPC_EV_NQ);
+            d_terms = S.out(terms, nb * 5);
+            d_rows = S.out(rows, nb * N * (7 + mo));
+        },
+        [&] { return evaluate_entry(c, false, B, d.x0, d.obs, d.n_obs, d.U, d_X, d_sum, d_terms, d_rows, (void*)c->stream); });
+}
+
 extern "C" int mpc_evaluate_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                          const double* U, double* Xpred, double* summary, double* terms,
                                          double* rows, void* stream) {
-    int rc = evaluate_args(c, B, x0, obs, U);
-    if (rc || B == 0) return rc;
-    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, Xpred, summary, terms, rows}))) return rc;
-    if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); });
-    KParams kp = kparams(&c->p);
-    const int rw = 7 + c->p.max_obs;       // the row width keeps the context's slab width without obstacles too
-    if (!obs) kp.max_obs = 0;
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const int GL = lane_group(kp.N);
-    for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
-        hipLaunchKernelGGL((mpc_evaluate_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL), dim3(WAVE), 0,
-                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, Xpred, summary, terms,
-                           rows);
-    });
-    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
-    return MPC_SUCCESS;
+    return evaluate_entry(c, false, B, x0, obs, n_obs, U, Xpred, summary, terms, rows, stream);
 }
 
 extern "C" int mpc_evaluate_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                   const double* U, double* Xpred, double* summary, double* terms, double* rows) {
-    int rc = evaluate_args(c, B, x0, obs, U);
-    if (rc || B == 0) return rc;
-    if (!Xpred && !summary && !terms && !rows) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] { c->cpu->evaluate_batch(c->p, B, x0, obs, n_obs, U, Xpred, summary, terms, rows); });
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
-    double *d_x0, *d_obs, *d_U, *d_X, *d_sum, *d_terms, *d_rows;
-    int* d_nobs;
-    return staged_call(c, "hipMalloc evaluator staging", [&](staging::Staging& S) {
-        d_x0 = S.in(x0, nb * 5);
-        d_obs = S.in(obs, nb * mo * 2);
-        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
-        d_U = S.in(U, nb * N * 2);
-        d_X = S.out(Xpred, nb * (N + 1) * 5);
-        d_sum = S.out(summary, nb * MPC_EV_NQ);
-        d_terms = S.out(terms, nb * 5);
-        d_rows = S.out(rows, nb * N * (7 + mo));
-    }, [&] {
-        return mpc_evaluate_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_X, d_sum, d_terms, d_rows, (void*)c->stream);
-    });
+    return evaluate_entry(c, true, B, x0, obs, n_obs, U, Xpred, summary, terms, rows, nullptr);
 }
 
-// ------------------------------------------------------------------------------------------
 // batched gradients (gradient_kernel.h)
-// ------------------------------------------------------------------------------------------
+static int gradient_entry(mpc_ctx* c, bool staged, int B, const double* x0, const double* obs, const int* n_obs,
+                          const double* U, const double* lam, double* grad, double* jtl, double* gx0, double* costate,
+                          double* summary, void* stream) {
+    BatchInputs d;
+    double *d_grad, *d_jtl, *d_gx0, *d_cos, *d_sum;
+    return evaluator_entry(
+        c, B, gradient_args(c, B, x0, obs, U, lam, jtl), staged, obs, n_obs,
+        {x0, obs, U, lam, grad, jtl, gx0, costate, summary}, grad || jtl || gx0 || costate || summary,
+        "hipMalloc gradient staging",
+        [&] { c->cpu->gradient_batch(c->p, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary); },
+        [&](const KParams& kp, int rw, const int* nob) {
+            const int GL = lane_group(kp.N);
+            for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
+                hipLaunchKernelGGL((mpc_gradient_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL),
+                                   dim3(WAVE), 0, (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, nob, U, lam, grad, jtl,
+                                   gx0, costate, summary);
+            });
+        },
+        [&](staging::Staging& S) {
+            const size_t nb = (size_t)B, N = (size_t)c->p.N;
+            d = stage_inputs(S, c, B, x0, obs, n_obs, U, lam);
+            d_grad = S.out(grad, nb * N * 2);
+            d_jtl = S.out(jtl, nb * N * 2);
+            d_gx0 = S.out(gx0, nb * 5);
+            d_cos = S.out(costate, nb * N * 5);
+            d_sum = S.out(summary, nb * MPC_GR_NQ);
+        },
+        [&] {
+            return gradient_entry(c, false, B, d.x0, d.obs, d.n_obs, d.U, d.lam, d_grad, d_jtl, d_gx0, d_cos, d_sum,
+                                  (void*)c->stream);
+        });
+}
+
 extern "C" int mpc_gradient_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                          const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                                          double* costate, double* summary, void* stream) {
-    int rc = gradient_args(c, B, x0, obs, U, lam, jtl);
-    if (rc || B == 0) return rc;
-    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, grad, jtl, gx0, costate, summary}))) return rc;
-    if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->gradient_batch(c->p, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary);
-        });
-    KParams kp = kparams(&c->p);
-    const int rw = 7 + c->p.max_obs;       // lam keeps the context's slab width without obstacles too
-    if (!obs) kp.max_obs = 0;
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const int GL = lane_group(kp.N);
-    for_gl_obs(GL, obs != nullptr, [&](auto gl, auto ob) {
-        hipLaunchKernelGGL((mpc_gradient_kernel<decltype(gl)::value, decltype(ob)::value>), group_grid(B, GL), dim3(WAVE), 0,
-                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, lam, grad, jtl, gx0,
-                           costate, summary);
-    });
-    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
-    return MPC_SUCCESS;
+    return gradient_entry(c, false, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary, stream);
 }
 
 extern "C" int mpc_gradient_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                   const double* U, const double* lam, double* grad, double* jtl, double* gx0,
                                   double* costate, double* summary) {
-    int rc = gradient_args(c, B, x0, obs, U, lam, jtl);
-    if (rc || B == 0) return rc;
-    if (!grad && !jtl && !gx0 && !costate && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->gradient_batch(c->p, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary);
-        });
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
-    double *d_x0, *d_obs, *d_U, *d_lam, *d_grad, *d_jtl, *d_gx0, *d_cos, *d_sum;
-    int* d_nobs;
-    return staged_call(c, "hipMalloc gradient staging", [&](staging::Staging& S) {
-        d_x0 = S.in(x0, nb * 5);
-        d_obs = S.in(obs, nb * mo * 2);
-        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
-        d_U = S.in(U, nb * N * 2);
-        d_lam = S.in(lam, nb * N * (7 + mo));
-        d_grad = S.out(grad, nb * N * 2);
-        d_jtl = S.out(jtl, nb * N * 2);
-        d_gx0 = S.out(gx0, nb * 5);
-        d_cos = S.out(costate, nb * N * 5);
-        d_sum = S.out(summary, nb * MPC_GR_NQ);
-    }, [&] {
-        return mpc_gradient_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_lam, d_grad, d_jtl, d_gx0, d_cos, d_sum,
-                                         (void*)c->stream);
-    });
+    return gradient_entry(c, true, B, x0, obs, n_obs, U, lam, grad, jtl, gx0, costate, summary, nullptr);
 }
 
-// ------------------------------------------------------------------------------------------
 // batched multiplier estimates (multiplier_kernel.h)
-// ------------------------------------------------------------------------------------------
+static int multipliers_entry(mpc_ctx* c, bool staged, int B, const double* x0, const double* obs, const int* n_obs,
+                             const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
+                             int* active, double* summary, void* stream) {
+    BatchInputs d;
+    double *d_lam, *d_sum;
+    int* d_act;
+    return evaluator_entry(
+        c, B, multipliers_args(c, B, x0, obs, U, active_tol, bound_tol, rank_tol), staged, obs, n_obs,
+        {x0, obs, U, lam, summary}, lam || active || summary, "hipMalloc multiplier staging",
+        [&] { c->cpu->multipliers_batch(c->p, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary); },
+        [&](const KParams& kp, int rw, const int* nob) {
+            // one wavefront per instance; the lane-group class of N sizes the kernel's LDS
+            for_gl_obs(lane_group(kp.N), obs != nullptr, [&](auto gl, auto ob) {
+                hipLaunchKernelGGL((mpc_multipliers_kernel<decltype(gl)::value, decltype(ob)::value>), dim3(B), dim3(WAVE),
+                                   0, (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, nob, U, active_tol, bound_tol,
+                                   rank_tol, lam, active, summary);
+            });
+        },
+        [&](staging::Staging& S) {
+            const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
+            d = stage_inputs(S, c, B, x0, obs, n_obs, U, nullptr);
+            d_lam = S.out(lam, nb * N * (7 + mo));
+            d_act = S.out(active, nb * MPC_MAX_ACTIVE);
+            d_sum = S.out(summary, nb * MPC_MU_NQ);
+        },
+        [&] {
+            return multipliers_entry(c, false, B, d.x0, d.obs, d.n_obs, d.U, active_tol, bound_tol, rank_tol, d_lam, d_act,
+                                     d_sum, (void*)c->stream);
+        });
+}
+
 extern "C" int mpc_multipliers_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                             const double* U, double active_tol, double bound_tol, double rank_tol,
                                             double* lam, int* active, double* summary, void* stream) {
-    int rc = multipliers_args(c, B, x0, obs, U, active_tol, bound_tol, rank_tol);
-    if (rc || B == 0) return rc;
-    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, summary}))) return rc;
-    if (!lam && !active && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->multipliers_batch(c->p, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary);
-        });
-    KParams kp = kparams(&c->p);
-    const int rw = 7 + c->p.max_obs;       // lam keeps the context's slab width without obstacles too
-    if (!obs) kp.max_obs = 0;
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    // one wavefront per instance; the lane-group class of N sizes the kernel's LDS
-    for_gl_obs(lane_group(kp.N), obs != nullptr, [&](auto gl, auto ob) {
-        hipLaunchKernelGGL((mpc_multipliers_kernel<decltype(gl)::value, decltype(ob)::value>), dim3(B), dim3(WAVE), 0,
-                           (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, active_tol, bound_tol,
-                           rank_tol, lam, active, summary);
-    });
-    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
-    return MPC_SUCCESS;
+    return multipliers_entry(c, false, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary, stream);
 }
 
 extern "C" int mpc_multipliers_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                      const double* U, double active_tol, double bound_tol, double rank_tol, double* lam,
                                      int* active, double* summary) {
-    int rc = multipliers_args(c, B, x0, obs, U, active_tol, bound_tol, rank_tol);
-    if (rc || B == 0) return rc;
-    if (!lam && !active && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->multipliers_batch(c->p, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary);
-        });
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs;
-    double *d_x0, *d_obs, *d_U, *d_lam, *d_sum;
-    int *d_nobs, *d_act;
-    return staged_call(c, "hipMalloc multiplier staging", [&](staging::Staging& S) {
-        d_x0 = S.in(x0, nb * 5);
-        d_obs = S.in(obs, nb * mo * 2);
-        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
-        d_U = S.in(U, nb * N * 2);
-        d_lam = S.out(lam, nb * N * (7 + mo));
-        d_act = S.out(active, nb * MPC_MAX_ACTIVE);
-        d_sum = S.out(summary, nb * MPC_MU_NQ);
-    }, [&] {
-        return mpc_multipliers_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, active_tol, bound_tol, rank_tol, d_lam, d_act,
-                                            d_sum, (void*)c->stream);
-    });
+    return multipliers_entry(c, true, B, x0, obs, n_obs, U, active_tol, bound_tol, rank_tol, lam, active, summary, nullptr);
 }
 
-// ------------------------------------------------------------------------------------------
 // batched Hessian-vector products and row tangents (hessvec_kernel.h)
-// ------------------------------------------------------------------------------------------
 static int hessvec_args(mpc_ctx* c, int B, const double* x0, const double* obs, const double* U, int M, const double* V,
                         int mode) {
     int rc = batch_args(c, B, x0, obs, U ? nullptr : "U is NULL (the Hessian needs the control sequence to differentiate at)");
@@ -727,62 +737,51 @@ static int hessvec_args(mpc_ctx* c, int B, const double* x0, const double* obs, 
     return MPC_SUCCESS;
 }
 
+static int hessvec_entry(mpc_ctx* c, bool staged, int B, const double* x0, const double* obs, const int* n_obs,
+                         const double* U, const double* lam, int M, const double* V, int mode, double* HV, double* JV,
+                         double* curv, double* summary, void* stream) {
+    BatchInputs d;
+    double *d_V, *d_HV, *d_JV, *d_curv, *d_sum;
+    return evaluator_entry(
+        c, B, hessvec_args(c, B, x0, obs, U, M, V, mode), staged, obs, n_obs, {x0, obs, U, lam, V, HV, JV, curv, summary},
+        HV || JV || curv || summary, "hipMalloc hessvec staging",
+        [&] { c->cpu->hessvec_batch(c->p, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary); },
+        [&](const KParams& kp, int rw, const int* nob) {
+            // one wavefront per instance; the pass width and the actual N size its LDS
+            const int W = hv_pass_width(kp.N);
+            const size_t lds = sizeof(double) * (size_t)hv_lds_doubles(kp.N, W);
+            for_gl_obs(W, obs != nullptr, [&](auto w, auto ob) {
+                constexpr int WV = decltype(w)::value == 32 ? 32 : 64;
+                hipLaunchKernelGGL((mpc_hessvec_kernel<WV, decltype(ob)::value>), dim3(B), dim3(WAVE), lds,
+                                   (hipStream_t)stream, c->tab, kp, B, rw, x0, obs, nob, U, lam, M, V, mode, HV, JV, curv,
+                                   summary);
+            });
+        },
+        [&](staging::Staging& S) {
+            const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs, nm = nb * (size_t)M;
+            d = stage_inputs(S, c, B, x0, obs, n_obs, U, lam);
+            d_V = S.in(V, nm * N * 2);
+            d_HV = S.out(HV, nm * N * 2);
+            d_JV = S.out(JV, nm * N * (7 + mo));
+            d_curv = S.out(curv, nm * 2);
+            d_sum = S.out(summary, nb * MPC_HV_NQ);
+        },
+        [&] {
+            return hessvec_entry(c, false, B, d.x0, d.obs, d.n_obs, d.U, d.lam, M, d_V, mode, d_HV, d_JV, d_curv, d_sum,
+                                 (void*)c->stream);
+        });
+}
+
 extern "C" int mpc_hessvec_batch_device(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                         const double* U, const double* lam, int M, const double* V, int mode, double* HV,
                                         double* JV, double* curv, double* summary, void* stream) {
-    int rc = hessvec_args(c, B, x0, obs, U, M, V, mode);
-    if (rc || B == 0) return rc;
-    if ((rc = device_args(c, obs, n_obs, {x0, obs, U, lam, V, HV, JV, curv, summary}))) return rc;
-    if (!HV && !JV && !curv && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->hessvec_batch(c->p, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary);
-        });
-    KParams kp = kparams(&c->p);
-    const int rw = 7 + c->p.max_obs;       // lam and JV keep the context's slab width without obstacles too
-    if (!obs) kp.max_obs = 0;
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    // one wavefront per instance; the pass width and the actual N size its LDS
-    const int W = hv_pass_width(kp.N);
-    const size_t lds = sizeof(double) * (size_t)hv_lds_doubles(kp.N, W);
-    for_gl_obs(W, obs != nullptr, [&](auto w, auto ob) {
-        constexpr int WV = decltype(w)::value == 32 ? 32 : 64;
-        hipLaunchKernelGGL((mpc_hessvec_kernel<WV, decltype(ob)::value>), dim3(B), dim3(WAVE), lds, (hipStream_t)stream,
-                           c->tab, kp, B, rw, x0, obs, obs ? n_obs : nullptr, U, lam, M, V, mode, HV, JV, curv, summary);
-    });
-    HIPCHK(hipGetLastError(), MPC_E_LAUNCH);
-    return MPC_SUCCESS;
+    return hessvec_entry(c, false, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary, stream);
 }
 
 extern "C" int mpc_hessvec_batch(mpc_ctx* c, int B, const double* x0, const double* obs, const int* n_obs,
                                  const double* U, const double* lam, int M, const double* V, int mode, double* HV,
                                  double* JV, double* curv, double* summary) {
-    int rc = hessvec_args(c, B, x0, obs, U, M, V, mode);
-    if (rc || B == 0) return rc;
-    if (!HV && !JV && !curv && !summary) return MPC_SUCCESS;
-    if (c->cpu)
-        return host_call([&] {
-            c->cpu->hessvec_batch(c->p, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary);
-        });
-    HIPCHK(hipSetDevice(c->device), MPC_E_DEVICE);
-    const size_t nb = (size_t)B, N = (size_t)c->p.N, mo = (size_t)c->p.max_obs, nm = nb * (size_t)M;
-    double *d_x0, *d_obs, *d_U, *d_lam, *d_V, *d_HV, *d_JV, *d_curv, *d_sum;
-    int* d_nobs;
-    return staged_call(c, "hipMalloc hessvec staging", [&](staging::Staging& S) {
-        d_x0 = S.in(x0, nb * 5);
-        d_obs = S.in(obs, nb * mo * 2);
-        d_nobs = obs ? S.in(n_obs, nb) : nullptr;
-        d_U = S.in(U, nb * N * 2);
-        d_lam = S.in(lam, nb * N * (7 + mo));
-        d_V = S.in(V, nm * N * 2);
-        d_HV = S.out(HV, nm * N * 2);
-        d_JV = S.out(JV, nm * N * (7 + mo));
-        d_curv = S.out(curv, nm * 2);
-        d_sum = S.out(summary, nb * MPC_HV_NQ);
-    }, [&] {
-        return mpc_hessvec_batch_device(c, B, d_x0, d_obs, d_nobs, d_U, d_lam, M, d_V, mode, d_HV, d_JV, d_curv, d_sum,
-                                        (void*)c->stream);
-    });
+    return hessvec_entry(c, true, B, x0, obs, n_obs, U, lam, M, V, mode, HV, JV, curv, summary, nullptr);
 }
 
 extern "C" void mpc_default_fsm(mpc_fsm* f) {

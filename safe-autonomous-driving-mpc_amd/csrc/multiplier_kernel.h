@@ -3,9 +3,9 @@
 // state.
 //
 // One wavefront per instance (the Gram matrix and the factorisation want a lane per active row, up to 64 of them).
-// The first phase is the gradient kernel's: predict_grp rolls the instance out, lane j = 0..N-1 owns control j and
-// A_j, lane j = 1..N owns stage j: its rows (ev_stage, parked in LDS), its stage gradient q_j; lane 0 runs the cost's
-// reverse sweep in place and lane j forms grad[j].  The stage lanes count their active rows; a prefix over the counts
+// The first phase is the shared phase (evaluator_common.h) without cost terms and row weights: predict_grp rolls the
+// instance out, lane j = 0..N-1 owns control j and A_j, lane j = 1..N owns stage j: its rows (ev_stage, parked in
+// LDS), its stage gradient q_j; lane 0 runs the cost's reverse sweep in place and lane j forms grad[j].  The stage lanes count their active rows; a prefix over the counts
 // gives every stage its place in the list, which it fills in the reference's order.  Lane a then owns active row a:
 // it runs the row's own reverse chain over the LDS-resident A_k (mu_row_chain) and parks j_a in LDS, forms row a of
 // the Gram matrix (columns b <= a) and r[a], and holds row a through the right-looking factorisation: after column c
@@ -22,7 +22,7 @@
 // conflict-free too) and G / L [64][65] by column.  The rows [N][rw] live in J's space until the list is built, and
 // the lam slab is assembled there at the end.  52.2 KB (GL = 16), 71.3 KB (GL = 32), 109.4 KB (GL = 64) per wavefront.
 #pragma once
-#include "device_common.h"
+#include "evaluator_common.h"
 
 #define MU_JS 65     // the lane stride of J's and G's columns (doubles)
 
@@ -59,37 +59,22 @@ mpc_multipliers_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __
     double* rowsb = J;
     const double qnan = __builtin_nan("");
 
-    double x0[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) x0[j] = x0g[5 * (size_t)b + j];
-    // the obstacle count as the solver reads it: NULL = all max_obs rows, clamped to [0, max_obs]
-    int nobs = 0;
-    const double* obs = nullptr;
-    if (OBS) {
-        nobs = nobsg ? nobsg[b] : Pr.max_obs;
-        nobs = nobs < 0 ? 0 : (nobs > Pr.max_obs ? Pr.max_obs : nobs);
-        obs = obsg + (size_t)b * Pr.max_obs * 2;
-    }
-
-    const bool ctrl = ln < N;                  // this lane owns control ln and A_ln
-    const bool stage = ln >= 1 && ln <= N;     // this lane owns stage ln
-    double u1 = 0.0, u2 = 0.0;
-    if (ctrl) {
-        u1 = Ug[(size_t)b * n2 + 2 * ln];
-        u2 = Ug[(size_t)b * n2 + 2 * ln + 1];
-        gradv[2 * ln] = u1;
-        gradv[2 * ln + 1] = u2;
-    }
-    wave_sync();
-    double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, sl[4] = {0.0, 0.0, 0.0, 0.0};
-    predict_grp(tab, N, dt, x0, gradv, Xr, kap, ln, st, sl);
-    // lane 0 read U from gradv before predict_grp's first barrier; gradv is free from here on
-
-    // ---- A_ln and the free test, then stage ln: its rows, q and its count of active rows ----
+    // ---- the shared phase (evaluator_common.h): the instance, its rollout (U is staged in gradv) and the
+    // linearisation without cost terms and without weighted rows: A_ln, then stage ln's rows (kept in LDS) and q ----
+    const EvcLds L{Xr, kap, nullptr, As, qs, nullptr};
+    EvcInst I;
+    evc_instance<OBS>(Pr, b, x0g, obsg, nobsg, I);
+    evc_rollout<true>(tab, Pr, b, ln, Ug, gradv, L, I);
+    const bool ctrl = I.ctrl, stage = I.stage;
+    const double u1 = I.u1, u2 = I.u2;
+    const int nobs = I.nobs;
+    EvRun run = ev_run_begin();
     GrRun gr = gr_run_begin();
+    evc_linearise<false, false>(Pr, b, rw, ln, L, I, nullptr, rowsb, run, gr);
+
+    // ---- the free test of control ln, and stage ln's count of active rows ----
     bool f0 = false, f1 = false;
     if (ctrl) {
-        stage_A(Xr + 5 * ln, dt, st[3], sl[2], As + 5 * ln);
         f0 = mu_free(u1, Pr.u_min0, Pr.u_max0, bound_tol);
         f1 = mu_free(u2, Pr.u_min1, Pr.u_max1, bound_tol);
         freem[2 * ln] = f0;
@@ -98,12 +83,7 @@ mpc_multipliers_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __
     int mycnt = 0;
     bool rownan = false;             // a NaN row is never active, and it makes the instance MPC_MU_NONFINITE
     if (stage) {
-        EvRun run = ev_run_begin();
-        EvStage S = ev_stage_begin();
-        double ct3[3], cd[5];
-        double* ro = rowsb + (ln - 1) * rw;
-        ev_stage(Pr, ln, Xr + 5 * ln, st, obs, nobs, rw, ct3, ro, S, run);
-        gr_stage(Pr, ln, Xr + 5 * ln, st, sl, obs, nobs, nullptr, qs + 5 * (ln - 1), cd, gr);
+        const double* ro = rowsb + (ln - 1) * rw;
         for (int i = 0; i < 7 + nobs; ++i) {
             const double g = ro[mu_list_col(i, nobs)];
             mycnt += mu_active(g, active_tol) ? 1 : 0;
@@ -111,13 +91,10 @@ mpc_multipliers_kernel(DevTable tab, KParams Pr, int B, int rw, const double* __
         }
     }
     cnt[ln] = mycnt;
-    wave_sync();
 
-    // ---- the cost's reverse sweep (lane 0), and the list: a prefix over the stage counts places every stage ----
-    if (ln == 0) {
-        double g0[5];
-        gr_sweep(N, dt, As, qs, g0);
-    }
+    // ---- the cost's reverse sweep (the shared phase's, lane 0), and the list: a prefix over the stage counts places
+    // every stage ----
+    evc_sweeps(N, dt, ln, L, false, nullptr);
     int off = 0, na = 0;
     for (int j = 1; j <= N; ++j) {
         const int cj = cnt[j];

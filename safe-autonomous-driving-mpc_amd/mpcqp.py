@@ -420,18 +420,16 @@ class Solver:
         _check(lib().mpc_solve_batch_device(self.h, int(B), x0_ptr, obs_ptr, nobs_ptr, ubar_ptr, u0_ptr, U_ptr,
                                             X_ptr, st_ptr, it_ptr, C.c_void_p(stream)), "mpc_solve_batch_device")
 
-    def evaluate_batch(self, x0, U, obs=None, n_obs=None, rows=False):
-        """mpc_evaluate_batch: the reference's measures of ANY control sequences U [B,N,2] from x0 [B,5] (obs, n_obs
-        as in solve_batch).  Returns dict(Xpred [B,N+1,5] = predict(x0, U), summary [B,10] (columns EVQ_FIELDS:
-        cost, min / argmin of the constraint rows, L1 violation, negative rows, minima per row family, box
-        excess), terms [B,5] (cost shares d, o, v, u1, u2)) and, with rows=True, rows [B,N,7+max_obs] (columns:
-        six lane rows, v, the obstacles, NaN past n_obs; constraint_rows() gives the reference's vector)."""
+    def _batch_inputs(self, x0, U, obs, n_obs, lam, what):
+        """The inputs the evaluators share, as the library takes them: (B, N, max_obs, x0 [B,5], U [B,N,2],
+        obs [B,max_obs,2] or None, n_obs [B] int32 or None (the library reads None as all max_obs rows; n_obs travels
+        only with obs), lam [B,N,7+max_obs] or None).  `what` ends the refusal of a missing U."""
         p = self.params
         N, mo = p.N, p.max_obs
         x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
         B = x0.shape[0]
         if U is None:
-            raise ValueError("U is required: the control sequences to evaluate")
+            raise ValueError(f"U is required: the control sequences to {what}")
         U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
         if obs is not None and np.asarray(obs).size > 0 and mo == 0:
             raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
@@ -440,6 +438,17 @@ class Solver:
             n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
         else:
             obs, n_obs = None, None
+        if lam is not None:
+            lam = np.ascontiguousarray(lam, np.float64).reshape(B, N, 7 + mo)
+        return B, N, mo, x0, U, obs, n_obs, lam
+
+    def evaluate_batch(self, x0, U, obs=None, n_obs=None, rows=False):
+        """mpc_evaluate_batch: the reference's measures of ANY control sequences U [B,N,2] from x0 [B,5] (obs, n_obs
+        as in solve_batch).  Returns dict(Xpred [B,N+1,5] = predict(x0, U), summary [B,10] (columns EVQ_FIELDS:
+        cost, min / argmin of the constraint rows, L1 violation, negative rows, minima per row family, box
+        excess), terms [B,5] (cost shares d, o, v, u1, u2)) and, with rows=True, rows [B,N,7+max_obs] (columns:
+        six lane rows, v, the obstacles, NaN past n_obs; constraint_rows() gives the reference's vector)."""
+        B, N, mo, x0, U, obs, n_obs, _ = self._batch_inputs(x0, U, obs, n_obs, None, "evaluate")
         X = np.empty((B, N + 1, 5)); summary = np.empty((B, EV_NQ)); terms = np.empty((B, 5))
         R = np.empty((B, N, 7 + mo)) if rows else None
         _check(lib().mpc_evaluate_batch(self.h, B, _p(x0), _p(obs), _pi(n_obs), _p(U), _p(X), _p(summary), _p(terms),
@@ -462,22 +471,7 @@ class Solver:
         gx0 [B,5] = d cost / d x0, summary [B,6] (columns GRQ_FIELDS: cost, max |grad|, max |grad - jtl|, the
         projected-gradient measure, max |lam g|, min lam)) and, with lam, jtl [B,N,2] = J' lam of the constraint
         rows; with costate=True, costate [B,N,5] = p_1..p_N of the cost."""
-        p = self.params
-        N, mo = p.N, p.max_obs
-        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
-        B = x0.shape[0]
-        if U is None:
-            raise ValueError("U is required: the control sequences to differentiate at")
-        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
-        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
-            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
-        if obs is not None and mo > 0:
-            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
-            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
-        else:
-            obs, n_obs = None, None
-        if lam is not None:
-            lam = np.ascontiguousarray(lam, np.float64).reshape(B, N, 7 + mo)
+        B, N, mo, x0, U, obs, n_obs, lam = self._batch_inputs(x0, U, obs, n_obs, lam, "differentiate at")
         grad = np.empty((B, N, 2)); gx0 = np.empty((B, 5)); summary = np.empty((B, GR_NQ))
         jtl = np.empty((B, N, 2)) if lam is not None else None
         P = np.empty((B, N, 5)) if costate else None
@@ -507,20 +501,7 @@ class Solver:
         (stage - 1) * (7 + max_obs) + column, -1 past the count), summary [B,6] (columns MUQ_FIELDS: status MU_*,
         active rows, free components, rows kept, least-squares residual, least pivot ratio)); `outputs` names the
         ones to compute."""
-        p = self.params
-        N, mo = p.N, p.max_obs
-        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
-        B = x0.shape[0]
-        if U is None:
-            raise ValueError("U is required: the control sequences to estimate the multipliers at")
-        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
-        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
-            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
-        if obs is not None and mo > 0:
-            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
-            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
-        else:
-            obs, n_obs = None, None
+        B, N, mo, x0, U, obs, n_obs, _ = self._batch_inputs(x0, U, obs, n_obs, None, "estimate the multipliers at")
         out = {}
         if "lam" in outputs:
             out["lam"] = np.empty((B, N, 7 + mo))
@@ -549,13 +530,7 @@ class Solver:
         H v, JV [B,M,N,7+max_obs] = J v in the layout of evaluate_batch's rows, curv [B,M,2] = (v'Hv, v'v),
         summary [B,5] (columns HVQ_FIELDS: cost, min and max Rayleigh quotient, its first minimising direction, the
         directions of negative curvature)); `outputs` names the ones to compute."""
-        p = self.params
-        N, mo = p.N, p.max_obs
-        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
-        B = x0.shape[0]
-        if U is None:
-            raise ValueError("U is required: the control sequences to differentiate at")
-        U = np.ascontiguousarray(U, np.float64).reshape(B, N, 2)
+        B, N, mo, x0, U, obs, n_obs, lam = self._batch_inputs(x0, U, obs, n_obs, lam, "differentiate at")
         if V is not None:
             V = np.ascontiguousarray(V, np.float64)
             M = V.size // max(B * N * 2, 1) if M is None else int(M)
@@ -563,15 +538,6 @@ class Solver:
         elif M is None:
             M = 2 * N
         M = int(M)
-        if obs is not None and np.asarray(obs).size > 0 and mo == 0:
-            raise ValueError("obstacles given but params.max_obs == 0: set max_obs to the slab width")
-        if obs is not None and mo > 0:
-            obs = np.ascontiguousarray(obs, np.float64).reshape(B, mo, 2)
-            n_obs = None if n_obs is None else np.ascontiguousarray(n_obs, np.int32).reshape(B)
-        else:
-            obs, n_obs = None, None
-        if lam is not None:
-            lam = np.ascontiguousarray(lam, np.float64).reshape(B, N, 7 + mo)
         Mo = max(M, 0)
         shapes = dict(HV=(B, Mo, N, 2), JV=(B, Mo, N, 7 + mo), curv=(B, Mo, 2), summary=(B, HV_NQ))
         out = {k: np.empty(shapes[k]) for k in shapes if k in outputs}

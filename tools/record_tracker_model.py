@@ -9,6 +9,7 @@ Only the public mpcqp.Solver API is used, so the script runs on any commit that 
     python tools/record_tracker_model.py                 # record from the library built in the tree (one GPU)
     python tools/record_tracker_model.py --lib PATH      # ... from another build of libmpcqp.so (an earlier commit's)
     python tools/record_tracker_model.py --verify        # run again, compare, exit 1 on a difference
+    python tools/record_tracker_model.py --derivatives   # the second file (below) instead; needs hessvec_batch
 
 The batches (built-in trajectory 1, seed 29): for N = 5, 15, 16, 31, 32 (both sides of the lane-group boundaries
 GL = 16 / 32 / 64) B = 5 instances (a spare lane group repeats the last one at GL = 16 and 32), each evaluated with
@@ -16,7 +17,15 @@ max_obs = 0 and with max_obs = 3 and n_obs = (0, 1, 3, 3, 1); at N = 16 once mor
 starts below s[0], instance 1 leaves the control box, instance 3 has a NaN in U, instance 4 rolls past s_max.  Then
 lookup and global_pose at 40 abscissae: both table ends and their neighbours, below s[0], at and past s_max, exact
 knots and their neighbours, the end of the control table, a NaN, and points inside.  Stored are the inputs and every
-output (Xpred, summary, terms, rows; state, control, pose)."""
+output (Xpred, summary, terms, rows; state, control, pose).
+
+--derivatives records the evaluator's three siblings the same way, into tests/golden/tracker_derivatives_device.npz:
+gradient_batch, multipliers_batch and hessvec_batch on the same five instances (seed 31) for N = 15, 16, 32 (one per
+lane-group class), each with max_obs = 0 and with max_obs = 3 and n_obs = (0, 1, 3, 3, 1).  The gradient with a seeded
+lam and the costate, and once without lam.  The multipliers at the default active_tol and at two steered ones, just
+above a tenth and four tenths of the batch's finite rows (evaluate_batch's), which give short lists kept whole, lists
+with dropped rows and overflowing ones.  The products with that lam in both modes for M = 2 seeded directions, and for
+the unit directions e_0..e_2 (V None); and once at N = 57, the first horizon of the 32-wide pass, for B = 2, M = 2."""
 import argparse
 import json
 import os
@@ -36,6 +45,13 @@ MAX_OBS = 3
 N_OBS = (0, 1, 3, 3, 1)
 N_NULL = 16                      # the horizon of the call with n_obs = NULL
 OUTPUTS = ("Xpred", "summary", "terms", "rows")
+
+DERIV_GOLDEN = os.path.join(ROOT, "tests", "golden", "tracker_derivatives_device.npz")
+DERIV_HORIZONS = (15, 16, 32)
+DERIV_M, DERIV_UNIT_M = 2, 3
+DERIV_STEER = (0.1, 0.4)         # the steered active_tol: just above these shares of the batch's finite rows
+DERIV_N32PASS, DERIV_B32PASS = 57, 2
+DERIV_MODES = ("exact", "gauss_newton")
 
 
 def batch(traj, N, rng):
@@ -100,8 +116,50 @@ def run(device=0):
     return out
 
 
-def load():
-    with np.load(GOLDEN) as z:
+def run_derivatives(device=0):
+    """every derivative batch on `device`: {name: array} of the inputs and outputs"""
+    import mpcqp
+    from trajectory_loader import TrajectoryLoader, builtin_trajectory
+    traj = TrajectoryLoader(builtin_trajectory(1))
+    rng = np.random.default_rng(31)
+    out = {}
+
+    def put(prefix, r):
+        out.update({f"{prefix}_{k}": np.asarray(v) for k, v in r.items()})
+
+    for N in DERIV_HORIZONS + (DERIV_N32PASS,):
+        x0, U, obs = batch(traj, N, rng)
+        nb = DERIV_B32PASS if N == DERIV_N32PASS else B
+        x0, U, obs = x0[:nb], U[:nb], obs[:nb]
+        V = rng.normal(0.0, 1.0, (nb, DERIV_M, N, 2))
+        out.update({f"N{N}_x0": x0, f"N{N}_U": U, f"N{N}_obs": obs, f"N{N}_V": V})
+        for tag, mo, o, no in (("mo0", 0, None, None), (f"mo{MAX_OBS}", MAX_OBS, obs, np.array(N_OBS[:nb], np.int32))):
+            lam = rng.uniform(0.0, 2.0, (nb, N, 7 + mo))
+            out[f"N{N}_{tag}_lam"] = lam
+            if N == DERIV_N32PASS and mo == 0:
+                continue
+            slv = mpcqp.Solver(traj.X_ref, traj.U_ref, mpcqp.default_params(N=N, max_obs=mo), device=device)
+            if N == DERIV_N32PASS:
+                put(f"N{N}_{tag}_hv_exact", slv.hessvec_batch(x0, U, V, None, lam, o, no, "exact"))
+                slv.close()
+                continue
+            put(f"N{N}_{tag}_gr", slv.gradient_batch(x0, U, o, no, lam=lam, costate=True))
+            put(f"N{N}_{tag}_gr_nolam", slv.gradient_batch(x0, U, o, no))
+            rows = slv.evaluate_batch(x0, U, o, no, rows=True)["rows"]
+            v = np.sort(rows[np.isfinite(rows)])
+            tols = np.array([1e-6] + [float(v[int(q * len(v))]) + 1e-7 for q in DERIV_STEER])
+            out[f"N{N}_{tag}_mu_tols"] = tols
+            for i, tol in enumerate(tols):
+                put(f"N{N}_{tag}_mu{i}", slv.multipliers_batch(x0, U, o, no, active_tol=float(tol)))
+            for mode in DERIV_MODES:
+                put(f"N{N}_{tag}_hv_{mode}", slv.hessvec_batch(x0, U, V, None, lam, o, no, mode))
+            put(f"N{N}_{tag}_hv_unit", slv.hessvec_batch(x0, U, None, DERIV_UNIT_M, lam, o, no, "exact"))
+            slv.close()
+    return out
+
+
+def load(path=GOLDEN):
+    with np.load(path) as z:
         return {k: z[k] for k in z.files if k != "meta_json"}
 
 
@@ -118,15 +176,18 @@ def main():
     ap.add_argument("--commit", default="", help="the commit that build was made from (stored in the metadata)")
     ap.add_argument("--gpu", default="", help="the device's name (metadata)")
     ap.add_argument("--rocm", default="", help="the ROCm version (metadata)")
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--derivatives", action="store_true", help="record / verify the derivatives' file instead")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--verify", action="store_true")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = DERIV_GOLDEN if a.derivatives else GOLDEN
     import mpcqp
     if a.lib:
         mpcqp.LIB_PATH = os.path.abspath(a.lib)
-    got = run(a.device)
+    got = run_derivatives(a.device) if a.derivatives else run(a.device)
     if a.verify:
-        d = differences(got, load())
+        d = differences(got, load(a.out))
         print(f"{len(d)} differing arrays of {len(got)}:", d)
         sys.exit(1 if d else 0)
     meta = dict(generator="tools/record_tracker_model.py", commit=a.commit, gpu=a.gpu, rocm=a.rocm,
